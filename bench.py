@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the SmoothNMF multiplicative-update loop on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): MU iterations / second on the 2048-channel x (512*512)-pixel X, k = 5, SmoothNMF with simplex
 on H and Laplacian smoothness (lambda = 1), fp32 arithmetic; the counts are held in the store the engine selects for
@@ -11,8 +11,16 @@ changes the reference book-keeps every iteration (espm/estimators/base.py:316-35
 sharded over the ranks (strong scaling: same total problem).  W warm-up iterations, then exactly K timed iterations
 between barrier + synchronize on both sides, maximum over ranks.
 
-Prints ONE JSON line on rank 0.  Beside the contract's fields:
-  roofline      the dominant kernel (the fused H update + W accumulation launch): algorithmic bytes per launch over its duration, measured live with HIP
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the contract's fields (metric, value,
+unit, n_gpus, steps, warmup, ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config) and nothing else.
+
+--dump-outputs DIR  after the timed steps, what they computed, as a caller of the loop reads it back: DIR/W.npy (n x k, float32), DIR/H.npy
+                (k x pixels, float32; the ranks' blocks joined in pixel order) and DIR/loss.npy (float64: the loss of the state each timed
+                step started from).  The inputs (image, W0, H0) are drawn from fixed seeds: the same arguments give the same inputs.
+
+--full adds everything else (--no-cpu, --no-cpu-full and --no-extras trim it):
+  loss_first, loss_last, nonfinite  the loss of the initial and of the final state, non-finite entries of the history
+  roofline     the dominant kernel (the fused H update + W accumulation launch): algorithmic bytes per launch over its duration, measured live with HIP
                 events on the launch stream inside the library's own loop (espm_mu_iterate_timed).  `launch_ms` = the timed region's step minus the launch
                 that follows the fused one (that launch between events: `second_launch_ms`) - what the fused launch occupies of the timed loop, so
                 `fits_in_step` holds by construction; `launch_ms_event_brackets` = the fused launch between its own events (every bracket serialises the
@@ -156,14 +164,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline / parity leg")
-    ap.add_argument("--no-cpu-full", action="store_true", help="CPU baseline from the 64-row crop only (skip the ~25 s full-size iteration)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the dense-store and steady-state legs (profiling runs)")
+    ap.add_argument("--full", action="store_true", help="also the CPU baseline and parity, the other stores, sizes and fits, the roofline and "
+                                                         "per-rank figures and the loss check (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write W, H and the timed steps' losses as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline / parity leg")
+    ap.add_argument("--no-cpu-full", action="store_true", help="with --full: CPU baseline from the 64-row crop only (skip the ~25 s full-size iteration)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the dense-store and steady-state legs (profiling runs)")
     ap.add_argument("--lambda-l", type=float, default=LAMBDA_L)
     ap.add_argument("--x-store", default="auto", choices=["auto", "ell", "u8", "bf16", "f32"])
     ap.add_argument("--no-autotune", action="store_true", help="keep the default launch plan instead of timing the candidates at set-up")
     ap.add_argument("--no-fused", action="store_true", help="two launches per iteration pair instead of the fused kernel (A/B)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # host thread pools no larger than the CPUs the container grants (espm_amd/_cpu_budget.py: pools sized by the 256 visible cores
     # exhaust a 16-CPU quota, and a throttled host cannot feed the device)
@@ -215,7 +228,7 @@ def main():
         group = dist.group.WORLD
 
     from espm_amd import _lib, synth
-    from espm_amd.engine import MUEngine, _stream
+    from espm_amd.engine import MUEngine
     import ctypes as C
 
     # ---- synthetic data: this rank's block of image rows.  Host-side preparation first, the device work (sampling, list
@@ -228,12 +241,12 @@ def main():
     W0, H0_full = synth.random_init(N_CH, K, NX * NY, seed=0, scale=COUNTS / N_CH)
     H0 = H0_full[:, row0 * NY:(row0 + rows) * NY]
     del H0_full
-    if world > 1:   # the start-up self-test of the one-shot record exchange (espm_amd/sharding.py) at full length: reported below
+    if world > 1 and args.full:   # the start-up self-test of the one-shot record exchange (espm_amd/sharding.py) at full length: reported below
         os.environ.setdefault("ESPM_XCHG_SELFTEST", "1000")
     total_iters = args.warmup + args.steps
     W0d, H0d = torch.from_numpy(W0).to(device, torch.float32), torch.from_numpy(H0).to(device, torch.float32)
     X = synth.sample_torch(prob, device, seed=1000, row0=row0)            # (p_local, n) f32 counts
-    X_crop = X[:CROP_ROWS * NY].cpu().numpy() if (rank == 0 and world == 1 and not args.no_cpu) else None
+    X_crop = X[:CROP_ROWS * NY].cpu().numpy() if (args.full and rank == 0 and world == 1 and not args.no_cpu) else None
     # The engine is built the way SmoothNMF(max_iter=FIT_LENGTH).fit builds it - autotune="auto": MUEngine's own policy, which times
     # the launch plans at set-up for fits of engine.AUTOTUNE_MIN_ITERS iterations or more (`value` is the
     # product's figure for a fit of that length, not a bench-only configuration; `short_fit` below is the engine of a
@@ -283,19 +296,37 @@ def main():
         eng.iterate(150, final_loss=False)
         eng.load_state(W0d, H0d)
         eng.iterate(args.warmup, final_loss=False)
+    def capture_outputs():
+        """What the timed steps computed, read back as a caller of the loop reads it: W, H (every rank's block, joined in pixel
+        order) and the loss of the state each timed step started from (slot t of the history: the loss of state t)."""
+        t_end = eng.st.it
+        loss = eng.history(upto=t_end - 1)["loss"][t_end - args.steps:]
+        W, H = eng.get_W(), eng.get_H()
+        if world > 1:
+            blocks = [None] * world
+            torch.distributed.all_gather_object(blocks, H)
+            H = np.concatenate(blocks, axis=1)
+        return dict(W=np.asarray(W, dtype=np.float32), H=np.asarray(H, dtype=np.float32), loss=np.asarray(loss, dtype=np.float64))
+
     def timed_legs():
         trace(f"timed legs on {eng.exchange.transport if world > 1 else 'one GPU'}")
         dt_ = timed(args.steps)
         trace("timed steps done")
+        outputs_ = None
+        if args.dump_outputs:
+            try:
+                outputs_ = capture_outputs()
+            except _lib.LostPeerError:   # (jointly on every rank: the run is timed again on the collective transport below)
+                outputs_ = None
         steady_ = None
-        if not args.no_extras:
+        if args.full and not args.no_extras:
             n_ss = 300
             steady_ = dict(steps=n_ss, value=n_ss / timed(n_ss), unit="it/s",
                            note="300 further iterations, same bracket: the device clocks have ramped by then")
         # ---- N > 1: every rank's launch times (HIP events on the launch stream), so that a scaling curve can be read: the local
         # half-steps against the W step that holds the record exchange - a rank that waits for a slower peer shows it there ----
         mine_ = None
-        if world > 1:
+        if world > 1 and args.full:
             hs, ws = eng.timed_iterations(40)
             torch.cuda.synchronize()
             trace("per-launch timing done")
@@ -332,9 +363,9 @@ def main():
                                                   f"self-test at start-up: lost {sr.get('lost')}, corrupt {sr.get('corrupt')}" if sr.get("fell_back_from") and (sr.get("lost") or sr.get("corrupt"))
                                                   else "a bounded wait gave up during the run (ranks sharing a device, or a peer that did not deliver)" if sr.get("n") else
                                                   "the one-shot exchange could not be opened (hipIpc peer mapping)"))
-        return dt_, steady_, mine_
+        return dt_, steady_, mine_, outputs_
 
-    dt, steady, mine = timed_legs()
+    dt, steady, mine, outputs = timed_legs()
     if world > 1 and eng.exchange.ctx is not None:
         # a bounded wait of the one-shot exchange can also give up AFTER a clean warm-up (ranks that share a device stall
         # each other depending on who is resident when: profiles/r04c_*): the health is asked again behind the timed legs, jointly, and
@@ -349,12 +380,106 @@ def main():
             eng.load_state(W0d, H0d)
             trace("state reloaded")
             eng.iterate(args.warmup, final_loss=False)
-            dt, steady, mine = timed_legs()
+            dt, steady, mine, outputs = timed_legs()
     its = args.steps / dt
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
     per_rank = None
-    if world > 1:
+    if world > 1 and args.full:
         per_rank = [None] * world
         torch.distributed.all_gather_object(per_rank, mine)
+
+    # ---- facts of the stored image the line's config reports (host-side, no device work beyond a one-number reduction) ----
+    st = eng.st
+    lib = eng.lib
+    fused = bool(lib.espm_mu_fused_applies(C.byref(st)))
+    p_loc = eng.p
+    if eng.x_store == "ell":
+        nnz_loc = float(eng.ell["nnz"])
+        nnz = torch.tensor([nnz_loc], dtype=torch.float64, device=device)
+        if world > 1:
+            torch.distributed.all_reduce(nnz)
+        nnz_total = float(nnz.item())
+        nnz_frac = nnz_total / (float(N_CH) * NX * NY)
+    else:
+        nnz_frac = None
+    roofline = dense = product_default = whole_fit = c5 = None
+    if args.full:
+        loss_first, loss_last, bad, roofline, dense, product_default, whole_fit, c5 = full_legs(
+            args, eng, X, W0d, H0d, rows, world, device, dt, its, fused, p_loc, nnz_total if eng.x_store == "ell" else None, total_iters)
+
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "MU iterations/sec, 2048ch x (512*512)px X, k=5 SmoothNMF",
+            "value": its, "unit": "it/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "2048ch x (512x512)px, k=5, SmoothNMF simplex_H + Laplacian lambda=%g, "
+                                   "X stored %s, W/H fp32" % (args.lambda_l, eng.x_store),
+                       "n": N_CH, "shape_2d": [NX, NY], "k": K, "lambda_L": args.lambda_l, "simplex_H": True,
+                       "parallelism": f"pixel-row shard x{world}" if world > 1 else "single GPU",
+                       "process_group": (dict(backend=backend, fell_back_from=backend_fell_back, ranks_per_device=max(1, world // max(torch.cuda.device_count(), 1)))
+                                         if world > 1 else None),
+                       "record_exchange": (dict(eng.exchange.selftest_result or {}, transport=transport) if world > 1 else None),
+                       "autotune": bool(eng.plan_timings is not None), "engine_policy": f"autotune='auto', as SmoothNMF(max_iter={FIT_LENGTH}).fit builds it",
+                       "per_rank": per_rank,
+                       "loss_every_iteration": True, "launches_per_iteration": 2 if fused else 3,
+                       "launch_plan": getattr(eng, "plan", None), "launch_plan_timings_us": eng.plan_timings,
+                       "nnz_frac": nnz_frac, "counts_per_pixel": COUNTS},
+        }
+        if args.full:
+            out.update({"loss_first": loss_first, "loss_last": loss_last, "nonfinite": bad, "roofline": roofline})
+        if steady:
+            out["steady_state"] = steady
+        if dense:
+            out["dense_store"] = dense
+        if product_default:
+            out["short_fit"] = product_default
+        if c5:
+            out["c5"] = c5
+        if whole_fit:
+            out["whole_fit"] = whole_fit
+        if X_crop is not None:
+            # SURVEY 8(d): a full-size faithful iteration where the host can hold it (checked, not assumed)
+            full, skip = None, None
+            try:
+                import psutil
+                avail = psutil.virtual_memory().available / 2 ** 30
+                if avail < 45:
+                    skip = f"{avail:.0f} GiB of host memory available, ~30 GiB of dense fp64 temporaries + copies needed"
+            except Exception as e:   # noqa: BLE001
+                skip = f"psutil: {e}"
+            if skip is None and not args.no_cpu_full:
+                try:
+                    full = cpu_full_size_iteration(X)
+                except MemoryError:
+                    skip = "MemoryError"
+            elif args.no_cpu_full:
+                skip = "--no-cpu-full"
+            out["cpu_baseline"], parity = cpu_baseline_and_parity(X_crop, device, skip_full=skip)
+            if full:
+                cb = out["cpu_baseline"]
+                cb["value"], cb["full_size"] = full["value"], full
+                cb["sample"] = (f"numpy fp64 oracle (reference op sequence: dense identity G, three n x k x p products, global-stop bisection), {full['iterations']} iterations "
+                                f"at the full size ({N_CH} ch x {NX * NY} px, {full['seconds_per_iteration']:.1f} s each); beside it `crop`: {cb['crop']['sample']}")
+            out["loss_parity_rel"] = parity["rel"]
+            out["loss_parity"] = parity
+        print(json.dumps(out), flush=True)
+    del X
+    if world > 1:
+        torch.distributed.barrier()
+        torch.distributed.destroy_process_group()
+
+
+def full_legs(args, eng, X, W0d, H0d, rows, world, device, dt, its, fused, p_loc, nnz_total, total_iters):
+    """--full: the loss check, the roofline / per-kernel timing and the legs on other stores, fits and sizes, after the timed
+    steps (the state has moved on from what --dump-outputs wrote)."""
+    from espm_amd import _lib, synth
+    from espm_amd.engine import MUEngine, _stream
+    import ctypes as C
 
     # ---- loss sanity + per-kernel timing with HIP events on the launch stream (rank-local) --------
     eng.eval_current(advance_h=False)
@@ -380,22 +505,15 @@ def main():
 
     s = _stream()   # torch's current stream IS the launch stream of every call below
     lib = eng.lib
-    fused = bool(lib.espm_mu_fused_applies(C.byref(st)))
-    p_loc = eng.p
     if eng.x_store == "ell":
         e_h, e_w = eng.ell["entries_h"], eng.ell["entries_w"]
         nnz_loc = float(eng.ell["nnz"])
-        nnz = torch.tensor([nnz_loc], dtype=torch.float64, device=device)
-        if world > 1:
-            torch.distributed.all_reduce(nnz)
-        nnz_total = float(nnz.item())
         bytes_it = 2 * nnz_total + 2 * K * NX * NY * 4             # SURVEY 8(d) with X = its non-zero entries (2 B each), once; H read + written
         flops_it = 8.0 * K * nnz_total                             # four products restricted to the non-zero entries
         bytes_h = 2 * e_h + 2 * K * p_loc * 4 + p_loc * 4          # H-step alone: its lists once, H read + written, the loss constants
         bytes_w = 2 * e_w + K * p_loc * 4                          # W accumulation alone: its lists once, H read
         bytes_fused_once = 2 * nnz_loc + 2 * K * p_loc * 4         # the fused launch by 8(d)'s count: X once, H read + written
         bytes_fused_lists = 2 * (e_h + e_w) + 2 * K * p_loc * 4 + p_loc * 4   # what it streams: both list sets (splits of counts > their field included)
-        nnz_frac = nnz_total / (float(N_CH) * NX * NY)
     else:
         xbytes = {"u8": 1, "bf16": 2, "f32": 4}[eng.x_store]
         bytes_h = N_CH * p_loc * xbytes + 2 * K * p_loc * 4
@@ -403,7 +521,6 @@ def main():
         bytes_it = N_CH * NX * NY * xbytes + 2 * K * NX * NY * 4
         flops_it = 8.0 * N_CH * K * NX * NY
         bytes_fused_once = bytes_fused_lists = None
-        nnz_frac = None
     traffic = traffic_source = None
     try:
         with open(os.path.join(ROOT, "profiles", "hbm_traffic.json")) as f:
@@ -545,69 +662,7 @@ def main():
                                   frac_lists_twice=(2 * (e5.ell["entries_h"] + e5.ell["entries_w"]) + 2 * k5 * nx5 * ny5 * 4 + nx5 * ny5 * 4) / t5 / HBM_PEAK,
                                   nnz_frac=float(e5.ell["nnz"]) / (float(n5) * nx5 * ny5))
         del e5
-
-    out = None
-    if rank == 0:
-        out = {
-            "metric": "MU iterations/sec, 2048ch x (512*512)px X, k=5 SmoothNMF",
-            "value": its, "unit": "it/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "2048ch x (512x512)px, k=5, SmoothNMF simplex_H + Laplacian lambda=%g, "
-                                   "X stored %s, W/H fp32" % (args.lambda_l, eng.x_store),
-                       "n": N_CH, "shape_2d": [NX, NY], "k": K, "lambda_L": args.lambda_l, "simplex_H": True,
-                       "parallelism": f"pixel-row shard x{world}" if world > 1 else "single GPU",
-                       "process_group": (dict(backend=backend, fell_back_from=backend_fell_back, ranks_per_device=max(1, world // max(torch.cuda.device_count(), 1)))
-                                         if world > 1 else None),
-                       "record_exchange": (dict(eng.exchange.selftest_result or {}, transport=transport) if world > 1 else None),
-                       "autotune": bool(eng.plan_timings is not None), "engine_policy": f"autotune='auto', as SmoothNMF(max_iter={FIT_LENGTH}).fit builds it",
-                       "per_rank": per_rank,
-                       "loss_every_iteration": True, "launches_per_iteration": 2 if fused else 3,
-                       "launch_plan": getattr(eng, "plan", None), "launch_plan_timings_us": eng.plan_timings,
-                       "nnz_frac": nnz_frac, "counts_per_pixel": COUNTS},
-            "loss_first": loss_first, "loss_last": loss_last, "nonfinite": bad,
-            "roofline": roofline,
-        }
-        if steady:
-            out["steady_state"] = steady
-        if dense:
-            out["dense_store"] = dense
-        if product_default:
-            out["short_fit"] = product_default
-        if c5:
-            out["c5"] = c5
-        if whole_fit:
-            out["whole_fit"] = whole_fit
-        if X_crop is not None:
-            # SURVEY 8(d): a full-size faithful iteration where the host can hold it (checked, not assumed)
-            full, skip = None, None
-            try:
-                import psutil
-                avail = psutil.virtual_memory().available / 2 ** 30
-                if avail < 45:
-                    skip = f"{avail:.0f} GiB of host memory available, ~30 GiB of dense fp64 temporaries + copies needed"
-            except Exception as e:   # noqa: BLE001
-                skip = f"psutil: {e}"
-            if skip is None and not args.no_cpu_full:
-                try:
-                    full = cpu_full_size_iteration(X)
-                except MemoryError:
-                    skip = "MemoryError"
-            elif args.no_cpu_full:
-                skip = "--no-cpu-full"
-            out["cpu_baseline"], parity = cpu_baseline_and_parity(X_crop, device, skip_full=skip)
-            if full:
-                cb = out["cpu_baseline"]
-                cb["value"], cb["full_size"] = full["value"], full
-                cb["sample"] = (f"numpy fp64 oracle (reference op sequence: dense identity G, three n x k x p products, global-stop bisection), {full['iterations']} iterations "
-                                f"at the full size ({N_CH} ch x {NX * NY} px, {full['seconds_per_iteration']:.1f} s each); beside it `crop`: {cb['crop']['sample']}")
-            out["loss_parity_rel"] = parity["rel"]
-            out["loss_parity"] = parity
-        print(json.dumps(out), flush=True)
-    del X
-    if world > 1:
-        torch.distributed.barrier()
-        torch.distributed.destroy_process_group()
+    return loss_first, loss_last, bad, roofline, dense, product_default, whole_fit, c5
 
 
 if __name__ == "__main__":

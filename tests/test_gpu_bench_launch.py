@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "ESPM_BENCH_BACKEND")}
     env["ESPM_XCHG_SELFTEST"] = "64"
-    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--no-extras", "--no-cpu"],
+    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full", "--no-extras", "--no-cpu"],
                         env=env, capture_output=True, text=True, timeout=900)
     assert pr.returncode == 0, pr.stderr[-3000:]
     lines = [ln for ln in pr.stdout.splitlines() if ln.startswith("{")]
@@ -43,7 +43,7 @@ def test_bench_four_ranks_selflaunch_reports_per_rank_diagnostics():
     fallback), and the replicated W has the same checksum on all four ranks."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "ESPM_BENCH_BACKEND")}
     env["ESPM_XCHG_SELFTEST"] = "32"
-    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "6", "--warmup", "2", "--no-extras", "--no-cpu"],
+    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "6", "--warmup", "2", "--full", "--no-extras", "--no-cpu"],
                         env=env, capture_output=True, text=True, timeout=1200)
     assert pr.returncode == 0, pr.stderr[-3000:]
     lines = [ln for ln in pr.stdout.splitlines() if ln.startswith("{")]
@@ -61,6 +61,33 @@ def test_bench_four_ranks_selflaunch_reports_per_rank_diagnostics():
     if log:
         with open(log, "w") as f:
             f.write(lines[0] + "\n")
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) prints the contract's fields and none of the extra legs; --steps is the number of timed steps; with
+    --dump-outputs it writes what those steps computed: W (n x k), H (k x pixels, on the simplex) and their losses."""
+    import numpy as np
+    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs",
+                         str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert pr.returncode == 0, pr.stderr[-3000:]
+    lines = [ln for ln in pr.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, pr.stdout[-2000:]
+    out = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config"):
+        assert key in out, key
+    assert out["steps"] == 7 and out["warmup"] == 2 and out["n_gpus"] == 1 and out["dtype"] == "f32" and out["higher_is_better"] is True
+    assert abs(out["ms_per_step"] * out["value"] / 1e3 - 1.0) < 1e-9
+    for key in ("roofline", "steady_state", "dense_store", "short_fit", "whole_fit", "c5", "cpu_baseline", "loss_parity", "loss_first"):
+        assert key not in out, key
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["H.npy", "W.npy", "loss.npy"], files
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64 << 20
+    W, H, loss = np.load(tmp_path / "W.npy"), np.load(tmp_path / "H.npy"), np.load(tmp_path / "loss.npy")
+    assert W.shape == (2048, 5) and W.dtype == np.float32 and np.isfinite(W).all() and (W >= 0).all()
+    assert H.shape == (5, 512 * 512) and H.dtype == np.float32 and np.isfinite(H).all() and (H >= 0).all()
+    np.testing.assert_allclose(H.sum(axis=0), 1.0, atol=1e-3)
+    assert loss.shape == (7,) and loss.dtype == np.float64 and np.isfinite(loss).all() and loss[-1] < loss[0]
 
 
 def test_bench_refuses_a_world_size_that_contradicts_gpus():

@@ -293,7 +293,7 @@ def test_bench_line_keeps_the_drivers_contract():
     import json
     src = open(os.path.join(ROOT, "bench.py")).read()
     ast.parse(src)
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--dump-outputs", "--full"):
         assert f'"{flag}"' in src, flag
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
                 "data", "config", "roofline"):
