@@ -23,6 +23,8 @@ _HEADER_TEXT = _abi.header_text()
 _D = _abi.parse_defines(_HEADER_TEXT)
 OK, EINVAL, ENOSOLUTION, EHIP, EUNSUPPORTED = 0, -1, -2, -3, -4          # enum espm_status
 X_F32, X_BF16, X_U8, X_ELL = 0, 1, 2, 3                                  # enum ESPM_X_*
+F64_X_U8, F64_X_BF16, F64_X_F32, F64_X_F64 = (_D["ESPM_F64_X_" + n] for n in ("U8", "BF16", "F32", "F64"))
+F64_MAX_K, F64_MAXIT = _D["ESPM_F64_MAX_K"], _D["ESPM_F64_MAXIT"]
 SRC_F32, SRC_F64 = 0, 1
 LAYOUT_CM, LAYOUT_PM = 0, 1
 ABI_VERSION = _D["ESPM_MU_ABI_VERSION"]
@@ -117,6 +119,17 @@ SYMBOLS = {
     "espm_mu_laplacian": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _i64, _vp, _vp]),
     "espm_lu_pl_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "espm_lu_pl": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _i64, _vp, _vp, C.c_size_t, _vp]),
+    # fp64 mode (csrc/mu_fp64.hip): kernels in the narrow build, stubs returning ESPM_EUNSUPPORTED in the wide ones
+    "espm_f64_scratch_doubles": (_i64, [C.c_int, C.c_int, C.c_int, _i64]),
+    "espm_f64_gw": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp]),
+    "espm_f64_hstat": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp]),
+    "espm_f64_h_pass": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_double,
+                                  C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "espm_f64_bisect": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "espm_f64_rel": (C.c_int, [_vp, _vp, _i64, C.c_double, _vp, _vp, _vp]),
+    "espm_f64_w_accum": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp]),
+    "espm_f64_w_finish": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_double, C.c_double,
+                                    C.c_int, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -60,14 +60,26 @@ class MUEngine:
     X : (n, p) array (``layout="cm"``) or (p, n) (``layout="pm"``, hyperspy's layout); numpy or a
         torch tensor (host or device), float32/float64.  When ``group`` is given, X is this rank's
         block of image rows and ``shape_2d`` its local (rows, ny).
+    precision : "fp32" (default) or "fp64" - the latter constructs ``engine_fp64.MUEngineF64`` (every array and operation in
+        fp64, the reference's simplex bisection; one GPU, 1..8 components).
     """
+
+    def __new__(cls, *args, precision="fp32", **kwargs):
+        # precision="fp64": the fp64 engine (espm_amd/engine_fp64.py, csrc/mu_fp64.hip), a subclass with the same methods
+        if precision == "fp64" and cls is MUEngine:
+            from .engine_fp64 import MUEngineF64
+            return super().__new__(MUEngineF64)
+        return super().__new__(cls)
 
     def __init__(self, X, n_components, *, layout="cm", G=None, shape_2d=None, lambda_L=0.0, mu=0,
                  epsilon_reg=1.0, simplex_H=False, simplex_W=True, log_shift=1e-14, dicotomy_tol=1e-5,
                  tol=1e-4, sigmaL=8.0, fixed_H=None, fixed_W=None, simplex_rows=None, xscale=1.0,
                  x_store="auto", max_iter=200, device=None, group=None, compute_loss=True,
                  fix_zero_lines=True, gw_floor=1e-30, x_tile=None, tile_px=None, h_variant=None, bregman=False, h_rule=0, pg_gamma_w=0.0,
-                 filled_channels=None, filled_pixels=None, frobenius=False, fused=True, force_sharded=False, autotune=False, x_facts=None):
+                 filled_channels=None, filled_pixels=None, frobenius=False, fused=True, force_sharded=False, autotune=False, x_facts=None,
+                 precision="fp32"):
+        if precision != "fp32":   # ("fp64" constructs MUEngineF64 in __new__)
+            raise ValueError(f"precision must be 'fp32' or 'fp64', got {precision!r}")
         # x_facts: what the caller already knows about X exactly as handed over (espm_amd/estimators/base.py: the scans that ride
         # behind the upload) - {"nonneg": True, "sum_x": float, "is_count": integers <= 255, "nnz": int}: the passes over X that
         # would establish the same here (9 ms at the headline size) are skipped.  One GPU, no lines to fill.

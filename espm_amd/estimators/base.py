@@ -363,6 +363,38 @@ class NMFEstimator(ABC, TransformerMixin, BaseEstimator):
         self._shard_group = group
         return self
 
+    # ---- arithmetic precision of the fits --------------------------------------------------------------
+    def set_precision(self, mode):
+        """Arithmetic of the fits: ``"fp32"`` (the default: fp32 kernels, fp64 loss sums) or ``"fp64"`` (every array and operation
+        in fp64, with the reference's simplex bisection and its global stop, dicotomy.py:111-173 - the mode that follows the
+        reference's trajectories, and its ``n_iter_``, at a small ``tol``).  Not a constructor argument: ``get_params()`` stays the
+        reference's.  Scope of ``"fp64"``: algo="log_surrogate" without linesearch, l2=False, no true_D / true_H, one GPU (no
+        ``shard()``), 1..8 components; anything else raises NotImplementedError from ``fit``.  Returns self."""
+        if mode not in ("fp32", "fp64"):
+            raise ValueError(f"precision must be 'fp32' or 'fp64', got {mode!r}")
+        self._precision = mode
+        return self
+
+    def _fp64(self):
+        return getattr(self, "_precision", "fp32") == "fp64"
+
+    def _fp64_refusal(self):
+        """Why a fit of this configuration cannot run in fp64 mode, or None."""
+        from espm_amd._lib import F64_MAX_K
+        if getattr(self, "algo", "log_surrogate") != "log_surrogate":
+            return f"algo={self.algo!r} (fp64 mode: algo='log_surrogate' only)"
+        if getattr(self, "linesearch", False):
+            return "linesearch=True"
+        if self.l2:
+            return "l2=True"
+        if self.true_D is not None or self.true_H is not None:
+            return "true_D / true_H tracking"
+        if getattr(self, "_shard_group", None) is not None:
+            return "shard() (fp64 mode runs on one GPU)"
+        if not 1 <= int(self.n_components) <= F64_MAX_K:
+            return f"n_components={self.n_components} (fp64 mode: 1..{F64_MAX_K} components)"
+        return None
+
     # ---- hooks implemented by the concrete estimator -------------------------------------------------
     @abstractmethod
     def _iteration(self, W, H):
@@ -406,7 +438,8 @@ class NMFEstimator(ABC, TransformerMixin, BaseEstimator):
                         simplex_W=simplex_W, log_shift=self.log_shift, tol=self.tol, fixed_H=fixed_H,
                         fixed_W=fixed_W, simplex_rows=rows, xscale=xscale, max_iter=self.max_iter,
                         fix_zero_lines=False, filled_channels=filled_channels, filled_pixels=filled_pixels, layout=layout,
-                        autotune=autotune, group=group, x_facts=x_facts, **self._engine_kwargs())
+                        autotune=autotune, group=group, x_facts=x_facts, **self._engine_kwargs(),
+                        **({"precision": "fp64"} if self._fp64() else {}))
 
     def _engine_G(self):
         G = self.G_
@@ -473,13 +506,17 @@ class NMFEstimator(ABC, TransformerMixin, BaseEstimator):
         # host pass: 0.18 s at 2048 x 512^2 fp32) moves to the device copy below; everything else
         # (dtype, shape, n_features_in_, feature names) is still scikit-learn's.
         # ESPM_FIT_TIMING=1: host-side time stamps of the fit's sections (no device synchronisation), printed at its end
+        if self._fp64():   # (before anything is uploaded)
+            why = self._fp64_refusal()
+            if why is not None:
+                raise NotImplementedError(f"fp64 mode (set_precision('fp64')) does not cover {why}")
         marks = [("enter", time.perf_counter())] if os.environ.get("ESPM_FIT_TIMING") else None
         mark = (lambda name: marks.append((name, time.perf_counter()))) if marks is not None else (lambda name: None)
         big = False
         try:
             import torch
             big = (hasattr(X, "shape") and getattr(X, "ndim", 0) == 2 and int(np.prod(X.shape)) >= _DEVICE_PREP_MIN_SIZE
-                   and getattr(X, "dtype", None) in (np.float32, np.float64) and torch.cuda.is_available())
+                   and getattr(X, "dtype", None) in (np.float32, np.float64) and torch.cuda.is_available() and not self._fp64())
         except Exception:
             big = False
         vkw = dict(dtype=[np.float64, np.float32])
@@ -539,7 +576,8 @@ class NMFEstimator(ABC, TransformerMixin, BaseEstimator):
             if torch.distributed.get_world_size(grp) > 1:
                 shard = _Shard(grp, self.shape_2d, int(Xv.shape[1]))
         x_local = False   # Xd_raw is this rank's block (sharded fit of a large X)
-        if Xv.size >= _DEVICE_PREP_MIN_SIZE:
+        # (fp64 mode: the host passes of the reference, in the array's own dtype; the engine takes X_fixed and uploads it)
+        if Xv.size >= _DEVICE_PREP_MIN_SIZE and not self._fp64():
             import torch
             if torch.cuda.is_available():
                 if Xv.flags.c_contiguous:
@@ -699,7 +737,7 @@ class NMFEstimator(ABC, TransformerMixin, BaseEstimator):
         self._L_cache = None
         self._L_pixels = int(self.X_.shape[1])
 
-        out_dtype = self.X_.dtype
+        out_dtype = np.dtype(np.float64) if self._fp64() else self.X_.dtype   # (fp64 mode: W_, H_ from the fp64 state)
         f.say, f.out_dtype = say, out_dtype
 
     def _fit_engine(self, f):
@@ -911,7 +949,13 @@ class NMFEstimator(ABC, TransformerMixin, BaseEstimator):
         kernels are compiled per component count - 1..8 in libespm_mu.so, 9..16 in libespm_mu_wide.so, 17..32 in libespm_mu_wide32.so -
         with the components of a pixel or channel in registers.  The sparse count store serves up to 16 components: sparse count data with
         more, or with 13-16 components and more than 2048-2144 channels (9-12: 2896-3024), take the dense 8-bit store (below 17 components
-        with a RuntimeWarning: the sparse store's G W table would not fit a workgroup's LDS)."""
+        with a RuntimeWarning: the sparse store's G W table would not fit a workgroup's LDS).
+
+        After ``set_precision("fp64")`` the fit computes in fp64 with the reference's simplex bisection and its global stop, so that
+        ``n_iter_`` and the trajectory follow the reference at a small ``tol``; ``W_`` and ``H_`` are float64.  Its scope:
+        algo="log_surrogate" (mu, epsilon_reg, lambda_L), simplex_H or simplex_W, fixed_H / fixed_W, G identity / dictionary /
+        physics model, normalize, hspy_comp, 1..8 components on one GPU; linesearch, l2, true_D / true_H, the other solvers,
+        shard() and more than 8 components raise NotImplementedError before X is uploaded."""
         self.fit_transform(X, **params)
         return self
 

@@ -545,6 +545,57 @@ int espm_mu_laplacian(const float* h, int k, int nx, int ny, int64_t ld, float* 
 size_t espm_lu_pl_scratch_bytes(int m, int r, int dtype);
 int espm_lu_pl(const void* a, int dtype, int m, int r, int64_t ld, void* out, void* scratch, size_t scratch_bytes, espm_stream_t stream);
 
+/* ---- fp64 mode (csrc/mu_fp64.hip; MUEngine(precision="fp64"), NMFEstimator.set_precision("fp64")) ------------------------------
+ * The log_surrogate multiplicative updates in fp64 with the reference's simplex bisection (dicotomy.py:4-55, :111-173: global stop).
+ * Plain fp64 device arrays, no espm_mu_state: W (M, k), G W (n, k) and R H^T (n, k) row-major, H (k, p), X (n, p) channel-major in
+ * the store x_type (ESPM_F64_X_*), every value exact; the effective X is (double) x * xscale.  Reductions run in a fixed order
+ * (per-workgroup partials, then one workgroup): a fit is bit-identical from run to run.  Only the narrow build (1..8 components)
+ * has the kernels; the wide builds return ESPM_EUNSUPPORTED from every one of these entry points. */
+#define ESPM_F64_MAX_K 8
+#define ESPM_F64_BLOCK 256     /* pixels per H-pass workgroup; entries per workgroup of the other reductions                   */
+#define ESPM_F64_CHUNK 2048    /* channels of G W staged in LDS per round of the H pass (k = 8: 128 KB)                         */
+#define ESPM_F64_WCHUNK 4096   /* pixels per workgroup of the W accumulation                                                  */
+#define ESPM_F64_MAXIT 127     /* bisection sweeps at most (the step bitmask is 128 bits)                                     */
+#define ESPM_F64_X_U8 0
+#define ESPM_F64_X_BF16 1
+#define ESPM_F64_X_F32 2
+#define ESPM_F64_X_F64 3
+
+/* Scratch (doubles) the H pass, espm_f64_hstat, espm_f64_rel and espm_f64_w_accum need for p pixels / count entries. */
+int64_t espm_f64_scratch_doubles(int n, int p, int k, int64_t count);
+/* G W (n, k) = G (n, m) W (m, k), or W itself with g == NULL (m = n); its column sums (k) and *small = 1 when an entry of G W is
+ * below log_shift (the loss then clamps G W, measures.py:493-504).  One launch plus one workgroup. */
+int espm_f64_gw(const double* g, const double* w, int n, int m, int k, double log_shift, double* gw, double* colsum, int32_t* small,
+                espm_stream_t stream);
+/* out (2k): [0, k) sum_j max(H_ij, log_shift), [k, 2k) max_j max(H_ij, log_shift) (updates.py:98-105, :139). */
+int espm_f64_hstat(const double* h, int k, int p, double log_shift, double* scratch, double* out, espm_stream_t stream);
+/* One pass over X for the state (G W, H): hist_row[0..3) = sum(Y - max(X, eps) log Y) over the clamped factors, sum mu_i log(H + eps_reg),
+ * sum H * (H L) (base.py:197-203, measures.py:524-577).  mode 0: only that; 1: also h_out = the H update without a simplex
+ * (updates.py:83-156, fixed_h entries >= 0 kept); 2: also num, den (k, p) of the update for espm_f64_bisect.  nx * ny == p: the
+ * 5-point grid Laplacian, nx == 0: the identity.  hstat: espm_f64_hstat of h (its maxima are read when lambda_L != 0). */
+int espm_f64_h_pass(const void* x, int x_type, int n, int p, double xscale, const double* gw, const double* colsum_gw,
+                    const int32_t* gw_small, const double* h, int k, const double* hstat, const double* mu, double eps_reg,
+                    double lambda_L, double sigma, int nx, int ny, double log_shift, int mode, const double* fixed_h, double* h_out,
+                    double* num, double* den, double* scratch, double* hist_row, espm_stream_t stream);
+/* The simplex multiplier of every pixel by the reference's bisection with its global stop, in two launches: every column bisects
+ * to maxit and ANDs the bitmask of the steps at which its |f| <= tol into mask (2 words); then every column recomputes its midpoint
+ * to the lowest common step and writes h_out = max(num / (den + nu), log_shift) (fixed_h entries >= 0 kept).  *status counts the
+ * columns that violate the reference's preconditions (dicotomy.py:17-19, :141-144).  maxit <= ESPM_F64_MAXIT. */
+int espm_f64_bisect(const double* num, const double* den, int k, int p, double log_shift, double tol, int maxit,
+                    const double* fixed_h, double* h_out, uint64_t* mask, int32_t* status, espm_stream_t stream);
+/* *out = max |a - b| / (a + tol mean(a)) over count entries (base.py:323-324). */
+int espm_f64_rel(const double* a, const double* b, int64_t count, double tol, double* scratch, double* out, espm_stream_t stream);
+/* rh (n, k) = (X / Y) max(H, eps)^T with Y = G W max(H, eps) (updates.py:50-59). */
+int espm_f64_w_accum(const void* x, int x_type, int n, int p, double xscale, const double* gw, const double* h, int k, double log_shift,
+                     double* scratch, double* rh, espm_stream_t stream);
+/* The W update from rh (updates.py:58-76): w_out = max(W (G^T rh) / (colsum(G) rowsum(H) + nu), log_shift), nu by the reference's
+ * bisection over the rows (rows != NULL: the physics model's rows, a mask of M bytes with nrows set; else nrows = M) when
+ * simplex != 0; fixed_w entries >= 0 kept.
+ * g == NULL: the identity (M = n).  hstat: espm_f64_hstat of the H the update uses.  One workgroup. */
+int espm_f64_w_finish(const double* rh, const double* g, const double* colsum_g, int n, int m, int k, const double* w,
+                      const double* hstat, int simplex, const uint8_t* rows, int nrows, double log_shift, double tol, int maxit,
+                      const double* fixed_w, double* w_out, int32_t* status, espm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
