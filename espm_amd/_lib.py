@@ -32,6 +32,7 @@ XCHG_HANDLE_BYTES = _D["ESPM_XCHG_HANDLE_BYTES"]
 ELL_TILE, ELL_PB, ELL_PBITS, ELL_LDS_MAX = _D["ESPM_ELL_TILE"], _D["ESPM_ELL_PB"], _D["ESPM_ELL_PBITS"], _D["ESPM_ELL_LDS_MAX"]
 ELL_STREAM_BYTES = _D["ESPM_ELL_STREAM_BYTES"]
 ELL_BUCKETS = _D["ESPM_ELL_BUCKETS"]
+ELL_HEAVY_MIN, ELL_HEAVY_MAX = _D["ESPM_ELL_HEAVY_MIN"], _D["ESPM_ELL_HEAVY_MAX"]
 ELL_UNIT_ROWS, ELL_UNIT_MAX_N, ELL_PAIR_MAX_K = _D["ESPM_ELL_UNIT_ROWS"], _D["ESPM_ELL_UNIT_MAX_N"], _D["ESPM_ELL_PAIR_MAX_K"]
 KP, PPAD, NPAD = _D["ESPM_KP"], _D["ESPM_PPAD"], _D["ESPM_NPAD"]         # (the default build; `variant(k)` below for the wide one)
 MAX_K = KP
@@ -73,6 +74,8 @@ SYMBOLS = {
     "espm_mu_ell_fill_hist": (C.c_int, [_SP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "espm_mu_ell_plan": (C.c_int, [_SP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "espm_mu_ell_fill": (C.c_int, [_SP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "espm_mu_ell_heavy_count": (C.c_int, [_SP, _vp, C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp]),
+    "espm_mu_ell_heavy_fill": (C.c_int, [_SP, _vp, C.c_int, C.c_int, _i64, _vp, _vp, _vp]),
     "espm_mu_hstat": (C.c_int, [_SP, C.c_int, _vp]),
     "espm_mu_build_gw": (C.c_int, [_SP, C.c_int, _vp]),
     "espm_mu_step_h": (C.c_int, [_SP, C.c_int, C.c_int, _vp]),

@@ -35,7 +35,8 @@ static int roundup(int v, int m) { return (v + m - 1) / m * m; }
   F(halo_top) F(halo_bot) F(hpart) F(hstat) F(a_slab) F(a) F(w_scratch) F(hist) F(hist_len) F(cur) F(it) F(ell_h) \
   F(ell_h_off) F(ell_klc) F(ell_w) F(ell_w_off) F(chan_perm) F(ell_cbits) F(n_cg) F(pix_perm) F(g_t) F(breg_sr_px) \
   F(breg_sr_ch) F(h_rule) F(pg_gamma_w) F(pg_q) F(ell_fill_px) F(ell_fill_num) F(ell_fill_n) F(tail_mode) F(no_fused) \
-  F(ell_pb) F(ell_stream)
+  F(ell_pb) F(ell_stream) F(ell_hv_n) F(ell_hv_npx) F(ell_hv_ngrp) F(ell_hv_px) F(ell_hv_px_off) F(ell_hv_pm) F(ell_hv_klc) F(ell_hv_kl) \
+  F(ell_hv_grp) F(ell_hv_grp_off) F(ell_hv_wm)
 
 // the caller's view of the state must be this library's (include/espm_mu.h, ESPM_MU_ABI_VERSION): checked before any field is read
 static int check_abi(const espm_mu_state* st) {
@@ -67,6 +68,12 @@ static int check_state(const espm_mu_state* st) {
   ESPM_REQUIRE(st->ell_stream == 0 || (st->ell_stream == 1 && st->x_dtype == ESPM_X_ELL), "ell_stream=%d: 0, or 1 with the sparse store", st->ell_stream);
   ESPM_REQUIRE(st->ell_fill_n >= 0 && (st->ell_fill_n == 0 || (st->x_dtype == ESPM_X_ELL && st->ell_fill_px && st->ell_fill_num)),
                "ell_fill_n=%d needs the sparse store, ell_fill_px and ell_fill_num", st->ell_fill_n);
+  ESPM_REQUIRE(st->ell_hv_n >= 0 && (st->ell_hv_n == 0 || (st->x_dtype == ESPM_X_ELL && st->h_rule == 0 && !st->breg_sr_px && st->ell_hv_npx >= 1 &&
+                                                          st->ell_hv_npx <= st->ell_hv_n && st->ell_hv_ngrp >= 1 && st->ell_hv_ngrp <= st->ell_hv_n &&
+                                                          st->ell_hv_px && st->ell_hv_px_off && st->ell_hv_pm && st->ell_hv_klc && st->ell_hv_kl &&
+                                                          st->ell_hv_grp && st->ell_hv_grp_off && st->ell_hv_wm && st->ell_fill_num)),
+               "ell_hv_n=%d needs the sparse store with the default H rule, 1 <= ell_hv_npx, ell_hv_ngrp <= ell_hv_n, every ell_hv_* array and "
+               "ell_fill_num", st->ell_hv_n);
   ESPM_REQUIRE(st->grid_mode == 0 || (st->nx >= 1 && st->ny >= 1 && st->nx * st->ny == st->p),
                "grid %d x %d does not match p=%d", st->nx, st->ny, st->p);
   ESPM_REQUIRE(st->xscale > 0.f, "xscale must be positive");
@@ -88,6 +95,25 @@ static int check_state(const espm_mu_state* st) {
 }
 
 static int nblk_h(const espm_mu_state* st) { return (st->p + st->tile_px - 1) / st->tile_px; }
+
+// Sparse store, before an H-step launch on h[src]: the numerators of the fill pixels and of the heavy elements' pixels, which the
+// epilogue adds (include/espm_mu.h, ell_fill_*, ell_hv_*)
+static int ell_pre_h(const espm_mu_state* st, int src, hipStream_t s) {
+  const int ld = st->ell_fill_n + (st->ell_hv_n > 0 ? st->ell_hv_npx : 0);
+  if (st->ell_fill_n > 0)
+    if (int rc = launch_ell_fill_num(st->gw_s, st->h[src], st->ell_fill_px, st->ell_fill_n, st->n, st->k, st->p_pad, st->log_shift,
+                                     st->ell_fill_num, s, ld))
+      return rc;
+  return st->ell_hv_n > 0 ? launch_ell_hv_h(st, src, ld, s) : ESPM_OK;
+}
+
+// ... and after it: the heavy elements' part of R H'^T into the slabs (w: the W accumulation has run, with H' = h[hnew] or, hnew < 0,
+// h_t) and their loss into the first record (loss: the H-step has written its records)
+static int ell_post(const espm_mu_state* st, int hnew, bool w, bool loss, hipStream_t s) {
+  if (st->ell_hv_n <= 0) return ESPM_OK;
+  if (hnew >= 0) return launch_ell_hv_post(st, st->h[hnew], (size_t)st->p_pad, 1, w, loss, s);
+  return launch_ell_hv_post(st, st->h_t, 1, ESPM_KP, w, loss, s);
+}
 
 // Both half-steps in one launch (mu_fused_kernel.hpp): sparse store, the default H rule, LDS for the table and the numerators
 // of a block of ell_pb pixels.  One record per pixel BLOCK.  (Round 2 kept the two launches below blocks of 512 pixels - images
@@ -247,6 +273,28 @@ int espm_mu_ell_fill_hist(const espm_mu_state* st, const void* x_pm_u8, const in
                          static_cast<hipStream_t>(stream), static_cast<const uint8_t*>(st->x_cm), st->n_cm, bkt_px, bkt_bc);
 }
 
+int espm_mu_ell_heavy_count(const espm_mu_state* st, const void* x, int src_dtype, int src_layout, int64_t ld, uint8_t* x_pm_u8,
+                            uint8_t* x_cm_u8, int32_t* cnt_px, espm_stream_t stream) {
+  if (int rc = check_ell_geometry(st)) return rc;
+  ESPM_REQUIRE(x && x_pm_u8 && cnt_px, "ell_heavy_count: NULL pointer");
+  ESPM_REQUIRE(src_dtype == ESPM_SRC_F32 || src_dtype == ESPM_SRC_F64, "ell_heavy_count: bad src_dtype %d", src_dtype);
+  ESPM_REQUIRE(src_layout == ESPM_LAYOUT_CM || src_layout == ESPM_LAYOUT_PM, "ell_heavy_count: bad layout %d", src_layout);
+  ESPM_REQUIRE(ld >= (src_layout == ESPM_LAYOUT_CM ? st->p : st->n), "ell_heavy_count: ld=%lld too small", (long long)ld);
+  ESPM_REQUIRE(!x_cm_u8 || st->n_cm == roundup(st->n, ESPM_NCM), "ell_heavy_count: x_cm is set but n_cm=%d is not n rounded up to %d", st->n_cm, ESPM_NCM);
+  return launch_ell_hv_count(x, src_dtype, src_layout, ld, st->n, st->p, st->n_pad, st->n_cm, x_pm_u8, x_cm_u8, cnt_px,
+                             static_cast<hipStream_t>(stream));
+}
+
+int espm_mu_ell_heavy_fill(const espm_mu_state* st, const void* x, int src_dtype, int src_layout, int64_t ld, const int32_t* px_off,
+                           int32_t* hv_pm, espm_stream_t stream) {
+  if (int rc = check_ell_geometry(st)) return rc;
+  ESPM_REQUIRE(x && px_off && hv_pm, "ell_heavy_fill: NULL pointer");
+  ESPM_REQUIRE(src_dtype == ESPM_SRC_F32 || src_dtype == ESPM_SRC_F64, "ell_heavy_fill: bad src_dtype %d", src_dtype);
+  ESPM_REQUIRE(src_layout == ESPM_LAYOUT_CM || src_layout == ESPM_LAYOUT_PM, "ell_heavy_fill: bad layout %d", src_layout);
+  ESPM_REQUIRE(ld >= (src_layout == ESPM_LAYOUT_CM ? st->p : st->n), "ell_heavy_fill: ld=%lld too small", (long long)ld);
+  return launch_ell_hv_fill(x, src_dtype, src_layout, ld, st->n, st->p, px_off, hv_pm, static_cast<hipStream_t>(stream));
+}
+
 int espm_mu_hstat(const espm_mu_state* st, int which, espm_stream_t stream) {
   if (int rc = check_state(st)) return rc;
   ESPM_REQUIRE(which == 0 || which == 1, "which must be 0/1");
@@ -334,12 +382,10 @@ int espm_mu_step_h(const espm_mu_state* st, int src, int write_h, espm_stream_t 
       a.cs_nbk = a.tail.nbk;
       a.tail_on = 1;
     }
-    if (a.fill_num) {  // pixels without counts: the numerator of their log_shift fill first (include/espm_mu.h)
-      if (int rc = launch_ell_fill_num(st->gw_s, st->h[src], st->ell_fill_px, st->ell_fill_n, st->n, st->k, st->p_pad, st->log_shift,
-                                       st->ell_fill_num, static_cast<hipStream_t>(stream)))
-        return rc;
-    }
-    return launch_h_ell(a, nblk_h(st), static_cast<hipStream_t>(stream));
+    // pixels without counts: the numerator of their log_shift fill first; heavy elements likewise (include/espm_mu.h)
+    if (int rc = ell_pre_h(st, src, static_cast<hipStream_t>(stream))) return rc;
+    if (int rc = launch_h_ell(a, nblk_h(st), static_cast<hipStream_t>(stream))) return rc;
+    return ell_post(st, -1, false, true, static_cast<hipStream_t>(stream));
   }
   return dispatch_h_step(make_h_args(st, src, write_h), st->x_dtype, st->tile_px, nblk_h(st),
                          static_cast<hipStream_t>(stream));
@@ -383,7 +429,10 @@ int espm_mu_loss_only(const espm_mu_state* st, int src, int slot, espm_stream_t 
 int espm_mu_w_accum(const espm_mu_state* st, espm_stream_t stream) {
   if (int rc = check_state(st)) return rc;
   ESPM_REQUIRE(st->nblk_w >= 1, "nblk_w must be >= 1");
-  if (st->x_dtype == ESPM_X_ELL) return launch_w_ell(make_w_args(st), st->k, st->nblk_w, static_cast<hipStream_t>(stream));
+  if (st->x_dtype == ESPM_X_ELL) {
+    if (int rc = launch_w_ell(make_w_args(st), st->k, st->nblk_w, static_cast<hipStream_t>(stream))) return rc;
+    return ell_post(st, -1, true, false, static_cast<hipStream_t>(stream));   // (H' = h_t)
+  }
   return dispatch_w_accum(make_w_args(st), st->k, st->x_dtype, st->nblk_w, static_cast<hipStream_t>(stream));
 }
 
@@ -408,11 +457,9 @@ int espm_mu_step_hw(const espm_mu_state* st, int src, espm_stream_t stream) {
     a.cs_nbk = a.tail.nbk;
     a.tail_on = 1;
   }
-  if (a.fill_num)
-    if (int rc = launch_ell_fill_num(st->gw_s, st->h[src], st->ell_fill_px, st->ell_fill_n, st->n, st->k, st->p_pad, st->log_shift,
-                                     st->ell_fill_num, s))
-      return rc;
-  return launch_fused_ell(a, make_w_args(st), st->nblk_w, s, st->no_fused == 2, st->ell_stream);
+  if (int rc = ell_pre_h(st, src, s)) return rc;
+  if (int rc = launch_fused_ell(a, make_w_args(st), st->nblk_w, s, st->no_fused == 2, st->ell_stream)) return rc;
+  return ell_post(st, 1 - src, true, true, s);
 }
 
 int espm_mu_w_reduce(const espm_mu_state* st, espm_stream_t stream) {
@@ -538,9 +585,7 @@ static int iterate_impl(espm_mu_state* st, int n_iter, int final_loss, espm_stre
     int rc;
     if (defer) {
       HStepArgs a = fused ? fused_h_args(st, cur) : make_h_args(st, cur, 1);
-      if (a.fill_num && (rc = launch_ell_fill_num(st->gw_s, st->h[cur], st->ell_fill_px, st->ell_fill_n, st->n, st->k, st->p_pad,
-                                                  st->log_shift, st->ell_fill_num, s)))
-        return rc;
+      if ((rc = ell_pre_h(st, cur, s))) return rc;
       if (pending) {
         a.cs_parts = tail.parts;
         a.cs_nbk = tail.nbk;
@@ -550,11 +595,13 @@ static int iterate_impl(espm_mu_state* st, int n_iter, int final_loss, espm_stre
       if (ev && (rc = check_hip(hipEventRecord(ev[3 * i], s), "iterate_timed: record"))) return rc;
       if (fused) {
         if ((rc = launch_fused_ell(a, make_w_args(st), st->nblk_w, s, st->no_fused == 2, st->ell_stream))) return rc;
+        if ((rc = ell_post(st, 1 - cur, true, true, s))) return rc;
         if (ev && (rc = check_hip(hipEventRecord(ev[3 * i + 1], s), "iterate_timed: record"))) return rc;
       } else {
         if ((rc = launch_h_ell(a, nblk_h(st), s))) return rc;
+        if ((rc = ell_post(st, -1, false, true, s))) return rc;
         if (ev && (rc = check_hip(hipEventRecord(ev[3 * i + 1], s), "iterate_timed: record"))) return rc;
-        if ((rc = espm_mu_w_accum(st, stream))) return rc;
+        if ((rc = espm_mu_w_accum(st, stream))) return rc;   // (with the heavy elements' part of the slabs)
       }
       const HFinalizeArgs fin = finalize_args(st, cur, slot, true);
       if (split) {

@@ -911,8 +911,9 @@ inline HStepArgs make_h_args(const espm_mu_state* st, int src, int write_h) {
   a.l2_m = nullptr;
   a.breg_sr = st->breg_sr_px;
   a.h_rule = st->h_rule;
-  a.fill_num = (st->x_dtype == ESPM_X_ELL && st->ell_fill_n > 0) ? st->ell_fill_num : nullptr;
-  a.fill_n = st->ell_fill_n;
+  // (the heavy elements' pixels take the columns after the fill's: include/espm_mu.h, ell_hv_*)
+  a.fill_n = st->ell_fill_n + (st->ell_hv_n > 0 ? st->ell_hv_npx : 0);
+  a.fill_num = (st->x_dtype == ESPM_X_ELL && a.fill_n > 0) ? st->ell_fill_num : nullptr;
   a.cs_parts = nullptr;
   a.cs_nbk = a.cs_lds_off = a.tail_on = 0;
   a.rec_nb = 0;
@@ -959,7 +960,14 @@ int launch_ell_fill(const uint8_t* x_pm, int n, int n_pad, int p, int p_pad, int
                     const uint8_t* bkt_bc = nullptr);
 int launch_w_ell(const WAccumArgs& args, int k, int nblk, hipStream_t stream);
 int launch_ell_fill_num(const float* gw_s, const float* h_in, const int32_t* fill_px, int fill_n, int n, int k, int p_pad, float fill,
-                        float* fill_num, hipStream_t stream);
+                        float* fill_num, hipStream_t stream, int ld = 0);
+// heavy elements of the sparse store (mu_ell_heavy.hip)
+int launch_ell_hv_count(const void* x, int src_dtype, int layout, int64_t ld, int n, int p, int n_pad, int n_cm, uint8_t* x8, uint8_t* x8c,
+                        int32_t* cnt_px, hipStream_t stream);
+int launch_ell_hv_fill(const void* x, int src_dtype, int layout, int64_t ld, int n, int p, const int32_t* px_off, int32_t* hv_pm,
+                       hipStream_t stream);
+int launch_ell_hv_h(const espm_mu_state* st, int src, int ld, hipStream_t stream);
+int launch_ell_hv_post(const espm_mu_state* st, const float* h, size_t hs_k, size_t hs_p, bool w, bool loss, hipStream_t stream);
 int dispatch_w_accum(const WAccumArgs& args, int k, int x_dtype, int nblk, hipStream_t stream);
 int launch_w_reduce(const float* slab, float* out, int nblk, int total, const HFinalizeArgs* fused_finalize,
                     hipStream_t stream, const float* bw_old = nullptr, double* bparts = nullptr, int n = 0, int k = 0, int n_pad = 0);

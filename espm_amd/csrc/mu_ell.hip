@@ -126,7 +126,7 @@ int launch_w_ell(const WAccumArgs& args, int k, int nblk, hipStream_t stream) {
 // per listed pixel, lanes over the channels, rows of gw_s straight from L2 (n x KP floats).
 __global__ __launch_bounds__(256) void ell_fill_num_kernel(const float* __restrict__ gw_s, const float* __restrict__ h_in,
                                                            const int32_t* __restrict__ fill_px, int fill_n, int n, int k, int p_pad,
-                                                           float fill, float* __restrict__ fill_num) {
+                                                           float fill, float* __restrict__ fill_num, int ld) {
   const int lane = threadIdx.x & 63;
   const int idx = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (idx >= fill_n) return;   // (whole waves)
@@ -151,14 +151,15 @@ __global__ __launch_bounds__(256) void ell_fill_num_kernel(const float* __restri
 #pragma unroll
   for (int kk = 0; kk < KP; ++kk) {
     const float t = wave_sum(s[kk]);
-    if (lane == 0 && kk < k) fill_num[(size_t)kk * fill_n + idx] = fill * t;
+    if (lane == 0 && kk < k) fill_num[(size_t)kk * ld + idx] = fill * t;
   }
 }
 
 int launch_ell_fill_num(const float* gw_s, const float* h_in, const int32_t* fill_px, int fill_n, int n, int k, int p_pad, float fill,
-                        float* fill_num, hipStream_t stream) {
+                        float* fill_num, hipStream_t stream, int ld) {
+  // ld: columns of fill_num (0: fill_n; more when the heavy elements' pixels follow, include/espm_mu.h)
   hipLaunchKernelGGL(ell_fill_num_kernel, dim3((fill_n + 3) / 4), dim3(256), 0, stream, gw_s, h_in, fill_px, fill_n, n, k, p_pad, fill,
-                     fill_num);
+                     fill_num, ld > 0 ? ld : fill_n);
   return check_hip(hipGetLastError(), "ell_fill_num launch");
 }
 

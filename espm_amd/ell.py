@@ -11,6 +11,9 @@ Layout (see the header for the authoritative description): 16-bit entries, two p
                 pixel; the channels of a wave are 64 consecutive entries of ``chan_perm[block]`` (the block's
                 channels by decreasing list length).
 A count larger than its field is split over several entries.
+Integer counts from ESPM_ELL_HEAVY_MIN = 256 on ("heavy" elements, up to 2^24) stay out of the lists: the lists are those of the
+image with them set to 0, and the heavy elements are kept with their exact values in two orders (``heavy_orders``; the header's
+ell_hv_* fields).
 Every list group (64 lists) starts with UNIT rows: entries with count 1 stored as index << 4, in every lane and
 position, as many as the group's poorest list has ones (rounded down to a multiple of 2 ELL_UNIT_ROWS entries); the
 general rows (count << bits | index) follow.  The offsets carry two words per group.
@@ -47,6 +50,38 @@ def _store16(ell16, dword, half, value):
     v = value.to(torch.int32)
     v = torch.where(v >= 32768, v - 65536, v).to(torch.int16)
     ell16[dword * 2 + half] = v
+
+
+def heavy_orders(q, c, x, n, pb):
+    """The heavy elements (pixel q, channel c, count x; sorted by pixel, then channel) in the two orders of include/espm_mu.h
+    (ell_hv_*): pixel-major {channel, count} pairs with the pixels that hold them and their offsets, and by (W block of pb pixels,
+    channel) {pixel, count} pairs with each group's channel and offsets."""
+    dev = q.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    px, cnt = torch.unique_consecutive(q, return_counts=True)
+    px_off = torch.zeros(px.numel() + 1, dtype=torch.int64, device=dev)
+    px_off[1:] = torch.cumsum(cnt, 0)
+    gkey = (q // pb) * n + c
+    order = torch.argsort(gkey, stable=True)                  # by block, channel, then (stable) pixel
+    gk, gcnt = torch.unique_consecutive(gkey[order], return_counts=True)
+    grp_off = torch.zeros(gk.numel() + 1, dtype=torch.int64, device=dev)
+    grp_off[1:] = torch.cumsum(gcnt, 0)
+    return dict(n=int(q.numel()), npx=int(px.numel()), ngrp=int(gk.numel()), px=px.to(**i32), px_off=px_off.to(**i32),
+                pm=torch.stack((c, x), 1).to(**i32).contiguous(), grp=(gk % n).to(**i32), grp_off=grp_off.to(**i32),
+                wm=torch.stack((q[order], x[order]), 1).to(**i32).contiguous())
+
+
+def split_heavy(Xpm, pb):
+    """(the image without its heavy elements, heavy_orders of them) - (Xpm, None) when there is none."""
+    p, n = Xpm.shape
+    nz = (Xpm >= _lib.ELL_HEAVY_MIN).nonzero(as_tuple=False)          # sorted by pixel, then channel
+    if nz.numel() == 0:
+        return Xpm, None
+    q, c = nz[:, 0], nz[:, 1]
+    x = Xpm[q, c].to(torch.int64)
+    light = Xpm.clone()
+    light[q, c] = 0
+    return light, heavy_orders(q, c, x, n, pb)
 
 
 def count_entries(Xpm, xmax_h, xmax_w, chunk=16384):
@@ -115,14 +150,16 @@ def _scatter_lists(ell16, major, minor, x, n_major, unit_cap, row_unit, row_gene
 
 
 def build(Xpm, p_pad, cbits, tile_px=512, chunk=16384):
-    """Xpm: (p, n) non-negative integer-valued tensor on the device (any float dtype).
+    """Xpm: (p, n) non-negative integer-valued tensor on the device (any float dtype), counts up to 2^24.
 
     Returns a dict of device tensors: ell_h (int32 dwords), ell_h_off (int32), klc (float32, p_pad), pix_perm (int32,
     p_pad), ell_w, ell_w_off, chan_perm (int32, nblk_w x 64 n_cg), and the python ints n_cg, nblk_w, nnz, entries_h,
-    entries_w, rows_h, rows_w, unit_rows_h, unit_rows_w."""
+    entries_w, rows_h, rows_w, unit_rows_h, unit_rows_w; with heavy elements also "hv" (heavy_orders; the lists and their entry
+    counts then hold the other elements only, nnz all of them)."""
     dev = Xpm.device
     p, n = Xpm.shape
     PB = 2 * tile_px                      # pixels per block of the W accumulation (espm_mu_state.ell_pb): two H tiles
+    Xpm, hv = split_heavy(Xpm, PB)        # (counts from 256 on stay out of the lists)
     PBITS = PB.bit_length() - 1
     xmax_h = (1 << (16 - cbits)) - 1
     xmax_w = (1 << (16 - PBITS)) - 1
@@ -209,10 +246,14 @@ def build(Xpm, p_pad, cbits, tile_px=512, chunk=16384):
         _scatter_lists(ell_w16, c, pl, xt[c, pl], n, 2 * wunit.reshape(-1)[g], w_off[2 * g], w_off[2 * g + 1], slot_of_c & 63,
                        xmax_w, PBITS)
 
-    return dict(ell_h=ell_h, ell_h_off=h_off.to(torch.int32), klc=klc, pix_perm=pix_perm.reshape(-1).to(torch.int32), ell_w=ell_w, ell_w_off=w_off.to(torch.int32),
-                chan_perm=chan_perm.to(torch.int32), n_cg=n_cg, nblk_w=nblk_w, nnz=nnz,
-                entries_h=int(per_px.sum()), entries_w=int(per_ch.sum()), rows_h=rows_h, rows_w=rows_w,
-                unit_rows_h=int(gunit.sum()), unit_rows_w=int(wunit.sum()))
+    out = dict(ell_h=ell_h, ell_h_off=h_off.to(torch.int32), klc=klc, pix_perm=pix_perm.reshape(-1).to(torch.int32), ell_w=ell_w, ell_w_off=w_off.to(torch.int32),
+               chan_perm=chan_perm.to(torch.int32), n_cg=n_cg, nblk_w=nblk_w, nnz=nnz,
+               entries_h=int(per_px.sum()), entries_w=int(per_ch.sum()), rows_h=rows_h, rows_w=rows_w,
+               unit_rows_h=int(gunit.sum()), unit_rows_w=int(wunit.sum()))
+    if hv is not None:
+        out["hv"] = hv
+        out["nnz"] += hv["n"]
+    return out
 
 
 def lds_bytes_h(n_pad, k):

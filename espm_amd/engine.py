@@ -33,6 +33,7 @@ from ._lib import MUState
 # launch plans are timed at set-up (MUEngine.autotune_plan) for fits at least this long when autotune="auto"
 AUTOTUNE_MIN_ITERS = 5000
 ELL_MAX_DENSITY = 0.5   # measured crossover with the dense 8-bit store at k = 5: 42 % non-zero 312 vs 394 us, 58 % 410 vs 399 us
+ELL_MAX_HEAVY_FRACTION = 0.1    # ... and at most this fraction of its non-zero counts is above 255 (heavy elements): measured at k = 5, 10 % 564 vs 796 us on the f32 store, 20 % 988 vs 796 (NOTEBOOK.md section 11)
 
 
 def _ptr(t):
@@ -81,7 +82,7 @@ class MUEngine:
         if precision != "fp32":   # ("fp64" constructs MUEngineF64 in __new__)
             raise ValueError(f"precision must be 'fp32' or 'fp64', got {precision!r}")
         # x_facts: what the caller already knows about X exactly as handed over (espm_amd/estimators/base.py: the scans that ride
-        # behind the upload) - {"nonneg": True, "sum_x": float, "is_count": integers <= 255, "nnz": int}: the passes over X that
+        # behind the upload) - {"nonneg": True, "sum_x": float, "is_count": integers <= 255, "nnz": int, "is_int": bool, "x_max": float}: the passes over X that
         # would establish the same here (9 ms at the headline size) are skipped.  One GPU, no lines to fill.
         self.device = require_gpu(device)
         self.group = group
@@ -209,12 +210,58 @@ class MUEngine:
             if unfilled:
                 set_empty(0)
             known = x_facts if (x_facts and not unfilled and "is_count" in x_facts and "nnz" in x_facts) else None
-            is_count = known["is_count"] if known else ((Xd == Xd.round()).all() & (Xd.max() <= 255))
+            # integer counts above 255 (up to 2^24) are the sparse store's heavy elements (include/espm_mu.h, ell_hv_*) where the fit's
+            # path has them wired in; ESPM_ELL_HEAVY=0 restores the choice without them
+            heavy_on = os.environ.get("ESPM_ELL_HEAVY", "1") != "0"
+            if known:
+                is_count = bool(known["is_count"])
+                x_int_max = known.get("x_max") if known.get("is_int") else None
+            else:
+                is_int = bool((Xd == Xd.round()).all())
+                x_int_max = float(Xd.max()) if is_int else None
+                is_count = is_int and x_int_max <= 255
+            n_heavy = 0
+            if not is_count and heavy_on and x_int_max is not None and x_int_max <= _lib.ELL_HEAVY_MAX:
+                n_heavy = int(torch.count_nonzero(Xd >= _lib.ELL_HEAVY_MIN))   # (a pass only for such data)
+            heavy_why = None   # why this fit's path cannot take heavy elements
+            if n_heavy:
+                if int(h_rule) != 0:
+                    heavy_why = "the heavy elements are wired in for the default H rule only"
+                elif self.bregman:
+                    heavy_why = "the heavy elements are not wired into the Bregman variant"
+                elif float(pg_gamma_w) > 0:
+                    heavy_why = "the heavy elements are not wired into the projected-gradient W step"
+            dense_code = 3     # (the store a rank with heavy elements falls back to: bf16 or f32)
             if bool(is_count):
                 code = 2
             else:   # (the bf16 round trip is two more passes over X and two temporaries of its size: only when it decides)
                 code = 1 if bool((Xd.to(torch.bfloat16).to(Xd.dtype) - Xd).abs().max() <= 1e-16) else 0
+                if n_heavy:
+                    dense_code = code
             self.x_store_note = None
+            self.n_heavy = n_heavy
+            if n_heavy:
+                from . import ell as _ell
+                n_pad8 = (self.n + 7) // 8 * 8
+                fits = k <= _lib.WIDE_MAX_K and self.n <= 16384 and _ell.lds_bytes_h(n_pad8, k) <= _lib.ELL_LDS_MAX
+                nnz_x = int(known["nnz"]) if known else int(torch.count_nonzero(Xd))
+                self._nnz_known = nnz_x
+                sparse = float(nnz_x) <= ELL_MAX_DENSITY * Xd.numel()
+                light = n_heavy <= ELL_MAX_HEAVY_FRACTION * nnz_x
+                dense = ("f32", "bf16")[code]
+                if fits and heavy_why is None and (x_store == "ell" or (sparse and light)):
+                    code = 3
+                elif not sparse:
+                    pass
+                elif heavy_why is not None:
+                    self.x_store_note = f"sparse count data with {n_heavy} counts above 255, but {heavy_why}: the dense {dense} store is used"
+                elif not fits:
+                    self.x_store_note = (f"sparse count data with {n_heavy} counts above 255, but the sparse store is built for up to "
+                                         f"{_lib.WIDE_MAX_K} components and n <= 16384 with a G W table that fits in LDS (n={self.n}, "
+                                         f"k={k}): the dense {dense} store is used")
+                else:
+                    self.x_store_note = (f"sparse count data, but {n_heavy} of its {nnz_x} non-zero counts are above 255 (more than "
+                                         f"{ELL_MAX_HEAVY_FRACTION:.0%}, where the sparse store stops paying): the dense {dense} store is used")
             if code == 2:
                 from . import ell as _ell
                 n_pad8 = (self.n + 7) // 8 * 8
@@ -236,15 +283,18 @@ class MUEngine:
                                          f"{_ell.lds_bytes_h(n_pad8, k)} bytes of LDS (limit {_lib.ELL_LDS_MAX}): the dense 8-bit store is used, "
                                          "about 3 x slower per iteration at this density")
                     warnings.warn("espm_amd: " + self.x_store_note, RuntimeWarning, stacklevel=3)
-            flag = torch.tensor([code], device=dev, dtype=torch.int32)
+            flag = torch.tensor([code, dense_code], device=dev, dtype=torch.int32)
             _tick("storage type (integer counts, bf16-exact, density)")
             if group is not None:
                 torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN, group=group)
+            # every rank takes the sparse store, or none does; then no rank whose counts exceed 255 takes the 8-bit store
+            flag = flag[:1] if int(flag[0]) == 3 else flag.min().reshape(1)
             if unfilled and int(flag.item()) != 3:
                 set_empty(log_shift)
                 flag.fill_(0)      # (the fill is neither an integer nor a bf16 value)
             if x_store == "ell" and int(flag.item()) != 3:
-                raise ValueError("x_store='ell' needs integer counts <= 255, n <= 16384 and a GW table that fits in LDS (12- or 16-float rows from 9 components on)")
+                raise ValueError("x_store='ell' needs integer counts <= 2^24 (above 255: the default H rule, no Bregman variant, no "
+                                 "projected-gradient W step), n <= 16384 and a GW table that fits in LDS (12- or 16-float rows from 9 components on)")
             refill = unfilled and int(flag.item()) == 3 and (filled_channels is not None or filled_pixels is not None)  # (the caller's tensor: put the fill back)
             x_store = ("f32", "bf16", "u8", "ell")[int(flag.item())]
         if int(h_rule) != 0 and x_store in ("u8", "bf16"):
@@ -291,14 +341,27 @@ class MUEngine:
                 _tick("sparse store build")
             assert self.ell["n_cg"] == st.n_cg and self.ell["nblk_w"] == st.nblk_w
             # pixels without counts: marked in the per-pixel loss constants, their fill's numerator has its own small pass
+            fill_n = 0
             if empty_px is not None and bool(empty_px.any()):
                 idx = torch.nonzero(empty_px).flatten()
                 if idx.numel() >= 1 << 24:
                     raise NotImplementedError("more than 2^24 pixels without counts")
+                fill_n = idx.numel()
                 self.fill_px = idx.to(torch.int32).contiguous()
-                self.fill_num = torch.zeros((k, idx.numel()), dtype=torch.float32, device=dev)
                 self.ell["klc"][idx] = -(torch.arange(idx.numel(), device=dev, dtype=torch.float32) + 1.0)
-            self.x_bytes = 4 * (self.ell["ell_h"].numel() + self.ell["ell_w"].numel())
+            # pixels with heavy elements: the fill table's next columns, their lists' loss constants kept aside (include/espm_mu.h, ell_hv_*)
+            hv = self.ell.get("hv")
+            npx = hv["npx"] if hv is not None else 0
+            if hv is not None:
+                if fill_n + npx >= 1 << 24:
+                    raise NotImplementedError("more than 2^24 pixels without counts or with counts above 255")
+                hpx = hv["px"].long()
+                self.hv_klc = self.ell["klc"][hpx].clone()
+                self.hv_kl = torch.zeros(npx, dtype=torch.float64, device=dev)
+                self.ell["klc"][hpx] = -(torch.arange(npx, device=dev, dtype=torch.float32) + float(fill_n + 1))
+            if fill_n + npx > 0:
+                self.fill_num = torch.zeros((k, fill_n + npx), dtype=torch.float32, device=dev)
+            self.x_bytes = 4 * (self.ell["ell_h"].numel() + self.ell["ell_w"].numel()) + (16 * hv["n"] if hv is not None else 0)
         else:
             xt = {"u8": torch.uint8, "bf16": torch.bfloat16, "f32": torch.float32}[x_store]
             if tile_px is not None:  # override the H-step tile chosen by espm_mu_query (tests, tuning)
@@ -387,7 +450,15 @@ class MUEngine:
             st.x_cm = st.x_pm = None
             st.ell_h, st.ell_h_off, st.ell_klc = (self.ell[key].data_ptr() for key in ("ell_h", "ell_h_off", "klc"))
             if self.fill_px is not None:
-                st.ell_fill_px, st.ell_fill_num, st.ell_fill_n = self.fill_px.data_ptr(), self.fill_num.data_ptr(), int(self.fill_px.numel())
+                st.ell_fill_px, st.ell_fill_n = self.fill_px.data_ptr(), int(self.fill_px.numel())
+            if self.fill_num is not None:
+                st.ell_fill_num = self.fill_num.data_ptr()
+            hv = self.ell.get("hv")
+            if hv is not None:
+                st.ell_hv_n, st.ell_hv_npx, st.ell_hv_ngrp = hv["n"], hv["npx"], hv["ngrp"]
+                st.ell_hv_px, st.ell_hv_px_off, st.ell_hv_pm = (hv[key].data_ptr() for key in ("px", "px_off", "pm"))
+                st.ell_hv_grp, st.ell_hv_grp_off, st.ell_hv_wm = (hv[key].data_ptr() for key in ("grp", "grp_off", "wm"))
+                st.ell_hv_klc, st.ell_hv_kl = self.hv_klc.data_ptr(), self.hv_kl.data_ptr()
             st.ell_w, st.ell_w_off, st.chan_perm = (self.ell[key].data_ptr() for key in ("ell_w", "ell_w_off", "chan_perm"))
             st.pix_perm = self.ell["pix_perm"].data_ptr()
         st.g = self.g.data_ptr() if self.g is not None else None
@@ -453,6 +524,23 @@ class MUEngine:
         self._check(self.lib.espm_mu_pack_x(_ptr(Xd), _lib.SRC_F64 if Xd.dtype == torch.float64 else _lib.SRC_F32,
                                  _lib.LAYOUT_PM if layout == "pm" else _lib.LAYOUT_CM, Xd.shape[1], self.n, self.p,
                                  _ptr(x8c) if x8c is not None else None, _ptr(x8), _lib.X_U8, st.n_pad, st.p_pad, _lib.PPAD, st.n_cm, _stream()))
+        hv = None
+        if getattr(self, "n_heavy", 0):
+            # counts above 255: out of the 8-bit copies (the lists leave them out), kept pixel-major with their values (include/espm_mu.h)
+            src = (_ptr(Xd), _lib.SRC_F64 if Xd.dtype == torch.float64 else _lib.SRC_F32, _lib.LAYOUT_PM if layout == "pm" else _lib.LAYOUT_CM,
+                   Xd.shape[1])
+            hv_cnt = torch.empty(self.p, **i32)
+            self._check(self.lib.espm_mu_ell_heavy_count(C.byref(st), *src, _ptr(x8), _ptr(x8c) if x8c is not None else None, _ptr(hv_cnt),
+                                                         _stream()))
+            hv_off = torch.zeros(self.p + 1, **i32)
+            hv_off[1:] = torch.cumsum(hv_cnt, 0)
+            n_hv = int(hv_off[-1])
+            if n_hv:
+                pm = torch.empty((n_hv, 2), **i32)
+                self._check(self.lib.espm_mu_ell_heavy_fill(C.byref(st), *src, _ptr(hv_off), _ptr(pm), _stream()))
+                q = torch.repeat_interleave(torch.arange(self.p, device=dev), hv_cnt.long())
+                from . import ell as _ell
+                hv = _ell.heavy_orders(q, pm[:, 0].long(), pm[:, 1].long(), self.n, st.ell_pb)
         cnt_px = torch.empty((2, st.p_pad), **i32)                    # entries, elements equal to 1
         cnt_bc = torch.empty((2, st.nblk_w, st.n_cg * 64), **i32)
         klc = torch.empty(st.p_pad, dtype=torch.float32, device=dev)
@@ -485,10 +573,13 @@ class MUEngine:
         if nnz is None:
             nnz = int(torch.count_nonzero(x8))   # (padding channels hold zeros)
         torch.cuda.current_stream().synchronize()
-        return dict(ell_h=ell_h, ell_h_off=h_off, klc=klc, pix_perm=pix_perm, ell_w=ell_w, ell_w_off=w_off, chan_perm=chan_perm, n_cg=st.n_cg,
-                    nblk_w=st.nblk_w, nnz=nnz, entries_h=int(cnt_px[0].sum()), entries_w=int(cnt_bc[0].sum()), rows_h=rows_h,
-                    rows_w=rows_w, unit_rows_h=int((h_off[1::2] - h_off[0:-1:2]).sum()),
-                    unit_rows_w=int((w_off[1::2] - w_off[0:-1:2]).sum()))
+        out = dict(ell_h=ell_h, ell_h_off=h_off, klc=klc, pix_perm=pix_perm, ell_w=ell_w, ell_w_off=w_off, chan_perm=chan_perm, n_cg=st.n_cg,
+                   nblk_w=st.nblk_w, nnz=nnz, entries_h=int(cnt_px[0].sum()), entries_w=int(cnt_bc[0].sum()), rows_h=rows_h,
+                   rows_w=rows_w, unit_rows_h=int((h_off[1::2] - h_off[0:-1:2]).sum()),
+                   unit_rows_w=int((w_off[1::2] - w_off[0:-1:2]).sum()))
+        if hv is not None:
+            out["hv"] = hv
+        return out
 
     def _pad_h(self, H):
         Hh = np.asarray(H, dtype=np.float32)

@@ -641,7 +641,8 @@ class NMFEstimator(ABC, TransformerMixin, BaseEstimator):
                 numel = float(Xv.size)
                 fill = n_zero_lines > 0
                 if not fill and not x_local:   # what the scans know about X as it goes to the engine (a filled X is another array: the engine looks itself)
-                    x_facts = dict(nonneg=True, sum_x=s1, is_count=bool(n_nonint == 0 and x_max <= 255), nnz=int(nnz))
+                    x_facts = dict(nonneg=True, sum_x=s1, is_count=bool(n_nonint == 0 and x_max <= 255), nnz=int(nnz),
+                                   is_int=bool(n_nonint == 0), x_max=x_max)
                 if fill:
                     Xd[:, zp] = self.log_shift
                     Xd[zc, :] = self.log_shift

@@ -109,6 +109,8 @@ enum { ESPM_LAYOUT_CM = 0 /* (n, p) channel-major */, ESPM_LAYOUT_PM = 1 /* (p, 
 #define ESPM_FUSED_MIN_BLOCKS 192 /* ... and smaller blocks when there are at least this many (one per CU, or nearly: a 64-row shard of the
                                    * headline image has 256 of 128 pixels; config 2's 128 blocks leave half the chip to the two launches,
                                    * which then win: 27.6 against 35.2 us per iteration, profiles/r03e_c2_iter.log)                              */
+#define ESPM_ELL_HEAVY_MIN 256   /* sparse store: counts from this on are heavy elements, kept outside the lists (espm_mu_state.ell_hv_*) */
+#define ESPM_ELL_HEAVY_MAX (1 << 24) /* ... up to this (fp32 holds every integer up to it exactly)                                  */
 #define ESPM_ELL_WTHREADS 1024 /* threads of a W-accumulation workgroup of the sparse store (16 waves)      */
 #ifndef ESPM_ELL_BUCKETS
 #define ESPM_ELL_BUCKETS 16    /* residue classes of the index by which a list's unit elements are placed in its unit rows (mu_ell_build.hip) */
@@ -156,7 +158,7 @@ enum { ESPM_LAYOUT_CM = 0 /* (n, p) channel-major */, ESPM_LAYOUT_PM = 1 /* (p, 
  * point that takes a state checks st->struct_size == sizeof(espm_mu_state) and st->abi_version == ESPM_MU_ABI_VERSION
  * first and fails with ESPM_EINVAL otherwise: a binding whose copy of the layout has drifted is refused instead of
  * having its pointers misread.  A binding can also compare its layout field by field with espm_mu_state_layout(). */
-#define ESPM_MU_ABI_VERSION 4
+#define ESPM_MU_ABI_VERSION 5
 
 typedef struct espm_mu_state {
   uint32_t struct_size;   /* sizeof(espm_mu_state) as the CALLER sees it                  */
@@ -296,6 +298,33 @@ typedef struct espm_mu_state {
    * 64-row shard of it, whose lists stay in the cache from one iteration to the next).  A hint: results are the same bits
    * either way, and a launch without a streamed form (blocks below ESPM_ELL_PB pixels, the generic instances) ignores it. */
   int32_t ell_stream;
+  /* Sparse store, heavy elements: integer counts ESPM_ELL_HEAVY_MIN .. ESPM_ELL_HEAVY_MAX (256 .. 2^24; fp32 holds every integer up
+   * to 2^24 exactly) are kept outside the 16-bit lists, with their exact values; the lists, ell_klc and the permutations are those of
+   * the image with these elements set to 0.  Two orders of the same elements:
+   *   pixel-major (H half-step): the ell_hv_npx pixels that hold heavy elements, ascending, in ell_hv_px; pixel i's elements are
+   *           ell_hv_pm[ell_hv_px_off[i] .. ell_hv_px_off[i + 1]), {channel, count} pairs by ascending channel.  Such a pixel is
+   *           marked in ell_klc as entry ell_fill_n + i of the fill table, ell_klc = -(1 + ell_fill_n + i), and its own loss
+   *           constant moves to ell_hv_klc[i]; ell_fill_num is then (k, ell_fill_n + ell_hv_npx) and ell_fill_px names the
+   *           ell_fill_n fill pixels only.  Before every H update (and loss evaluation) a pass forms the heavy numerator
+   *           sum_c x GW_c / (GW_c . H_pixel) into that column of ell_fill_num, which the H-step's epilogue adds like the fill's,
+   *           and the pixels' loss terms ell_hv_klc[i] + sum x log2(x / Y), summed per 256 of them, into the workspace ell_hv_kl;
+   *           after the launch one workgroup adds the sum of those partial sums (fixed order) to the KL field of the first hpart record.
+   *   by (W block, channel) (W accumulation): group g holds the elements of channel ell_hv_grp[g] in the W block of ell_pb pixels
+   *           that contains them, ell_hv_wm[ell_hv_grp_off[g] .. ell_hv_grp_off[g + 1]) as {pixel, count} by ascending pixel; groups
+   *           by block, then channel.  After the accumulation one thread per group adds sum x / Y' H'_pixel to its entries of
+   *           a_slab[block] (no atomics: a group owns them), so every reduction of the slabs sums them unchanged.
+   * ell_hv_n = 0: no heavy element, every pointer below may be NULL and nothing runs. */
+  int32_t ell_hv_n;              /* heavy elements                                          */
+  int32_t ell_hv_npx;            /* pixels with heavy elements                              */
+  int32_t ell_hv_ngrp;           /* (W block, channel) groups                               */
+  const int32_t* ell_hv_px;      /* (ell_hv_npx)                                            */
+  const int32_t* ell_hv_px_off;  /* (ell_hv_npx + 1)                                        */
+  const int32_t* ell_hv_pm;      /* (ell_hv_n, 2) {channel, count}, pixel-major             */
+  const float* ell_hv_klc;       /* (ell_hv_npx) the pixels' loss constants of their lists  */
+  double* ell_hv_kl;             /* (ell_hv_npx) workspace: partial sums of the loss terms  */
+  const int32_t* ell_hv_grp;     /* (ell_hv_ngrp) channel of each group                     */
+  const int32_t* ell_hv_grp_off; /* (ell_hv_ngrp + 1)                                       */
+  const int32_t* ell_hv_wm;      /* (ell_hv_n, 2) {pixel, count}, by (W block, channel)     */
 } espm_mu_state;
 
 const char* espm_mu_version(void);
@@ -343,6 +372,16 @@ int espm_mu_ell_plan(const espm_mu_state* st, const int32_t* cnt_px, const int32
 int espm_mu_ell_fill(const espm_mu_state* st, const void* x_pm_u8, const int32_t* chan_perm, const int32_t* pix_perm,
                      const int32_t* ell_h_off, const int32_t* ell_w_off, uint32_t* ell_h, uint32_t* ell_w,
                      espm_stream_t stream);
+/* Heavy elements of the sparse store (espm_mu_state.ell_hv_*) from the dense image x (src_dtype ESPM_SRC_F32 / _F64, src_layout CM
+ * (n, p) or PM (p, n), leading dimension ld: espm_mu_pack_x's source), in two steps around the caller's prefix sum:
+ *   count: cnt_px (p) heavy elements of each pixel; sets them to 0 in the 8-bit copies x_pm_u8 (p, n_pad) and, if not NULL, x_cm_u8
+ *          ([p_pad / ESPM_PPAD][n_cm][ESPM_PPAD]) that espm_mu_pack_x wrote, so that the lists built from them leave them out.
+ *   fill : px_off (p + 1, the exclusive prefix sum of cnt_px) -> hv_pm (px_off[p], 2) {channel, count} pairs, pixel-major,
+ *          ascending channel.  The pixels with elements and the (W block, channel) order are plain sorting (espm_amd/ell.py). */
+int espm_mu_ell_heavy_count(const espm_mu_state* st, const void* x, int src_dtype, int src_layout, int64_t ld, uint8_t* x_pm_u8,
+                            uint8_t* x_cm_u8, int32_t* cnt_px, espm_stream_t stream);
+int espm_mu_ell_heavy_fill(const espm_mu_state* st, const void* x, int src_dtype, int src_layout, int64_t ld, const int32_t* px_off,
+                           int32_t* hv_pm, espm_stream_t stream);
 
 /* statistics (row sums, row maxima) of st->h[which] into st->hstat[which] (local pixels). */
 int espm_mu_hstat(const espm_mu_state* st, int which, espm_stream_t stream);
