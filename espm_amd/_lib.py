@@ -25,6 +25,7 @@ OK, EINVAL, ENOSOLUTION, EHIP, EUNSUPPORTED = 0, -1, -2, -3, -4          # enum 
 X_F32, X_BF16, X_U8, X_ELL = 0, 1, 2, 3                                  # enum ESPM_X_*
 F64_X_U8, F64_X_BF16, F64_X_F32, F64_X_F64 = (_D["ESPM_F64_X_" + n] for n in ("U8", "BF16", "F32", "F64"))
 F64_MAX_K, F64_MAXIT = _D["ESPM_F64_MAX_K"], _D["ESPM_F64_MAXIT"]
+F64S_MAX_COUNT, F64S_MAX_N, F64S_WBLOCK = _D["ESPM_F64S_MAX_COUNT"], _D["ESPM_F64S_MAX_N"], _D["ESPM_F64S_WBLOCK"]
 SRC_F32, SRC_F64 = 0, 1
 LAYOUT_CM, LAYOUT_PM = 0, 1
 ABI_VERSION = _D["ESPM_MU_ABI_VERSION"]
@@ -133,6 +134,13 @@ SYMBOLS = {
     "espm_f64_w_accum": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp]),
     "espm_f64_w_finish": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_double, C.c_double,
                                     C.c_int, _vp, _vp, _vp, _vp]),
+    # fp64 mode on the sparse store (csrc/mu_fp64_sparse.hip)
+    "espm_f64_sparse_scratch_doubles": (_i64, [C.c_int, C.c_int, C.c_int]),
+    "espm_f64_sparse_h_pass": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp,
+                                         C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp]),
+    "espm_f64_sparse_w_accum": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp, C.c_int, C.c_double, _vp, _vp,
+                                          _vp]),
 }
 
 

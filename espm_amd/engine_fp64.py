@@ -8,6 +8,8 @@ this mode follows its trajectories.
 Data layout in HBM (torch tensors):
   x      (n, p) u8|bf16|f32|f64   X channel-major, in the narrowest store that holds every value exactly; the kernels
                                   read (double) x * xscale
+  sp     the sparse store          instead of x for a sparse image of integer counts (x_store "sparse", espm_amd/sparse64.py):
+                                  its non-zero elements in two orders, on the kernels of csrc/mu_fp64_sparse.hip
   h[2]   (k, p) f64               ping-pong H
   w[2]   (M, k) f64               ping-pong W (M = m, or n when G is the identity)
   gw     (n, k) f64               G W, its column sums, a flag "an entry is below log_shift"
@@ -23,7 +25,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, sparse64
 from .conf import dicotomy_tol as DICOTOMY_TOL, maxit_dichotomy as MAXIT
 from .engine import MUEngine, _ptr, _stream, require_gpu
 
@@ -49,7 +51,8 @@ class MUEngineF64(MUEngine):
     def __init__(self, X, n_components, *, layout="cm", G=None, shape_2d=None, lambda_L=0.0, mu=0, epsilon_reg=1.0,
                  simplex_H=False, simplex_W=True, log_shift=1e-14, dicotomy_tol=DICOTOMY_TOL, tol=1e-4, sigmaL=8.0,
                  fixed_H=None, fixed_W=None, simplex_rows=None, xscale=1.0, x_store="auto", max_iter=200, device=None,
-                 group=None, fix_zero_lines=True, precision="fp64", bregman=False, h_rule=0, frobenius=False, **ignored):
+                 group=None, fix_zero_lines=True, precision="fp64", bregman=False, h_rule=0, frobenius=False, filled_channels=None,
+                 filled_pixels=None, **ignored):
         if group is not None:
             raise NotImplementedError("fp64 mode runs on one GPU: no sharded engine")
         if bregman or h_rule or frobenius:
@@ -66,42 +69,30 @@ class MUEngineF64(MUEngine):
         f64 = dict(dtype=torch.float64, device=dev)
 
         # ---- X: (n, p) channel-major on the device, in a store that holds it exactly ------------------------------------
-        Xd = X if isinstance(X, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(X))
-        Xd = Xd.to(device=dev, dtype=torch.float64)
-        if Xd.dim() != 2:
+        Xt = X if isinstance(X, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(X))
+        if Xt.dim() != 2:
             raise ValueError("X must be 2-D")
-        if layout == "pm":
-            Xd = Xd.t()
-        elif layout != "cm":
+        if layout not in ("cm", "pm"):
             raise ValueError("layout must be 'cm' or 'pm'")
-        Xd = Xd.contiguous()
-        n, p = Xd.shape
-        self.n, self.p, self.p_total = int(n), int(p), int(p)
         self.out_dtype = np.float64
-        if bool((Xd < 0).any()):
-            raise ValueError("Negative values in data")  # espm/estimators/base.py:528
-        if fix_zero_lines:   # base.py:519-528
-            zp, zc = Xd.sum(dim=0) == 0, Xd.sum(dim=1) == 0
-            Xd[:, zp] = log_shift
-            Xd[zc, :] = log_shift
-        store = _exact_store(Xd) if x_store == "auto" else x_store
-        if store not in _STORES:
-            raise ValueError(f"fp64 mode: x_store must be 'auto', 'u8', 'bf16', 'f32' or 'f64', got {x_store!r}")
-        if store != "f64" and _STORES[store] < _STORES[_exact_store(Xd)]:
-            raise ValueError(f"fp64 mode: X does not fit the {store} store exactly")
-        self.x_store, self.x_type = store, _STORES[store]
-        self.x = {"u8": lambda t: t.to(torch.uint8), "bf16": lambda t: t.to(torch.bfloat16), "f32": lambda t: t.to(torch.float32),
-                  "f64": lambda t: t}[store](Xd).contiguous()
         self.xscale = float(xscale)
-        # const_KL (base.py:200-201) of the effective X, in row chunks
-        total = torch.zeros((), **f64)
-        step = max(1, (32 << 20) // max(1, self.p))
-        for a in range(0, self.n, step):
-            xs = Xd[a:a + step] * self.xscale
-            total += (xs * torch.log(xs.clamp_min(log_shift))).sum() - xs.sum()
-        self.c_kl = float(total)
-        self.sum_x = float(Xd.sum()) if self.xscale == 1.0 else float((Xd * self.xscale).sum())
-        del Xd
+        self.sp, self.x, self.x_type = None, None, None
+        self.x_store_note = None   # (why 'auto' kept an image dense, if it did)
+        if x_store in ("auto", "sparse"):
+            # one pass over X in row chunks in its own dtype (a host array goes up chunk by chunk: no fp64 copy of the image)
+            stats = sparse64.scan(Xt, layout, x_store, filled_channels=filled_channels, filled_pixels=filled_pixels, device=dev)
+            use, note = sparse64.choose(stats, x_store)
+            if use:
+                self.sp = sparse64.build(stats, fix_zero_lines)
+                self.n, self.p, self.p_total = stats["n"], stats["p"], stats["p"]
+                self.x_store = "sparse"
+                self.c_kl, self.sum_x = sparse64.constants(self.sp, self.xscale, log_shift)
+            else:
+                self.x_store_note = note
+            del stats
+        if self.sp is None:
+            self.x_store = self._dense_store(Xt, layout, x_store, fix_zero_lines, log_shift)
+        del Xt
 
         # ---- G, parameters ------------------------------------------------------------------------------------------------
         self.m = 0 if G is None else int(np.asarray(G).shape[1])
@@ -149,12 +140,49 @@ class MUEngineF64(MUEngine):
         self.mask = torch.zeros(2, dtype=torch.int64, device=dev)
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
         need = max(int(self.lib.espm_f64_scratch_doubles(self.n, self.p, k, k * self.p)),
-                   int(self.lib.espm_f64_scratch_doubles(self.n, self.p, k, self.M * k)))
+                   int(self.lib.espm_f64_scratch_doubles(self.n, self.p, k, self.M * k)),
+                   int(self.lib.espm_f64_sparse_scratch_doubles(self.n, self.p, k)) if self.sp is not None else 0)
         self.scratch = torch.zeros(need, **f64)
         self.hist_len = int(max_iter) + 3
         self.hist = torch.zeros((self.hist_len, 8), **f64)
         self.cur, self.it = 0, 0
         self._h_ready = None   # (cur, it) of an H update eval_current left in h[1 - cur]
+
+    def _dense_store(self, Xt, layout, x_store, fix_zero_lines, log_shift):
+        """X (n, p) channel-major on the device in a dense store that holds it exactly; const_KL and sum_x of the effective X."""
+        dev, f64 = self.device, dict(dtype=torch.float64, device=self.device)
+        Xd = Xt.to(device=dev, dtype=torch.float64)
+        if layout == "pm":
+            Xd = Xd.t()
+        elif layout != "cm":
+            raise ValueError("layout must be 'cm' or 'pm'")
+        Xd = Xd.contiguous()
+        n, p = Xd.shape
+        self.n, self.p, self.p_total = int(n), int(p), int(p)
+        if bool((Xd < 0).any()):
+            raise ValueError("Negative values in data")  # espm/estimators/base.py:528
+        if fix_zero_lines:   # base.py:519-528
+            zp, zc = Xd.sum(dim=0) == 0, Xd.sum(dim=1) == 0
+            Xd[:, zp] = log_shift
+            Xd[zc, :] = log_shift
+        store = _exact_store(Xd) if x_store == "auto" else x_store
+        if store not in _STORES:
+            raise ValueError(f"fp64 mode: x_store must be 'auto', 'sparse', 'u8', 'bf16', 'f32' or 'f64', got {x_store!r}")
+        if store != "f64" and _STORES[store] < _STORES[_exact_store(Xd)]:
+            raise ValueError(f"fp64 mode: X does not fit the {store} store exactly")
+        self.x_store, self.x_type = store, _STORES[store]
+        self.x = {"u8": lambda t: t.to(torch.uint8), "bf16": lambda t: t.to(torch.bfloat16), "f32": lambda t: t.to(torch.float32),
+                  "f64": lambda t: t}[store](Xd).contiguous()
+        # const_KL (base.py:200-201) of the effective X, in row chunks
+        total = torch.zeros((), **f64)
+        step = max(1, (32 << 20) // max(1, self.p))
+        for a in range(0, self.n, step):
+            xs = Xd[a:a + step] * self.xscale
+            total += (xs * torch.log(xs.clamp_min(log_shift))).sum() - xs.sum()
+        self.c_kl = float(total)
+        self.sum_x = float(Xd.sum()) if self.xscale == 1.0 else float((Xd * self.xscale).sum())
+        del Xd
+        return store
 
     # ---- helpers ----------------------------------------------------------------------------------------------------------------
     def _dev(self, a, shape, name):
@@ -178,8 +206,13 @@ class MUEngineF64(MUEngine):
             self._hstat(self.h[src])
         mode = 0 if not mode_update else (2 if self.simplex_H else 1)
         num, den = (self.numden[0], self.numden[1]) if mode == 2 else (None, None)
-        self._check(self.lib.espm_f64_h_pass(
-            _ptr(self.x), self.x_type, self.n, self.p, self.xscale, _ptr(self.gw), _ptr(self.colsum_gw), _ptr(self.gw_small),
+        if self.sp is not None:
+            sp = self.sp
+            head = (self.lib.espm_f64_sparse_h_pass, (_ptr(sp["h_elem"]), _ptr(sp["h_off"]), _ptr(sp["ec"]), sp["n_ec"], _ptr(sp["ep_flag"])))
+        else:
+            head = (self.lib.espm_f64_h_pass, (_ptr(self.x), self.x_type))
+        self._check(head[0](
+            *head[1], self.n, self.p, self.xscale, _ptr(self.gw), _ptr(self.colsum_gw), _ptr(self.gw_small),
             _ptr(self.h[src]), self.k, _ptr(self.hstat), _ptr(self.mu), self.eps_reg, self.lambda_L, self.sigma, self.nx, self.ny,
             self.log_shift, mode, _ptr(self.fixed_h), _ptr(self.h[dst]) if mode == 1 else None, _ptr(num), _ptr(den),
             _ptr(self.scratch), _ptr(self.hist[slot]), _stream()))
@@ -190,8 +223,13 @@ class MUEngineF64(MUEngine):
     def _w_update(self, w_src, h_src, w_dst):
         """W update from w[w_src] (its G W is current) with H = h[h_src] into w[w_dst]."""
         self._hstat(self.h[h_src])
-        self._check(self.lib.espm_f64_w_accum(_ptr(self.x), self.x_type, self.n, self.p, self.xscale, _ptr(self.gw), _ptr(self.h[h_src]),
-                                              self.k, self.log_shift, _ptr(self.scratch), _ptr(self.rh), _stream()))
+        if self.sp is not None:
+            sp = self.sp
+            head = (self.lib.espm_f64_sparse_w_accum, (_ptr(sp["w_elem"]), _ptr(sp["w_off"]), _ptr(sp["ec_flag"]), _ptr(sp["ep"]), _ptr(sp["ep_off"])))
+        else:
+            head = (self.lib.espm_f64_w_accum, (_ptr(self.x), self.x_type))
+        self._check(head[0](*head[1], self.n, self.p, self.xscale, _ptr(self.gw), _ptr(self.h[h_src]), self.k, self.log_shift,
+                            _ptr(self.scratch), _ptr(self.rh), _stream()))
         g = self.g if self.m else None
         self._check(self.lib.espm_f64_w_finish(_ptr(self.rh), _ptr(g), _ptr(self.colsum_g), self.n, self.m, self.k, _ptr(self.w[w_src]),
                                                _ptr(self.hstat), int(self.simplex_W), _ptr(self.rows), self.nrows, self.log_shift,

@@ -635,6 +635,42 @@ int espm_f64_w_finish(const double* rh, const double* g, const double* colsum_g,
                       const double* hstat, int simplex, const uint8_t* rows, int nrows, double log_shift, double tol, int maxit,
                       const double* fixed_w, double* w_out, int32_t* status, espm_stream_t stream);
 
+/* ---- fp64 mode, sparse store (csrc/mu_fp64_sparse.hip; x_store = "sparse" of the fp64 engine, built by espm_amd/sparse64.py) ------
+ * A count image (non-negative integers up to ESPM_F64S_MAX_COUNT, n <= ESPM_F64S_MAX_N channels) kept as its non-zero elements,
+ * one dword each, count << 16 | index, the raw count (the kernels multiply by xscale), in two orders:
+ *   H order  by pixel.  The lists of the 64 consecutive pixels 64 g .. 64 g + 63 ("group" g) are interleaved dword-wise: element r
+ *            of pixel 64 g + l is h_elem[h_off[g] + 64 r + l]; index = channel, ascending within a list; a list shorter than the
+ *            longest of its group is padded with 0 (no element has count 0).  h_off: ceil(p / 64) + 1 dword offsets (int64).
+ *   W order  by (block b of ESPM_F64S_WBLOCK pixels, channel c), plain CSR: list b * n + c is w_elem[w_off[b n + c] .. w_off[b n + c + 1]),
+ *            index = pixel - b * ESPM_F64S_WBLOCK, ascending.  w_off: ceil(p / ESPM_F64S_WBLOCK) * n + 1 offsets (int64).
+ * Both orders hold the same elements.  Lines without a count are not in the store; the engine records them (base.py:519-528 fills
+ * them with log_shift) and the kernels apply that fill, every filled entry being log_shift * xscale:
+ *   ec (n_ec channel indices, ascending) / ec_flag (n bytes)           the empty channels
+ *   ep (pixel indices, ascending) / ep_flag (p bytes) / ep_off (ceil(p / ESPM_F64S_WBLOCK) + 1 offsets into ep, per W block)
+ *                                                                      the empty pixels; all NULL (n_ec = 0) without the fill.
+ * The reference's zeros that are not zeros: the loss clamps X, so a zero entry of a kept line adds -log_shift log Y: the H pass sums
+ * log Y over every channel of a pixel without reading X (fp32 log of the fp64 Y, fp64 sum; its 1e-7 relative error enters the loss at
+ * 1e-21) and takes the elements' own fp64 logs off it.  An empty channel's row adds log_shift xscale G W[c, :] / Y to every pixel's
+ * numerator (fp32 reciprocal: 1e-7 of a 1e-14 term) and is the whole of rh[c, :], which the W pass therefore computes in fp64 over
+ * every pixel.  An empty pixel's column is the whole of that pixel's numerator: fp64 in both passes.
+ * Same contracts as espm_f64_h_pass / espm_f64_w_accum otherwise; fixed-order reductions; ESPM_EUNSUPPORTED from the wide builds. */
+#define ESPM_F64S_MAX_COUNT 65535
+#define ESPM_F64S_MAX_N 65536
+#define ESPM_F64S_HBLOCK 512       /* pixels (threads) per H-pass workgroup                                                    */
+#define ESPM_F64S_WBLOCK 65536     /* pixels per block of the W order                                                          */
+#define ESPM_F64S_LDS_BYTES 163840 /* G W (n k doubles) is staged in LDS by the H pass up to this size, read through L2 above   */
+
+/* Scratch (doubles) of the two entry points below; the engine allocates the larger of this and espm_f64_scratch_doubles. */
+int64_t espm_f64_sparse_scratch_doubles(int n, int p, int k);
+int espm_f64_sparse_h_pass(const uint32_t* h_elem, const int64_t* h_off, const int32_t* ec, int n_ec, const uint8_t* ep_flag, int n, int p,
+                           double xscale, const double* gw, const double* colsum_gw, const int32_t* gw_small, const double* h, int k,
+                           const double* hstat, const double* mu, double eps_reg, double lambda_L, double sigma, int nx, int ny,
+                           double log_shift, int mode, const double* fixed_h, double* h_out, double* num, double* den, double* scratch,
+                           double* hist_row, espm_stream_t stream);
+int espm_f64_sparse_w_accum(const uint32_t* w_elem, const int64_t* w_off, const uint8_t* ec_flag, const int32_t* ep, const int32_t* ep_off,
+                            int n, int p, double xscale, const double* gw, const double* h, int k, double log_shift, double* scratch,
+                            double* rh, espm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
