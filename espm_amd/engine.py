@@ -28,12 +28,10 @@ import torch
 
 from . import _lib
 from ._lib import MUState
+from .store import CODES, StoreFacts, choose_store
 
-# the sparse count store is chosen (x_store='auto') when at most this fraction of X is non-zero
 # launch plans are timed at set-up (MUEngine.autotune_plan) for fits at least this long when autotune="auto"
 AUTOTUNE_MIN_ITERS = 5000
-ELL_MAX_DENSITY = 0.5   # measured crossover with the dense 8-bit store at k = 5: 42 % non-zero 312 vs 394 us, 58 % 410 vs 399 us
-ELL_MAX_HEAVY_FRACTION = 0.1    # ... and at most this fraction of its non-zero counts is above 255 (heavy elements): measured at k = 5, 10 % 564 vs 796 us on the f32 store, 20 % 988 vs 796 (NOTEBOOK.md section 11)
 
 
 def _ptr(t):
@@ -51,6 +49,52 @@ def require_gpu(device=None):
     return torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
 
 
+def _set_up_timer():
+    """ESPM_ENGINE_TIMING=1: device-synchronised time of the set-up steps (tools/analysis)."""
+    if not os.environ.get("ESPM_ENGINE_TIMING"):
+        return lambda name: None
+    last = [time.perf_counter()]
+
+    def tick(name):
+        torch.cuda.synchronize()
+        now = time.perf_counter()
+        print(f"[engine set-up] {name}: {1e3 * (now - last[0]):.1f} ms", file=sys.stderr, flush=True)
+        last[0] = now
+    return tick
+
+
+def _set_lines(Xd, layout, empty_px, empty_ch, v):
+    """The lines of X that the two masks name, set to v."""
+    px_axis = 0 if layout == "pm" else 1
+    for mask, axis in ((empty_px, px_axis), (empty_ch, 1 - px_axis)):   # (the reference's order, base.py:524-525)
+        if mask is not None:
+            if axis == 0:
+                Xd[mask, :] = v
+            else:
+                Xd[:, mask] = v
+
+
+def _scan_x(Xd, known=None, heavy_on=True):
+    """The StoreFacts of the image Xd (any device), or of the caller's XFacts ``known`` about it.  Every fact is a pass over X or
+    more, so each is taken only where the earlier ones leave it a say in the choice (store.StoreFacts)."""
+    if known is not None:
+        is_int, x_max = bool(known.is_int), (known.x_max if known.is_int else None)
+    else:
+        is_int = bool((Xd == Xd.round()).all())
+        x_max = float(Xd.max()) if is_int else None
+    is_count = is_int and x_max <= 255
+    n_heavy = 0
+    if not is_count and heavy_on and is_int and x_max <= _lib.ELL_HEAVY_MAX:
+        n_heavy = int(torch.count_nonzero(Xd >= _lib.ELL_HEAVY_MIN))   # (a pass only for such data)
+    bf16_exact = None
+    if not is_count:   # (the bf16 round trip is two more passes over X and two temporaries of its size: only when it decides)
+        bf16_exact = bool((Xd.to(torch.bfloat16).to(Xd.dtype) - Xd).abs().max() <= 1e-16)
+    nnz = None
+    if is_count or n_heavy:   # (the sparse store's build does not count again: a pass over the 8-bit copy was 2.6 of its 12 ms)
+        nnz = int(known.nnz) if known is not None else int(torch.count_nonzero(Xd))
+    return StoreFacts(is_int, x_max, n_heavy, bf16_exact, nnz)
+
+
 class MUEngine:
     """One SmoothNMF problem resident on one GPU.
 
@@ -61,6 +105,8 @@ class MUEngine:
     X : (n, p) array (``layout="cm"``) or (p, n) (``layout="pm"``, hyperspy's layout); numpy or a
         torch tensor (host or device), float32/float64.  When ``group`` is given, X is this rank's
         block of image rows and ``shape_2d`` its local (rows, ny).
+    x_facts : ``store.XFacts``, what the caller already knows about X exactly as handed over; discarded when a group is given
+        or fix_zero_lines is set.
     precision : "fp32" (default) or "fp64" - the latter constructs ``engine_fp64.MUEngineF64`` (every array and operation in
         fp64, the reference's simplex bisection; one GPU, 1..8 components).
     """
@@ -81,9 +127,6 @@ class MUEngine:
                  precision="fp32"):
         if precision != "fp32":   # ("fp64" constructs MUEngineF64 in __new__)
             raise ValueError(f"precision must be 'fp32' or 'fp64', got {precision!r}")
-        # x_facts: what the caller already knows about X exactly as handed over (espm_amd/estimators/base.py: the scans that ride
-        # behind the upload) - {"nonneg": True, "sum_x": float, "is_count": integers <= 255, "nnz": int, "is_int": bool, "x_max": float}: the passes over X that
-        # would establish the same here (9 ms at the headline size) are skipped.  One GPU, no lines to fill.
         self.device = require_gpu(device)
         self.group = group
         self.world = torch.distributed.get_world_size(group) if group is not None else 1
@@ -91,22 +134,55 @@ class MUEngine:
         # the sharded code path (records, exchange, combine) also for a group of ONE rank: what a rank of an N-GPU run does
         # per iteration, measurable on one GPU (tools/analysis/shard_iter.py)
         self.sharded = self.world > 1 or (bool(force_sharded) and group is not None)
-        dev = self.device
         k = int(n_components)
         self.k = k
         self.V = _lib.variant(k)          # the build with the kernels for k components (1..8, 9..16, or 17..32 on the dense stores)
         self.lib, self._check = self.V.lib, self.V.check
+        self._tick = _set_up_timer()
 
-        _t_dbg = [time.perf_counter()] if os.environ.get("ESPM_ENGINE_TIMING") else None
+        Xd, empty_ch, empty_px, x_facts, breg_px = self._ingest(X, layout, x_facts, fix_zero_lines, filled_channels, filled_pixels,
+                                                                log_shift, G, bregman)
+        # A fit with the Frobenius data term (l2=True with algo="l2_surrogate", smooth_nmf.py:223-237, :404-413, base.py:197-198):
+        # quadratic-surrogate H step, Frobenius W step and loss; on the dense fp32 store
+        self.frobenius = bool(frobenius)
+        if self.frobenius:
+            if float(xscale) != 1.0 or int(h_rule) != 1 or simplex_W:
+                raise NotImplementedError("the Frobenius fit is built for xscale = 1 (hand over the scaled X), "
+                                          "h_rule = 1 and no simplex over W (updates.py:31-36 has none)")
+            x_store = "f32"
+        if h_variant:
+            raise NotImplementedError("h_variant=1 (Y = GW H on the matrix cores) was retired: slower than the vector kernels "
+                                      "at k <= 8 and sensitive to a transcendental-operand hazard (DESIGN.md)")
+        # x_store_note: why 'auto' did not take the sparse store for sparse count data, if so
+        self.x_store, self.x_store_note, self.n_heavy, nnz, refill = self._select_store(
+            Xd, layout, x_store, x_facts, empty_ch, empty_px, log_shift, h_rule, pg_gamma_w,
+            filled_channels is not None or filled_pixels is not None)
+        st = self.st = self._geometry(shape_2d, tile_px, x_tile)
+        self._build_store(Xd, layout, self.n_heavy, nnz, empty_px)
+        if refill:
+            _set_lines(Xd, layout, empty_px, empty_ch, log_shift)
+        torch.cuda.current_stream().synchronize()
+        del Xd
+        self._ingest_G(G)
+        self._set_hyper_parameters(simplex_H=simplex_H, simplex_W=simplex_W, compute_loss=compute_loss, lambda_L=lambda_L, sigmaL=sigmaL,
+                                   h_rule=h_rule, pg_gamma_w=pg_gamma_w, epsilon_reg=epsilon_reg, log_shift=log_shift,
+                                   dicotomy_tol=dicotomy_tol, tol=tol, xscale=xscale, gw_floor=gw_floor, mu=mu)
+        self._allocate(max_iter, fixed_H, fixed_W, simplex_rows, simplex_W, log_shift, breg_px,
+                       with_pg_q=float(pg_gamma_w) > 0 or int(h_rule) == 2)
+        self._bind()
+        self._launch_policy(fused, autotune, max_iter)
+        if self.sharded:
+            from .sharding import ShardExchange
+            self.exchange = ShardExchange(group, k, st.n_pad, st.ny, bool(st.grid_mode and self.lambda_L != 0.0), self.device, lib=self.lib,
+                                          stream_fn=_stream)
+            if self.exchange.layout.nbytes != int(self.lib.espm_mu_shard_record_bytes(C.byref(st))):
+                raise RuntimeError("record layout of espm_amd.sharding and libespm_mu disagree")
 
-        def _tick(name):   # ESPM_ENGINE_TIMING=1: device-synchronised time of the set-up steps (tools/analysis)
-            if _t_dbg is not None:
-                torch.cuda.synchronize()
-                now = time.perf_counter()
-                print(f"[engine set-up] {name}: {1e3 * (now - _t_dbg[0]):.1f} ms", file=sys.stderr, flush=True)
-                _t_dbg[0] = now
-
-        # ---- X to the device, zero lines, storage type ------------------------------------------
+    # ---- the steps of the set-up, in the order __init__ takes them ------------------------------------------------------------------
+    def _ingest(self, X, layout, x_facts, fix_zero_lines, filled_channels, filled_pixels, log_shift, G, bregman):
+        """X to the device, its checks, the masks of its empty lines (filled when fix_zero_lines), sum_x and the Bregman variant's
+        sums.  Returns (Xd, empty_ch, empty_px, the x_facts that still hold, the Bregman pixel sums or None)."""
+        dev, group = self.device, self.group
         Xd = X if isinstance(X, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(X))
         if Xd.dtype not in (torch.float32, torch.float64):
             Xd = Xd.to(torch.float64)
@@ -125,7 +201,7 @@ class MUEngine:
         self.out_dtype = np.float64 if Xd.dtype == torch.float64 else np.float32
         if x_facts is not None and (group is not None or fix_zero_lines):
             x_facts = None
-        if not (x_facts and x_facts.get("nonneg")) and bool((Xd < 0).any()):
+        if not (x_facts is not None and x_facts.nonneg) and bool((Xd < 0).any()):
             raise ValueError("Negative values in data")  # espm/estimators/base.py:528
         # channels that hold nothing but the log_shift fill (all ranks see the same mask): the sparse store may leave them empty
         empty_ch = None
@@ -148,21 +224,17 @@ class MUEngine:
             if bool(zc.any()) or bool(zp.any()):
                 Xd = Xd.clone()
                 empty_ch, empty_px = zc, zp
-                if layout == "cm":
-                    Xd[:, zp] = log_shift
-                    Xd[zc, :] = log_shift
-                else:
-                    Xd[zp, :] = log_shift
-                    Xd[:, zc] = log_shift
-        if x_facts and "sum_x" in x_facts:
-            self.sum_x = float(x_facts["sum_x"])
+                _set_lines(Xd, layout, zp, zc, log_shift)
+        if x_facts is not None:
+            self.sum_x = float(x_facts.sum_x)
         else:
-            self.sum_x = Xd.sum(dtype=torch.float64)
+            sum_x = Xd.sum(dtype=torch.float64)
             if group is not None:
-                torch.distributed.all_reduce(self.sum_x, group=group)
-            self.sum_x = float(self.sum_x)
-        _tick("sign check, empty lines, sum of X")
+                torch.distributed.all_reduce(sum_x, group=group)
+            self.sum_x = float(sum_x)
+        self._tick("sign check, empty lines, sum of X")
         self.bregman = bool(bregman)
+        breg_px = None
         if self.bregman:
             # Bregman variant (updates.py:40-48, :120-125): sums of X over the channels (per pixel) and over the pixels
             # (per channel, global); built for G = identity only - the reference's own W step needs a square G
@@ -173,32 +245,18 @@ class MUEngine:
             if group is not None:
                 torch.distributed.all_reduce(sr_ch, group=group)
             self._breg_ch = sr_ch.to(torch.float32).contiguous()
-            self._breg_px_local = Xd.sum(dim=ch_axis, dtype=torch.float64).to(torch.float32)
-        # A fit with the Frobenius data term (l2=True with algo="l2_surrogate", smooth_nmf.py:223-237, :404-413, base.py:197-198):
-        # quadratic-surrogate H step, Frobenius W step and loss; on the dense fp32 store
-        self.frobenius = bool(frobenius)
-        if self.frobenius:
-            if float(xscale) != 1.0 or int(h_rule) != 1 or simplex_W:
-                raise NotImplementedError("the Frobenius fit is built for xscale = 1 (hand over the scaled X), "
-                                          "h_rule = 1 and no simplex over W (updates.py:31-36 has none)")
-            x_store = "f32"
-        if h_variant:
-            raise NotImplementedError("h_variant=1 (Y = GW H on the matrix cores) was retired: slower than the vector kernels "
-                                      "at k <= 8 and sensitive to a transcendental-operand hazard (DESIGN.md)")
-        refill = False
+            breg_px = Xd.sum(dim=ch_axis, dtype=torch.float64).to(torch.float32)
+        return Xd, empty_ch, empty_px, x_facts, breg_px
 
-        def set_empty(v):
-            for mask, axis in ((empty_px, px_axis), (empty_ch, ch_axis)):   # (the reference's order, base.py:524-525)
-                if mask is not None:
-                    if axis == 0:
-                        Xd[mask, :] = v
-                    else:
-                        Xd[:, mask] = v
+    def _select_store(self, Xd, layout, x_store, x_facts, empty_ch, empty_px, log_shift, h_rule, pg_gamma_w, masks_given):
+        """The store X goes on: under 'auto' / 'ell' the scan of X, store.choose_store and the ranks' agreement.  Returns (x_store,
+        the note, the number of heavy elements, the non-zero count if the scan took it, whether the caller's tensor needs its
+        fill put back after the build)."""
+        group = self.group
+        note, n_heavy, nnz, refill = None, 0, None, False
         if x_store in ("auto", "ell"):
-            # u8 / ell: integer counts <= 255.  All-zero channels / pixels were filled with 1e-14 above (base.py:519-528),
-            # which is not an integer: such data keep the bf16 store and the reference's exact semantics.
-            # ell (non-zero entries only) when at most ELL_MAX_DENSITY of the entries are non-zero and the GW table
-            # fits in LDS; the decision is taken jointly by all ranks.
+            # All-zero channels / pixels were filled with 1e-14 (base.py:519-528), which is not an integer: such data keep the bf16
+            # store and the reference's exact semantics - unless the sparse store takes them; the decision is taken jointly by all ranks.
             # Channels that are empty in the whole image (common in measured spectra: the bins below the detector's
             # threshold and above the beam energy) do not cost the sparse store: their fill of log_shift = 1e-14 counts
             # per bin moves W, H and the loss by O(1e-14) and is left out of the lists (DESIGN.md section 3); without
@@ -208,105 +266,40 @@ class MUEngine:
             unfilled = (not self.bregman and ((empty_ch is not None and bool(empty_ch.any()))
                                               or (empty_px is not None and bool(empty_px.any()))))
             if unfilled:
-                set_empty(0)
-            known = x_facts if (x_facts and not unfilled and "is_count" in x_facts and "nnz" in x_facts) else None
-            # integer counts above 255 (up to 2^24) are the sparse store's heavy elements (include/espm_mu.h, ell_hv_*) where the fit's
-            # path has them wired in; ESPM_ELL_HEAVY=0 restores the choice without them
+                _set_lines(Xd, layout, empty_px, empty_ch, 0)
             heavy_on = os.environ.get("ESPM_ELL_HEAVY", "1") != "0"
-            if known:
-                is_count = bool(known["is_count"])
-                x_int_max = known.get("x_max") if known.get("is_int") else None
-            else:
-                is_int = bool((Xd == Xd.round()).all())
-                x_int_max = float(Xd.max()) if is_int else None
-                is_count = is_int and x_int_max <= 255
-            n_heavy = 0
-            if not is_count and heavy_on and x_int_max is not None and x_int_max <= _lib.ELL_HEAVY_MAX:
-                n_heavy = int(torch.count_nonzero(Xd >= _lib.ELL_HEAVY_MIN))   # (a pass only for such data)
-            heavy_why = None   # why this fit's path cannot take heavy elements
-            if n_heavy:
-                if int(h_rule) != 0:
-                    heavy_why = "the heavy elements are wired in for the default H rule only"
-                elif self.bregman:
-                    heavy_why = "the heavy elements are not wired into the Bregman variant"
-                elif float(pg_gamma_w) > 0:
-                    heavy_why = "the heavy elements are not wired into the projected-gradient W step"
-            dense_code = 3     # (the store a rank with heavy elements falls back to: bf16 or f32)
-            if bool(is_count):
-                code = 2
-            else:   # (the bf16 round trip is two more passes over X and two temporaries of its size: only when it decides)
-                code = 1 if bool((Xd.to(torch.bfloat16).to(Xd.dtype) - Xd).abs().max() <= 1e-16) else 0
-                if n_heavy:
-                    dense_code = code
-            self.x_store_note = None
-            self.n_heavy = n_heavy
-            if n_heavy:
-                from . import ell as _ell
-                n_pad8 = (self.n + 7) // 8 * 8
-                fits = k <= _lib.WIDE_MAX_K and self.n <= 16384 and _ell.lds_bytes_h(n_pad8, k) <= _lib.ELL_LDS_MAX
-                nnz_x = int(known["nnz"]) if known else int(torch.count_nonzero(Xd))
-                self._nnz_known = nnz_x
-                sparse = float(nnz_x) <= ELL_MAX_DENSITY * Xd.numel()
-                light = n_heavy <= ELL_MAX_HEAVY_FRACTION * nnz_x
-                dense = ("f32", "bf16")[code]
-                if fits and heavy_why is None and (x_store == "ell" or (sparse and light)):
-                    code = 3
-                elif not sparse:
-                    pass
-                elif heavy_why is not None:
-                    self.x_store_note = f"sparse count data with {n_heavy} counts above 255, but {heavy_why}: the dense {dense} store is used"
-                elif not fits:
-                    self.x_store_note = (f"sparse count data with {n_heavy} counts above 255, but the sparse store is built for up to "
-                                         f"{_lib.WIDE_MAX_K} components and n <= 16384 with a G W table that fits in LDS (n={self.n}, "
-                                         f"k={k}): the dense {dense} store is used")
-                else:
-                    self.x_store_note = (f"sparse count data, but {n_heavy} of its {nnz_x} non-zero counts are above 255 (more than "
-                                         f"{ELL_MAX_HEAVY_FRACTION:.0%}, where the sparse store stops paying): the dense {dense} store is used")
-            if code == 2:
-                from . import ell as _ell
-                n_pad8 = (self.n + 7) // 8 * 8
-                fits = k <= _lib.WIDE_MAX_K and self.n <= 16384 and _ell.lds_bytes_h(n_pad8, k) <= _lib.ELL_LDS_MAX
-                nnz_x = int(known["nnz"]) if known else int(torch.count_nonzero(Xd))
-                self._nnz_known = nnz_x          # (the sparse store's build does not count again: a pass over the 8-bit copy was 2.6 of its 12 ms)
-                sparse = float(nnz_x) <= ELL_MAX_DENSITY * Xd.numel()
-                if fits and (x_store == "ell" or sparse):
-                    code = 3
-                elif sparse and k > _lib.WIDE_MAX_K:
-                    self.x_store_note = (f"sparse count data, but the sparse store is built for up to {_lib.WIDE_MAX_K} components (k={k}: a table row of "
-                                         "32 floats leaves a workgroup's LDS no room): the dense 8-bit store is used, both contractions on the matrix cores")
-                elif sparse and not fits:
-                    # not silently (missing 3): sparse count data that the sparse store would take - about 3 x the dense store's
-                    # rate at 20 % non-zero entries - but whose G W table does not fit a workgroup's LDS next to a tile's numerators
-                    # (rows of 12 / 16 floats from 9 / 13 components on: 16 components stop at 2048 channels, 12 at 2896)
-                    import warnings
-                    self.x_store_note = (f"sparse count data, but the sparse store's table for n={self.n}, k={k} needs "
-                                         f"{_ell.lds_bytes_h(n_pad8, k)} bytes of LDS (limit {_lib.ELL_LDS_MAX}): the dense 8-bit store is used, "
-                                         "about 3 x slower per iteration at this density")
-                    warnings.warn("espm_amd: " + self.x_store_note, RuntimeWarning, stacklevel=3)
-            flag = torch.tensor([code, dense_code], device=dev, dtype=torch.int32)
-            _tick("storage type (integer counts, bf16-exact, density)")
+            facts = _scan_x(Xd, None if unfilled else x_facts, heavy_on)
+            n_heavy, nnz = facts.n_heavy, facts.nnz
+            code, dense_code, note, warn = choose_store(self.n, self.p, self.k, x_store, facts, h_rule=h_rule, bregman=self.bregman,
+                                                        pg_gamma_w=pg_gamma_w, heavy_on=heavy_on)
+            if warn:
+                import warnings
+                warnings.warn("espm_amd: " + note, RuntimeWarning, stacklevel=4)   # (two frames above __init__)
+            flag = torch.tensor([code, dense_code], device=self.device, dtype=torch.int32)
+            self._tick("storage type (integer counts, bf16-exact, density)")
             if group is not None:
                 torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN, group=group)
             # every rank takes the sparse store, or none does; then no rank whose counts exceed 255 takes the 8-bit store
             flag = flag[:1] if int(flag[0]) == 3 else flag.min().reshape(1)
             if unfilled and int(flag.item()) != 3:
-                set_empty(log_shift)
+                _set_lines(Xd, layout, empty_px, empty_ch, log_shift)
                 flag.fill_(0)      # (the fill is neither an integer nor a bf16 value)
             if x_store == "ell" and int(flag.item()) != 3:
                 raise ValueError("x_store='ell' needs integer counts <= 2^24 (above 255: the default H rule, no Bregman variant, no "
                                  "projected-gradient W step), n <= 16384 and a GW table that fits in LDS (12- or 16-float rows from 9 components on)")
-            refill = unfilled and int(flag.item()) == 3 and (filled_channels is not None or filled_pixels is not None)  # (the caller's tensor: put the fill back)
-            x_store = ("f32", "bf16", "u8", "ell")[int(flag.item())]
+            refill = unfilled and int(flag.item()) == 3 and masks_given  # (the caller's tensor: put the fill back)
+            x_store = CODES[int(flag.item())]
         if int(h_rule) != 0 and x_store in ("u8", "bf16"):
             x_store = "f32"   # the alternate H rules are built for the sparse and the fp32 store
-        if x_store not in ("u8", "bf16", "f32", "ell"):
+        if x_store not in CODES:
             raise ValueError("x_store must be 'auto', 'ell', 'u8', 'bf16' or 'f32'")
-        self.x_store = x_store
-        self.x_store_note = getattr(self, "x_store_note", None)   # (why 'auto' did not take the sparse store for sparse count data, if so)
+        return x_store, note, n_heavy, nnz, refill
 
+    def _geometry(self, shape_2d, tile_px, x_tile):
+        """The MUState with the problem's sizes and the tiling espm_mu_query gives them (tile_px / x_tile override it)."""
+        p, x_store = self.p, self.x_store
         st = MUState()
-        self.st = st
-        st.n, st.p, st.k = self.n, self.p, k
+        st.n, st.p, st.k = self.n, p, self.k
         st.x_dtype = {"u8": _lib.X_U8, "bf16": _lib.X_BF16, "f32": _lib.X_F32, "ell": _lib.X_ELL}[x_store]
         if shape_2d is not None:
             nx, ny = int(shape_2d[0]), int(shape_2d[1])
@@ -323,22 +316,38 @@ class MUEngine:
             st.tile_px = st.x_tile = int(force_tile)
             st.ell_pb = 2 * st.tile_px        # (a block of the W accumulation is two H tiles, include/espm_mu.h)
             st.nblk_w = (p + st.ell_pb - 1) // st.ell_pb
-        p_total = torch.tensor([p], dtype=torch.int64, device=dev)
-        if group is not None:
-            torch.distributed.all_reduce(p_total, group=group)
+        if x_store != "ell":
+            if tile_px is not None:  # override the H-step tile chosen by espm_mu_query (tests, tuning)
+                st.tile_px = int(tile_px)
+                st.x_tile = int(tile_px)
+            if x_tile is not None:
+                st.x_tile = int(x_tile)
+        p_total = torch.tensor([p], dtype=torch.int64, device=self.device)
+        if self.group is not None:
+            torch.distributed.all_reduce(p_total, group=self.group)
         st.p_total = int(p_total.item())
         self.p_total = st.p_total
+        return st
 
+    def _build_store(self, Xd, layout, n_heavy, nnz, empty_px):
+        """X into its store: the sparse count store with the bookkeeping of its pixels without counts and of its heavy elements, or
+        the two dense copies."""
+        st, dev, k = self.st, self.device, self.k
         self.ell = None
         self.fill_px = self.fill_num = None
-        if x_store == "ell":
+        torch_builder = self.x_store == "ell" and os.environ.get("ESPM_ELL_BUILDER", "hip") == "torch"   # the tensor-op builder (tests cross-check the two)
+        if not torch_builder:   # X as espm_mu_pack_x and the heavy elements' passes read it
+            Xc = Xd.contiguous()
+            src = (_ptr(Xc), _lib.SRC_F64 if Xc.dtype == torch.float64 else _lib.SRC_F32, _lib.LAYOUT_PM if layout == "pm" else _lib.LAYOUT_CM,
+                   Xc.shape[1])
+        if self.x_store == "ell":
             from . import ell as _ell
             self.x_cm = self.x_pm = None
-            if os.environ.get("ESPM_ELL_BUILDER", "hip") == "torch":  # the tensor-op builder (tests cross-check the two)
+            if torch_builder:
                 self.ell = _ell.build(Xd if layout == "pm" else Xd.t(), st.p_pad, st.ell_cbits, st.tile_px)
             else:
-                self.ell = self._build_ell(Xd.contiguous(), layout)
-                _tick("sparse store build")
+                self.ell = self._build_ell(src, n_heavy, nnz)
+                self._tick("sparse store build")
             assert self.ell["n_cg"] == st.n_cg and self.ell["nblk_w"] == st.nblk_w
             # pixels without counts: marked in the per-pixel loss constants, their fill's numerator has its own small pass
             fill_n = 0
@@ -363,25 +372,16 @@ class MUEngine:
                 self.fill_num = torch.zeros((k, fill_n + npx), dtype=torch.float32, device=dev)
             self.x_bytes = 4 * (self.ell["ell_h"].numel() + self.ell["ell_w"].numel()) + (16 * hv["n"] if hv is not None else 0)
         else:
-            xt = {"u8": torch.uint8, "bf16": torch.bfloat16, "f32": torch.float32}[x_store]
-            if tile_px is not None:  # override the H-step tile chosen by espm_mu_query (tests, tuning)
-                st.tile_px = int(tile_px)
-                st.x_tile = int(tile_px)
-            if x_tile is not None:
-                st.x_tile = int(x_tile)
+            xt = {"u8": torch.uint8, "bf16": torch.bfloat16, "f32": torch.float32}[self.x_store]
             self.x_cm = torch.empty((st.p_pad // st.x_tile, st.n_cm, st.x_tile), dtype=xt, device=dev)
             self.x_pm = torch.empty((self.p, st.n_pad), dtype=xt, device=dev)
-            Xd = Xd.contiguous()
-            self._check(self.lib.espm_mu_pack_x(_ptr(Xd), _lib.SRC_F64 if Xd.dtype == torch.float64 else _lib.SRC_F32,
-                                     _lib.LAYOUT_PM if layout == "pm" else _lib.LAYOUT_CM, Xd.shape[1], self.n, self.p,
-                                     _ptr(self.x_cm), _ptr(self.x_pm), st.x_dtype, st.n_pad, st.p_pad, st.x_tile, st.n_cm, _stream()))
+            self._check(self.lib.espm_mu_pack_x(*src, self.n, self.p, _ptr(self.x_cm), _ptr(self.x_pm), st.x_dtype, st.n_pad, st.p_pad,
+                                                st.x_tile, st.n_cm, _stream()))
             self.x_bytes = self.x_cm.numel() * self.x_cm.element_size() + self.x_pm.numel() * self.x_pm.element_size()
-        if refill:
-            set_empty(log_shift)
-        torch.cuda.current_stream().synchronize()
-        del Xd
 
-        # ---- G ------------------------------------------------------------------------------------
+    def _ingest_G(self, G):
+        """G, its transpose and its column sums on the device (None: the identity)."""
+        st, dev = self.st, self.device
         if G is not None:
             Gh = np.ascontiguousarray(np.asarray(G, dtype=np.float32))
             if Gh.ndim != 2 or Gh.shape[0] != self.n:
@@ -397,7 +397,10 @@ class MUEngine:
             st.m = 0
         self.M = self.m if self.m > 0 else self.n
 
-        # ---- hyper-parameters -----------------------------------------------------------------------
+    def _set_hyper_parameters(self, *, simplex_H, simplex_W, compute_loss, lambda_L, sigmaL, h_rule, pg_gamma_w, epsilon_reg, log_shift,
+                              dicotomy_tol, tol, xscale, gw_floor, mu):
+        """The scalars of the update rules into the state struct, mu to the device."""
+        st = self.st
         st.simplex_h, st.simplex_w = int(bool(simplex_H)), int(bool(simplex_W))
         st.compute_loss = int(bool(compute_loss))
         st.lambda_l, st.sigma_l = float(lambda_L), float(sigmaL)
@@ -412,9 +415,11 @@ class MUEngine:
         if mu_arr.ndim == 0 and float(mu_arr) == 0.0:
             self.mu = None
         else:
-            self.mu = torch.from_numpy(np.broadcast_to(mu_arr, (k,)).astype(np.float32).copy()).to(dev)
+            self.mu = torch.from_numpy(np.broadcast_to(mu_arr, (self.k,)).astype(np.float32).copy()).to(self.device)
 
-        # ---- state and workspaces --------------------------------------------------------------------
+    def _allocate(self, max_iter, fixed_H, fixed_W, simplex_rows, simplex_W, log_shift, breg_px, with_pg_q):
+        """State and workspaces."""
+        st, dev, k = self.st, self.device, self.k
         f32 = dict(dtype=torch.float32, device=dev)
         f64 = dict(dtype=torch.float64, device=dev)
         self.w = [torch.zeros((self.M, k), **f32) for _ in range(2)]
@@ -425,7 +430,7 @@ class MUEngine:
         nblk_h = (self.p + st.tile_px - 1) // st.tile_px
         self.hpart = torch.zeros((nblk_h, self.V.HP_STRIDE), **f64)
         self.hstat = [torch.zeros(self.V.HS_STRIDE, **f64) for _ in range(2)]
-        _tick("rest up to the state buffers")
+        self._tick("rest up to the state buffers")
         self.a_slab = torch.zeros((st.nblk_w, k, st.n_pad), **f32)
         self.a = torch.zeros((k, st.n_pad), **f32)
         self.w_scratch = torch.zeros((2, self.M, k), **f32)
@@ -443,7 +448,14 @@ class MUEngine:
                 raise ValueError("No solution exists!")
         else:
             self.simplex_rows = None
+        if self.bregman:
+            self.breg_px = torch.zeros(st.p_pad, **f32)
+            self.breg_px[:self.p] = breg_px
+        self.pg_q = torch.zeros((self.hist_len, 2), **f64) if with_pg_q else None
 
+    def _bind(self):
+        """Every device pointer of the state struct."""
+        st = self.st
         if self.ell is None:
             st.x_cm, st.x_pm = self.x_cm.data_ptr(), self.x_pm.data_ptr()
         else:
@@ -474,9 +486,6 @@ class MUEngine:
         st.simplex_rows = self.simplex_rows.data_ptr() if self.simplex_rows is not None else None
         st.halo_top = st.halo_bot = None
         if self.bregman:
-            self.breg_px = torch.zeros(st.p_pad, **f32)
-            self.breg_px[:self.p] = self._breg_px_local
-            del self._breg_px_local
             st.breg_sr_px, st.breg_sr_ch = self.breg_px.data_ptr(), self._breg_ch.data_ptr()
         else:
             st.breg_sr_px = st.breg_sr_ch = None
@@ -484,9 +493,12 @@ class MUEngine:
         st.hstat[0], st.hstat[1] = self.hstat[0].data_ptr(), self.hstat[1].data_ptr()
         st.a_slab, st.a, st.w_scratch = self.a_slab.data_ptr(), self.a.data_ptr(), self.w_scratch.data_ptr()
         st.hist, st.hist_len = self.hist.data_ptr(), self.hist_len
-        self.pg_q = torch.zeros((self.hist_len, 2), **f64) if float(pg_gamma_w) > 0 or int(h_rule) == 2 else None
         st.pg_q = self.pg_q.data_ptr() if self.pg_q is not None else None
         st.cur, st.it = 0, 0
+
+    def _launch_policy(self, fused, autotune, max_iter):
+        """How the iteration is launched: fused or not, streamed list loads, whether the first load_state times the plans."""
+        st = self.st
         # both half-steps of an iteration in one launch where the library's fused kernel applies (sparse store at 512-pixel
         # tiles, default H rule: include/espm_mu.h, no_fused); `fused=False` keeps the two launches (A/B, tests)
         if os.environ.get("ESPM_FUSED"):   # tests: "always" runs the fused launch on small blocks too, "0" never
@@ -495,7 +507,7 @@ class MUEngine:
         # lists larger than the last-level cache are read with loads that do not allocate there (include/espm_mu.h: ell_stream;
         # ESPM_ELL_STREAM_MB: another threshold, for A/B - 0 streams always, a huge one never)
         limit = float(os.environ["ESPM_ELL_STREAM_MB"]) * 2 ** 20 if os.environ.get("ESPM_ELL_STREAM_MB") else _lib.ELL_STREAM_BYTES
-        st.ell_stream = int(x_store == "ell" and self.x_bytes > limit)
+        st.ell_stream = int(self.x_store == "ell" and self.x_bytes > limit)
         self._accum_done = False
         # autotune: at the first load_state the launch plans that apply to this problem are timed on the ingested image and
         # the fastest is kept (see autotune_plan)
@@ -504,31 +516,22 @@ class MUEngine:
         self._autotune = (int(max_iter) >= AUTOTUNE_MIN_ITERS) if autotune == "auto" else bool(autotune)
         self.plan_timings = None
 
-        # ---- sharding -----------------------------------------------------------------------------------
-        if self.sharded:
-            from .sharding import ShardExchange
-            self.exchange = ShardExchange(group, k, st.n_pad, st.ny, bool(st.grid_mode and self.lambda_L != 0.0), dev, lib=self.lib,
-                                          stream_fn=_stream)
-            if self.exchange.layout.nbytes != int(self.lib.espm_mu_shard_record_bytes(C.byref(st))):
-                raise RuntimeError("record layout of espm_amd.sharding and libespm_mu disagree")
-
     # ------------------------------------------------------------------------------------------------
-    def _build_ell(self, Xd, layout):
+    def _build_ell(self, src, n_heavy, nnz):
         """Sparse count store through the C ABI: dense 8-bit pixel-major copy (espm_mu_pack_x) -> espm_mu_ell_count /
-        _plan / _fill.  Same result as espm_amd.ell.build (tests/test_gpu_updates.py::test_ell_builders_agree)."""
+        _plan / _fill.  Same result as espm_amd.ell.build (tests/test_gpu_updates.py::test_ell_builders_agree).  src: X as the
+        ABI reads it (pointer, ESPM_SRC_*, ESPM_LAYOUT_*, leading dimension); n_heavy, nnz: its counts above 255 and its non-zero
+        entries, which the store's choice has counted."""
         st, dev = self.st, self.device
         i32 = dict(dtype=torch.int32, device=dev)
         x8 = torch.empty((self.p, st.n_pad), dtype=torch.uint8, device=dev)
         # (the channel-major copy beside it: the channel lists' fill reads it with 16-byte loads, include/espm_mu.h; ESPM_ELL_BUILD_CM=0: without, A/B)
         x8c = torch.empty((st.p_pad // _lib.PPAD, st.n_cm, _lib.PPAD), dtype=torch.uint8, device=dev) if os.environ.get("ESPM_ELL_BUILD_CM") != "0" else None
-        self._check(self.lib.espm_mu_pack_x(_ptr(Xd), _lib.SRC_F64 if Xd.dtype == torch.float64 else _lib.SRC_F32,
-                                 _lib.LAYOUT_PM if layout == "pm" else _lib.LAYOUT_CM, Xd.shape[1], self.n, self.p,
-                                 _ptr(x8c) if x8c is not None else None, _ptr(x8), _lib.X_U8, st.n_pad, st.p_pad, _lib.PPAD, st.n_cm, _stream()))
+        self._check(self.lib.espm_mu_pack_x(*src, self.n, self.p, _ptr(x8c) if x8c is not None else None, _ptr(x8), _lib.X_U8, st.n_pad,
+                                            st.p_pad, _lib.PPAD, st.n_cm, _stream()))
         hv = None
-        if getattr(self, "n_heavy", 0):
+        if n_heavy:
             # counts above 255: out of the 8-bit copies (the lists leave them out), kept pixel-major with their values (include/espm_mu.h)
-            src = (_ptr(Xd), _lib.SRC_F64 if Xd.dtype == torch.float64 else _lib.SRC_F32, _lib.LAYOUT_PM if layout == "pm" else _lib.LAYOUT_CM,
-                   Xd.shape[1])
             hv_cnt = torch.empty(self.p, **i32)
             self._check(self.lib.espm_mu_ell_heavy_count(C.byref(st), *src, _ptr(x8), _ptr(x8c) if x8c is not None else None, _ptr(hv_cnt),
                                                          _stream()))
@@ -569,9 +572,6 @@ class MUEngine:
                                                        _ptr(ell_h), _ptr(ell_w), _ptr(bkt_px) if hist else None, _ptr(bkt_bc) if hist else None, _stream()))
         finally:
             st.x_cm = None
-        nnz = getattr(self, "_nnz_known", None)
-        if nnz is None:
-            nnz = int(torch.count_nonzero(x8))   # (padding channels hold zeros)
         torch.cuda.current_stream().synchronize()
         out = dict(ell_h=ell_h, ell_h_off=h_off, klc=klc, pix_perm=pix_perm, ell_w=ell_w, ell_w_off=w_off, chan_perm=chan_perm, n_cg=st.n_cg,
                    nblk_w=st.nblk_w, nnz=nnz, entries_h=int(cnt_px[0].sum()), entries_w=int(cnt_bc[0].sum()), rows_h=rows_h,

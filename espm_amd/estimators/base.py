@@ -19,6 +19,7 @@ from sklearn.utils.validation import check_is_fitted, validate_data
 
 from espm_amd.conf import log_shift
 from espm_amd.estimators.updates import initialize_algorithms
+from espm_amd.store import XFacts
 from espm_amd.utils import create_laplacian_matrix, identity_laplacian, rescaled_DH
 
 
@@ -101,7 +102,7 @@ def _upload_with_scans(host, device, log_shift):
         col_sum += xd.sum(dim=0)
         s1 += rs.sum()
         s2 += (xd * torch.log(xd.clamp_min(log_shift))).sum()
-        # (what the engine's choice of a store asks of X - integer counts up to 255, how many non-zero: engine.py - while the data pass by)
+        # (what the engine's choice of a store asks of X - integer counts up to 255, how many non-zero: store.XFacts - while the data pass by)
         facts[:2] += torch.stack(((x != x.round()).sum(), (x != 0).sum())).to(torch.float64)
         facts[2] = torch.maximum(facts[2], x.max().to(torch.float64))
         del x, fin, xd, rs
@@ -641,8 +642,7 @@ class NMFEstimator(ABC, TransformerMixin, BaseEstimator):
                 numel = float(Xv.size)
                 fill = n_zero_lines > 0
                 if not fill and not x_local:   # what the scans know about X as it goes to the engine (a filled X is another array: the engine looks itself)
-                    x_facts = dict(nonneg=True, sum_x=s1, is_count=bool(n_nonint == 0 and x_max <= 255), nnz=int(nnz),
-                                   is_int=bool(n_nonint == 0), x_max=x_max)
+                    x_facts = XFacts(nonneg=True, sum_x=s1, is_int=bool(n_nonint == 0), x_max=x_max, nnz=int(nnz))
                 if fill:
                     Xd[:, zp] = self.log_shift
                     Xd[zc, :] = self.log_shift

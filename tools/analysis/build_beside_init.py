@@ -8,6 +8,7 @@ import numpy as np
 import torch
 from espm_amd import init_device as idv, synth
 from espm_amd.engine import MUEngine
+from espm_amd.store import XFacts
 
 dev = torch.device("cuda", 0)
 torch.cuda.set_device(0)
@@ -17,7 +18,7 @@ Xpm = synth.sample_torch(prob, dev, seed=1000)       # (p, n)
 Xd = Xpm.T
 Xh = np.empty((n, nx * ny), dtype=np.float32)
 nnz = int(torch.count_nonzero(Xpm))
-facts = dict(nonneg=True, sum_x=float(Xpm.sum(dtype=torch.float64)), is_count=True, nnz=nnz)
+facts = XFacts(nonneg=True, sum_x=float(Xpm.sum(dtype=torch.float64)), is_int=True, x_max=float(Xpm.max()), nnz=nnz)
 
 
 def init():
@@ -28,7 +29,7 @@ def build(stream=None):
     ctx = torch.cuda.stream(stream) if stream is not None else torch.cuda.stream(torch.cuda.current_stream())
     with ctx:
         eng = MUEngine(Xpm, k, layout="pm", shape_2d=(nx, ny), lambda_L=1.0, simplex_H=True, simplex_W=False, tol=0.0, max_iter=200, device=dev,
-                       x_facts=dict(facts), fix_zero_lines=False)
+                       x_facts=facts, fix_zero_lines=False)
         torch.cuda.current_stream().synchronize()
     return eng
 

@@ -2,7 +2,7 @@
 """Heavy elements of the sparse store (include/espm_mu.h, ell_hv_*) at the headline geometry: per-iteration time of
   (a) the image as generated,  (b) one element set to 1000,  (c) a fraction of the non-zero elements set to counts in 256 .. 4000,
 each on the sparse store and (c) also on the forced fp32 store, interleaved over rounds, medians.  Also the set-up time of each engine
-(the store's build included) and, with --crossover, more fractions on the sparse store to place engine.ELL_MAX_HEAVY_FRACTION.
+(the store's build included) and, with --crossover, more fractions on the sparse store to place store.ELL_MAX_HEAVY_FRACTION.
 --profile FRAC: only the sparse store at that fraction, for a rocprofv3 --kernel-trace --stats run.  JSON lines on stdout."""
 import argparse
 import json
