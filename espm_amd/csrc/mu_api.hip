@@ -36,7 +36,7 @@ static int roundup(int v, int m) { return (v + m - 1) / m * m; }
   F(ell_h_off) F(ell_klc) F(ell_w) F(ell_w_off) F(chan_perm) F(ell_cbits) F(n_cg) F(pix_perm) F(g_t) F(breg_sr_px) \
   F(breg_sr_ch) F(h_rule) F(pg_gamma_w) F(pg_q) F(ell_fill_px) F(ell_fill_num) F(ell_fill_n) F(tail_mode) F(no_fused) \
   F(ell_pb) F(ell_stream) F(ell_hv_n) F(ell_hv_npx) F(ell_hv_ngrp) F(ell_hv_px) F(ell_hv_px_off) F(ell_hv_pm) F(ell_hv_klc) F(ell_hv_kl) \
-  F(ell_hv_grp) F(ell_hv_grp_off) F(ell_hv_wm)
+  F(ell_hv_grp) F(ell_hv_grp_off) F(ell_hv_wm) F(hpart_alt)
 
 // the caller's view of the state must be this library's (include/espm_mu.h, ESPM_MU_ABI_VERSION): checked before any field is read
 static int check_abi(const espm_mu_state* st) {
@@ -625,6 +625,61 @@ static int iterate_impl(espm_mu_state* st, int n_iter, int final_loss, espm_stre
   }
   if (pending)
     if (int rc = launch_w_update_tail(tail, s)) return rc;
+  if (final_loss) return espm_mu_loss_only(st, st->cur, st->it, stream);
+  return ESPM_OK;
+}
+
+// ---- H-only iterations (include/espm_mu.h) -------------------------------------------------------------------------------------
+static bool h_chain_ok(const espm_mu_state* st) { return st->hpart_alt != nullptr && h_chain_built(st); }
+
+int espm_mu_h_chain_applies(const espm_mu_state* st) {
+  if (int rc = check_state(st)) return rc;   // (negative: a state the library cannot read)
+  return h_chain_ok(st) ? 1 : 0;
+}
+
+int espm_mu_iterate_h(espm_mu_state* st, int n_iter, int final_loss, espm_stream_t stream) {
+  if (int rc = check_state(st)) return rc;
+  ESPM_REQUIRE(n_iter >= 0, "n_iter must be >= 0");
+  ESPM_REQUIRE(st->it + n_iter < st->hist_len, "history too short: it=%d + %d >= %d", st->it, n_iter, st->hist_len);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n_iter > 0)   // rel_W of an update that leaves W alone (base.py:323)
+    if (int rc = check_hip(hipMemset2DAsync(st->hist + (size_t)(st->it + 1) * ESPM_HI_STRIDE + ESPM_HI_REL_W, ESPM_HI_STRIDE * sizeof(double), 0,
+                                            sizeof(double), (size_t)n_iter, s), "iterate_h: rel_W"))
+      return rc;
+  if (h_chain_ok(st) && n_iter > 0) {
+    double* rec[2] = {st->hpart, st->hpart_alt};
+    for (int i = 0; i < n_iter; ++i) {
+      const int cur = st->cur, slot = st->it;
+      HStepArgs a = make_h_args(st, cur, 1);
+      a.hpart = rec[i & 1];
+      if (i > 0) {   // the records of the step before: their statistics for this step, their history row by the extra workgroup
+        a.chain_prev = rec[(i - 1) & 1];
+        a.chain_nb = nblk_h(st);
+        a.chain_fin_on = 1;
+        a.chain_fin = finalize_args(st, 1 - cur, slot - 1, true);
+        a.chain_fin.have_prev = slot - 1 > 0;
+        a.chain_fin.hpart = a.chain_prev;
+      }
+      if (st->x_dtype == ESPM_X_ELL)   // pixels without counts: the numerator of their log_shift fill first (include/espm_mu.h)
+        if (int rc = ell_pre_h(st, cur, s)) return rc;
+      if (int rc = launch_h_chain(a, st->x_dtype, st->tile_px, nblk_h(st), s)) return rc;
+      st->cur = 1 - cur;
+      st->it = slot + 1;
+    }
+    // the last step's records
+    HFinalizeArgs fin = finalize_args(st, 1 - st->cur, st->it - 1, true);
+    fin.have_prev = st->it - 1 > 0;
+    fin.hpart = rec[(n_iter - 1) & 1];
+    if (int rc = launch_h_finalize(fin, s)) return rc;
+  } else {
+    for (int i = 0; i < n_iter; ++i) {
+      const int cur = st->cur, slot = st->it;
+      if (int rc = espm_mu_step_h(st, cur, 1, stream)) return rc;
+      if (int rc = launch_h_finalize(finalize_args(st, cur, slot, true), s)) return rc;
+      st->cur = 1 - cur;
+      st->it = slot + 1;
+    }
+  }
   if (final_loss) return espm_mu_loss_only(st, st->cur, st->it, stream);
   return ESPM_OK;
 }

@@ -638,6 +638,16 @@ __device__ __forceinline__ float stencil_hl(const float* hrow, const float* halo
 }
 
 // kernel-side argument blocks and launchers (mu_h_step.hip, mu_w_step.hip, mu_aux.hip)
+struct HFinalizeArgs {
+  const double* hpart;
+  const double* colsum_gw;
+  const double* hstat_in;
+  double* hstat_out;
+  double* hist_slot;
+  int nblk, k, compute_loss, have_prev;
+  float xscale;
+  double* pg_q;  // projected-gradient rule: where the sum of the records' PGQ field goes, else null
+};
 struct HStepArgs {
   const void* x_cm;
   const void* x_pm;  // pixel-major copy (p, n_pad): the matrix-core H-step of the wide build streams this one
@@ -683,16 +693,14 @@ struct HStepArgs {
   // fused half-steps (mu_fused_kernel.hpp): a workgroup covers TWO record slots of hpart - its record goes to slot
   // 2 * blockIdx.x of rec_nb, zeros (neutral for every field) to the next; 0: one record per workgroup
   int rec_nb;
-};
-struct HFinalizeArgs {
-  const double* hpart;
-  const double* colsum_gw;
-  const double* hstat_in;
-  double* hstat_out;
-  double* hist_slot;
-  int nblk, k, compute_loss, have_prev;
-  float xscale;
-  double* pg_q;  // projected-gradient rule: where the sum of the records' PGQ field goes, else null
+  // chained H-only iteration (espm_mu_iterate_h, the CHAIN instances: mu_h_chain.hpp).  chain_prev: the records the PREVIOUS launch
+  // wrote (the other parity of the record buffers, chain_nb blocks): every workgroup reduces the row sums and maxima of h_in from
+  // them itself, in espm_mu_h_finalize's order, into 8 k doubles of LDS at byte offset chain_lds_off - hstat_in is then not read
+  // (null: the first launch of a batch reads hstat_in).  chain_fin_on: one extra workgroup reduces those records as chain_fin says
+  // (the previous step's history row and hstat); tail_on is then 1 too - the extra workgroup is not a record.
+  const double* chain_prev;
+  int chain_nb, chain_lds_off, chain_fin_on;
+  HFinalizeArgs chain_fin;
 };
 // index bits of a W-step entry of the sparse store: log2 of the pixels per block (64 .. 1024)
 __host__ __device__ inline int ell_pbits(int pb) {
@@ -917,6 +925,9 @@ inline HStepArgs make_h_args(const espm_mu_state* st, int src, int write_h) {
   a.cs_parts = nullptr;
   a.cs_nbk = a.cs_lds_off = a.tail_on = 0;
   a.rec_nb = 0;
+  a.chain_prev = nullptr;
+  a.chain_nb = a.chain_lds_off = a.chain_fin_on = 0;
+  a.chain_fin = HFinalizeArgs{};
   a.n_pad = st->n_pad;
   return a;
 }
@@ -946,6 +957,9 @@ inline WAccumArgs make_w_args(const espm_mu_state* st) {
 }
 
 int dispatch_h_step(const HStepArgs& args, int x_dtype, int tile_px, int nblk, hipStream_t stream);
+// the chained instances (mu_h_chain.hip): whether one is built for the launch, and the launch (nblk workgroups + the extra one when args.chain_fin_on)
+bool h_chain_built(const espm_mu_state* st);
+int launch_h_chain(const HStepArgs& args, int x_dtype, int tile_px, int nblk, hipStream_t stream);
 int launch_h_finalize(const HFinalizeArgs& args, hipStream_t stream);
 int launch_h_ell(const HStepArgs& args, int nblk, hipStream_t stream);
 int launch_fused_ell(const HStepArgs& h, const WAccumArgs& w, int nblk, hipStream_t stream, int static_units = 0, int stream_lists = 0);

@@ -474,7 +474,8 @@ __device__ __forceinline__ void ell_h_rows(const uint32_t* lrow, int x0, int x1,
 //     most two partial numerators.
 //   otherwise every 64-pixel list group is walked by `nsplit` waves, each taking a contiguous slice of its rows
 //     (small images use nsplit = 2, 4 or 8 so that the grid still covers the chip).
-template <int K, bool LOSS, int UNR, int RULE = 0>
+// CHAIN: the chained H-only iteration (mu_h_chain.hpp); the extra workgroup is then the record reduction of the previous step, not a W update's tail.
+template <int K, bool LOSS, int UNR, int RULE = 0, bool CHAIN = false>
 __global__ __launch_bounds__(ESPM_ELL_TILE, (K > 8 ? 2 : 4)) void h_step_ell_kernel(const HStepArgs a) {   // (more than 8 components: 256 registers, one workgroup per CU by its LDS anyway)
   constexpr int NT = ESPM_ELL_TILE;
   constexpr bool PAIRS_OK = K <= ESPM_ELL_PAIR_MAX_K;
@@ -485,7 +486,15 @@ __global__ __launch_bounds__(ESPM_ELL_TILE, (K > 8 ? 2 : 4)) void h_step_ell_ker
   const int TP = a.ell_tp;             // pixels of this workgroup: 64 * (8 / nsplit)
   const int gpw = TP >> 6;             // list groups per workgroup
   const bool pairs = PAIRS_OK && gpw == NT / 64;
-  if (a.tail_on && blockIdx.x == gridDim.x - 1) {   // (uniform) the extra workgroup: tail of the previous W update
+  double* chain_scr = nullptr;
+  if constexpr (CHAIN) {
+    if (a.chain_fin_on && blockIdx.x == gridDim.x - 1) {   // (uniform) the extra workgroup: the previous step's records
+      chain_finalize_wg(a.chain_fin, reinterpret_cast<double*>(smem));
+      return;
+    }
+    chain_scr = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(smem) + a.chain_lds_off);
+    if (a.chain_prev) chain_stats_wave_stage<K>(a.chain_prev, a.chain_nb, chain_scr);   // (combined behind the epilogue's barrier)
+  } else if (a.tail_on && blockIdx.x == gridDim.x - 1) {   // (uniform) the extra workgroup: tail of the previous W update
     w_tail_body<20>(a.tail, reinterpret_cast<double*>(smem));
     return;
   }
@@ -556,7 +565,10 @@ __global__ __launch_bounds__(ESPM_ELL_TILE, (K > 8 ? 2 : 4)) void h_step_ell_ker
     __syncthreads();
     form_cs();
   }
-  h_epilogue<K, true, RULE>(a, part, nparts, TP, tile0, LOSS ? kl : 0.f, cs_lds);
+  if constexpr (CHAIN)
+    h_epilogue<K, true, RULE, 0, false, HEpiNoHook, true>(a, part, nparts, TP, tile0, LOSS ? kl : 0.f, cs_lds, nullptr, 0, false, nullptr, -1.f, HEpiNoHook(), nullptr, 0, nullptr, chain_scr);
+  else
+    h_epilogue<K, true, RULE>(a, part, nparts, TP, tile0, LOSS ? kl : 0.f, cs_lds);
 }
 
 // ---- W accumulation ---------------------------------------------------------------------------------

@@ -10,6 +10,7 @@
 #define ESPM_FUSED_RED_PACKED 1
 #endif
 #include "mu_common.hpp"
+#include "mu_h_chain.hpp"
 
 namespace espm {
 
@@ -166,13 +167,16 @@ struct HEpiNoHook {
 };
 // after_pixels(): called by every thread behind its pixels' update, ahead of the record reduction and its barrier (the fused kernel
 // requests the first rows of its W walk there).
-template <int K, bool EARLY = true, int RULE = 0, int MAXP = 0, bool PLAIN = false, typename Hook = HEpiNoHook>
+// CHAIN (mu_h_chain.hpp): where a.chain_prev is set, the statistics of h_in come from the previous launch's records instead of
+// a.hstat_in: as `chain`, reduced at the start of the kernel (the dense kernels), or - chain_scr - combined here behind the barrier
+// from the wave stage the kernel left in LDS (the sparse kernel, whose walk has no scalar register to spare for them).
+template <int K, bool EARLY = true, int RULE = 0, int MAXP = 0, bool PLAIN = false, typename Hook = HEpiNoHook, bool CHAIN = false>
 __device__ __forceinline__ void h_epilogue(const HStepArgs& a, float* smem, int nparts, int TP, int tile0, float kl_lane,
                                            const double* colsum = nullptr,   // the workgroup's own copy of colsum(GW) (LDS), else a.colsum_gw
                                            float* lds_tab = nullptr, int lds_rows = 0, bool kl_rows = false,
                                            double* red_scratch = nullptr,   // fused half-steps: scratch of its own for the waves' sums -> ONE barrier after the per-pixel work
                                            float relw_lane = -1.f, Hook after_pixels = Hook(),
-                                           const float* unit_kl = nullptr, int n_unit_kl = 0) {   // fused half-steps (round 5): the H walk's units leave their KL sums as n_unit_kl floats in LDS instead of a row of the partials
+                                           const float* unit_kl = nullptr, int n_unit_kl = 0, const ChainStats<K>* chain = nullptr, const double* chain_scr = nullptr) {   // fused half-steps (round 5): the H walk's units leave their KL sums as n_unit_kl floats in LDS instead of a row of the partials
   constexpr int NRED = ESPM_HP_NSCALAR + 2 * K + 1;  // sums: scalars (but RELH) + K row sums; max: RELH + K row maxima + RELW
   float red[NRED];   // per-thread partials in fp32 (one or two pixels per thread); fp64 from the wave results on (block_reduce_f32)
 #pragma unroll
@@ -204,8 +208,10 @@ __device__ __forceinline__ void h_epilogue(const HStepArgs& a, float* smem, int 
     klc_first = a.ell_klc[tile0 + (int)threadIdx.x];
     klc_loaded = true;
   }
+  bool chained = false;   // (a constant outside the CHAIN instances)
+  if constexpr (CHAIN) chained = a.chain_prev != nullptr;
   float rel_shift = 0.f;
-  if (f_prev) {  // base.py:324: tol * mean(H) of the state being evaluated (global row sums)
+  if (f_prev && !chained) {  // base.py:324: tol * mean(H) of the state being evaluated (global row sums)
     double tot = 0.0;
 #pragma unroll
     for (int kk = 0; kk < K; ++kk) tot += a.hstat_in[ESPM_HS_ROWSUM + kk];
@@ -213,9 +219,28 @@ __device__ __forceinline__ void h_epilogue(const HStepArgs& a, float* smem, int 
   }
   float mhv[K];   // GLOBAL max over pixels of every row of H, updates.py:139
 #pragma unroll
-  for (int kk = 0; kk < K; ++kk) mhv[kk] = (RULE == 0 && f_lap) ? (float)a.hstat_in[ESPM_HS_MAX + kk] : 0.f;
+  for (int kk = 0; kk < K; ++kk) mhv[kk] = (RULE == 0 && f_lap && !chained) ? (float)a.hstat_in[ESPM_HS_MAX + kk] : 0.f;
+  if constexpr (CHAIN) {
+    if (chained && !chain_scr) {   // (uniform) the same two quantities from the records' reduction
+      if (f_prev) rel_shift = chain->rel_shift;
+      if (RULE == 0 && f_lap) {
+#pragma unroll
+        for (int kk = 0; kk < K; ++kk) mhv[kk] = chain->mhv[kk];
+      }
+    }
+  }
   __syncthreads();
   ESPM_PHASE_STAMP(3);
+  if constexpr (CHAIN) {
+    if (chained && chain_scr) {   // (uniform)
+      const ChainStats<K> late = chain_stats_combine<K>(a, chain_scr);
+      if (f_prev) rel_shift = late.rel_shift;
+      if (RULE == 0 && f_lap) {
+#pragma unroll
+        for (int kk = 0; kk < K; ++kk) mhv[kk] = late.mhv[kk];
+      }
+    }
+  }
 
   // ---- epilogue: one thread per pixel -------------------------------------------------------
   auto emit_ht = [&](int q, int jj, const float (&ht)[KP]) {   // the transposed copy of the new column: memory, or the W walk's LDS table
@@ -521,10 +546,20 @@ __device__ __forceinline__ void h_epilogue(const HStepArgs& a, float* smem, int 
 // NBUF: depth of the register ring of X load groups kept in flight (0 / 1: no explicit prefetch).
 // L2: the Frobenius branch (updates.py:109-118): num = GW^T X, no ratio, no loss; the epilogue takes the denominator
 // (GW^T GW) H from a.l2_m.
-template <int K, typename XT, int PX, int NW, bool LOSS, int U, int NBUF, bool L2 = false, int RULE = 0>
+// CHAIN: the chained H-only iteration (mu_h_chain.hpp) - the statistics of h_in from the previous launch's records, an extra workgroup for
+// the previous step's history row.
+template <int K, typename XT, int PX, int NW, bool LOSS, int U, int NBUF, bool L2 = false, int RULE = 0, bool CHAIN = false>
 __global__ __launch_bounds__(NW * 64, (K > 12 && NW == 4) ? 2 : 1) void h_step_kernel(const HStepArgs a) {   // (k > 12: two workgroups per CU, <= 256 registers)
   extern __shared__ __attribute__((aligned(16))) float smem[];  // [NW][K][TP]
   constexpr int TP = 64 * PX;
+  ChainStats<K> chain{};
+  if constexpr (CHAIN) {
+    if (a.chain_fin_on && blockIdx.x == gridDim.x - 1) {   // (uniform) the extra workgroup
+      chain_finalize_wg(a.chain_fin, reinterpret_cast<double*>(smem));
+      return;
+    }
+    if (a.chain_prev) chain = chain_stats<K>(a, reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(smem) + a.chain_lds_off));
+  }
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int tile0 = blockIdx.x * TP;
@@ -675,7 +710,10 @@ __global__ __launch_bounds__(NW * 64, (K > 12 && NW == 4) ? 2 : 1) void h_step_k
 #pragma unroll
     for (int i = 0; i < P2; ++i) kl_lane += kl[i].x + kl[i].y;
   }
-  h_epilogue<K, true, RULE>(a, smem, NW, TP, tile0, kl_lane);
+  if constexpr (CHAIN)
+    h_epilogue<K, true, RULE, 0, false, HEpiNoHook, true>(a, smem, NW, TP, tile0, kl_lane, nullptr, nullptr, 0, false, nullptr, -1.f, HEpiNoHook(), nullptr, 0, &chain);
+  else
+    h_epilogue<K, true, RULE>(a, smem, NW, TP, tile0, kl_lane);
 }
 
 }  // namespace espm

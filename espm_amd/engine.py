@@ -429,6 +429,7 @@ class MUEngine:
         self.colsum_gw = torch.zeros(self.V.KP, **f64)
         nblk_h = (self.p + st.tile_px - 1) // st.tile_px
         self.hpart = torch.zeros((nblk_h, self.V.HP_STRIDE), **f64)
+        self.hpart_alt = torch.zeros_like(self.hpart)   # (H-only iterations: the records alternate, include/espm_mu.h)
         self.hstat = [torch.zeros(self.V.HS_STRIDE, **f64) for _ in range(2)]
         self._tick("rest up to the state buffers")
         self.a_slab = torch.zeros((st.nblk_w, k, st.n_pad), **f32)
@@ -490,6 +491,11 @@ class MUEngine:
         else:
             st.breg_sr_px = st.breg_sr_ch = None
         st.hpart = self.hpart.data_ptr()
+        # H-only iterations run espm_mu_step_h + espm_mu_h_finalize per iteration by default: measured, the chained H-step's one launch is
+        # not faster on any store (level on the sparse store, 32 % slower on the 8-bit store at the headline image).
+        # ESPM_H_CHAIN=1 hands the library the second record buffer, i.e. selects the chained launch where it is built (A/B, tests; same
+        # bits); ESPM_H_CHAIN=0, or unset: the general path
+        st.hpart_alt = self.hpart_alt.data_ptr() if os.environ.get("ESPM_H_CHAIN", "0") == "1" else None
         st.hstat[0], st.hstat[1] = self.hstat[0].data_ptr(), self.hstat[1].data_ptr()
         st.a_slab, st.a, st.w_scratch = self.a_slab.data_ptr(), self.a.data_ptr(), self.w_scratch.data_ptr()
         st.hist, st.hist_len = self.hist.data_ptr(), self.hist_len
@@ -998,6 +1004,51 @@ class MUEngine:
                 self.finish_iteration()
             if final_loss:
                 self.eval_current(False)
+
+    # ---- H-only iterations: W held (what the reference computes with fixed_W = W, updates.py:75-76) ------------------------------
+    def _hold_w(self):
+        """Both W buffers hold the current W: st.cur flips with every H-only iteration as the index of the current H."""
+        if self.sharded or self.frobenius:
+            raise NotImplementedError("H-only iterations: one GPU, not the Frobenius fit")
+        self._flush_finalize()
+        self._accum_done = False
+        cur = self.st.cur
+        self.w[1 - cur].copy_(self.w[cur])
+
+    def h_chain_applies(self):
+        """Whether ``iterate_h`` runs one launch per iteration (include/espm_mu.h: espm_mu_h_chain_applies)."""
+        return int(self.lib.espm_mu_h_chain_applies(C.byref(self.st))) == 1
+
+    def advance_h_only(self):
+        """One H-only iteration, host-sequenced (the granular step of a stop-rule loop): the H-step from the current state and the
+        reduction of its records - history slot ``it`` gets the loss pieces of the current state - then the new H is the current one.
+        ``eval_current(advance_h=True)`` on the two-launch path, without the W step that would follow."""
+        st = self.st
+        cur, slot = st.cur, st.it
+        if slot + 1 >= self.hist_len:
+            raise ValueError("history buffer exhausted: raise max_iter")
+        self._hold_w()
+        self._check(self.lib.espm_mu_step_h(C.byref(st), cur, 1, _stream()))
+        self._check(self.lib.espm_mu_h_finalize(C.byref(st), cur, slot, _stream()))
+        self.hist[slot + 1, _lib.HI_REL_W] = 0.0   # base.py:323 of an update that leaves W alone
+        st.cur, st.it = 1 - cur, slot + 1
+
+    def retreat_h(self):
+        """Takes the last ``advance_h_only`` back: the H it started from is still in the other buffer, with its statistics."""
+        st = self.st
+        if st.it < 1:
+            raise ValueError("no H-only iteration to take back")
+        self._flush_finalize()
+        st.cur, st.it = 1 - st.cur, st.it - 1
+
+    def iterate_h(self, n_iter, final_loss=True):
+        """``n_iter`` H-only iterations without host synchronisation (``espm_mu_iterate_h``: one launch per iteration where the
+        chained H-step applies)."""
+        st = self.st
+        if st.it + int(n_iter) + 1 > self.hist_len:
+            raise ValueError("history buffer exhausted: raise max_iter")
+        self._hold_w()
+        self._check(self.lib.espm_mu_iterate_h(C.byref(st), int(n_iter), int(bool(final_loss)), _stream()))
 
     def iterate_timed(self, n_iter):
         """``n_iter`` iterations of the library's own loop (``espm_mu_iterate``: enqueued from C, the device never waits for the

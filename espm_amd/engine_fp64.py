@@ -344,4 +344,4 @@ class MUEngineF64(MUEngine):
         raise NotImplementedError("fp64 mode: not available (single-GPU log_surrogate updates only)")
 
     autotune_plan = settle_exchange = use_collective_exchange = linesearch_step = pg_linesearch_h = pg_linesearch_w = _unsupported
-    iterate_timed = timed_iterations = _unsupported
+    iterate_timed = timed_iterations = advance_h_only = iterate_h = _unsupported

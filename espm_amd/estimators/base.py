@@ -15,6 +15,7 @@ from abc import ABC, abstractmethod
 
 import numpy as np
 from sklearn.base import BaseEstimator, TransformerMixin
+from sklearn.utils.metaestimators import available_if
 from sklearn.utils.validation import check_is_fitted, validate_data
 
 from espm_amd.conf import log_shift
@@ -306,7 +307,29 @@ class _Shard:
         return np.concatenate([part[:, :c].cpu().numpy() for part, c in zip(parts, self.counts)], axis=1)
 
 
-class NMFEstimator(ABC, TransformerMixin, BaseEstimator):
+def _rows_are_pixels(est):
+    return bool(est.hspy_comp)
+
+
+class _PixelTransform:
+    """``transform`` of an estimator whose rows are pixels (``hspy_comp=True``: X is (pixels, channels), what hyperspy's decomposition
+    hands over and what its contract - "fit() and transform()" - asks for).  There scikit-learn's meaning of ``transform`` and the H-only
+    fit coincide: samples in, one row of abundances per sample out, ``fit_transform`` returning the same kind of array (H.T).  With
+    ``hspy_comp=False`` the rows of X are channels and ``fit_transform`` returns G W, one row per CHANNEL: a ``transform`` that
+    returned H there would break scikit-learn's transformer contract (``transform(X)`` ~ ``fit_transform(X)``, same number of rows,
+    the column count of ``fit`` enforced - the pixel count, which new data need not share), so the method is not available there
+    (``hasattr`` is False, scikit-learn's ``available_if``) and the same computation is ``unmix``.
+
+    A mixin of its own, ahead of TransformerMixin: that class wraps the ``transform`` it finds in a subclass's own namespace for
+    ``set_output``, which would replace the conditional descriptor with a plain function."""
+
+    @available_if(_rows_are_pixels)
+    def transform(self, X, H=None, shape_2d=None):
+        """``unmix(X, H, shape_2d)`` for X (pixels, channels): returns H.T, (pixels, components), as ``fit_transform`` does."""
+        return self.unmix(X, H=H, shape_2d=shape_2d)
+
+
+class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
     """Abstract NMF estimator, X (n, p) ~ G (n, m) W (m, k) H (k, p); parameters and attributes as in
     espm/estimators/base.py:68-152."""
 
@@ -959,6 +982,204 @@ class NMFEstimator(ABC, TransformerMixin, BaseEstimator):
         shard() and more than 8 components raise NotImplementedError before X is uploaded."""
         self.fit_transform(X, **params)
         return self
+
+    # ---- transform: H of new data against the fitted W (an H-only fit) ---------------------------------------------------------
+    def _transform_refusal(self):
+        """Why ``transform`` cannot serve this estimator, or None."""
+        if self._fp64():
+            return "fp64 mode (set_precision('fp64')): its engine has no H-only iteration"
+        if getattr(self, "linesearch", False):
+            return "linesearch=True (gamma_ would have to adapt as in the fit)"
+        if getattr(self, "algo", "log_surrogate") == "projected_gradient":
+            return "algo='projected_gradient'"
+        if self.l2:
+            return "l2=True (the Frobenius fit)"
+        if getattr(self, "_shard_group", None) is not None:
+            return "an estimator that was shard()ed (transform runs on one GPU)"
+        return None
+
+    def unmix(self, X, H=None, shape_2d=None):
+        """H of new data ``X`` against the fitted spectra (``transform`` is this method where the estimator is a scikit-learn transformer
+        of pixels, ``hspy_comp=True``: see ``_PixelTransform``): what the reference computes with the same parameters, ``normalize=False``,
+        ``fixed_W=Wf`` and ``fit_transform(Xs, W=Wf, H=H0)`` (base.py:293-420 with updates.py:75-76 overwriting every entry of W) -
+        the H rule every iteration, rel_W = 0, the reference's stop rules and loss.  ``Wf``, ``Xs`` are ``W_`` and ``X``, both times
+        the fit's ``norm_factor_`` under ``normalize`` (the factor is not recomputed: the objective is the one the fit minimised);
+        G is the fitted ``G_`` (a physics model is not refreshed: W does not move).  ``H=None``: |lstsq(G W, X)|, normalised under
+        ``simplex_H``, floored at ``log_shift`` (updates.py:213-221).  ``shape_2d``: the grid of ``X``'s pixels, by default the
+        estimator's when the pixel count matches; the estimator's ``fixed_H`` belongs to the fitted image and is not applied.
+
+        X is (channels, pixels), or (pixels, channels) with ``hspy_comp`` - then H.T is returned, as by ``fit_transform``.  The fitted
+        attributes stay as they are; the run's own record goes to ``transform_n_iter_``, ``transform_losses_`` and ``transform_rel_``
+        (rel_H of every iteration).  Built from the fit's stages with a context of its own; the stop-rule loop is ``_fit_loop``'s
+        without the W step.  NotImplementedError, before anything is uploaded: linesearch, algo='projected_gradient', l2=True,
+        shard(), fp64 mode."""
+        import types
+        check_is_fitted(self, "W_")
+        why = self._transform_refusal()
+        if why is not None:
+            raise NotImplementedError(f"transform / unmix does not cover {why}")
+        t = types.SimpleNamespace()
+        self._transform_validate(t, X, shape_2d)
+        self._transform_ingest(t)
+        eng = self._transform_engine(t, H)
+        self._transform_loop(t, eng)
+        Hn = eng.get_H().astype(t.out_dtype)
+        if not self.simplex_H and not self.simplex_W:   # base.py:399-400
+            Hn = rescaled_DH(t.Wf.astype(t.out_dtype), Hn)[1]
+        return Hn.T if self.hspy_comp else Hn
+
+    def _transform_validate(self, t, X, shape_2d):
+        """scikit-learn's validation against the fitted channel count (reset=False), the grid of the new pixels."""
+        big = False
+        try:
+            import torch
+            big = (hasattr(X, "shape") and getattr(X, "ndim", 0) == 2 and int(np.prod(X.shape)) >= _DEVICE_PREP_MIN_SIZE
+                   and getattr(X, "dtype", None) in (np.float32, np.float64) and torch.cuda.is_available())
+        except Exception:
+            big = False
+        # (scikit-learn counts the PIXELS as features here, base.py:243-247: the new data may have another number of them, so the
+        #  array is checked as in the fit but not against n_features_in_)
+        from sklearn.utils.validation import check_array
+        vkw = dict(dtype=[np.float64, np.float32])
+        if big:
+            vkw["ensure_all_finite"] = False
+        Xv = check_array(X.T if self.hspy_comp else X, **vkw)
+        if Xv.shape[0] != self.G_.shape[0]:
+            raise ValueError(f"X has {Xv.shape[0]} channels, the fitted G_ has {self.G_.shape[0]}")
+        p = int(Xv.shape[1])
+        if shape_2d is None and self.shape_2d is not None and int(self.shape_2d[0]) * int(self.shape_2d[1]) == p:
+            shape_2d = self.shape_2d
+        if shape_2d is not None and int(shape_2d[0]) * int(shape_2d[1]) != p:
+            raise ValueError(f"shape_2d {tuple(shape_2d)} does not match the {p} pixels of X")
+        if shape_2d is None and getattr(self, "lambda_L", 0) != 0:
+            raise ValueError(f"lambda_L != 0 needs the grid of the {p} pixels of X: pass shape_2d (the estimator's is {self.shape_2d})")
+        t.Xv, t.big, t.shape_2d = Xv, big, shape_2d
+
+    def _transform_ingest(self, t):
+        """_fit_ingest for data that is not kept: sign check and empty lines (base.py:519-528) on the host, or for a large X on its ONE
+        device copy by the upload's scans; the fit's norm_factor_."""
+        Xv = t.Xv
+        t.xscale = float(self.norm_factor_) if self.normalize else 1.0
+        t.Xd_raw, t.x_facts, t.layout = None, None, "cm"
+        if t.big:
+            import torch
+            if Xv.flags.c_contiguous:
+                host = Xv
+            elif Xv.T.flags.c_contiguous:
+                host, t.layout = Xv.T, "pm"
+            else:
+                host = np.ascontiguousarray(Xv)
+            Xd_raw, scans = _upload_with_scans(host, torch.device("cuda", torch.cuda.current_device()), self.log_shift)
+            n_bad, n_nan, n_neg = (int(v) for v in scans["bad"].cpu())
+            if n_bad:
+                raise ValueError(f"Input X contains {'NaN' if n_nan else 'infinity'}.")
+            if n_neg:
+                raise ValueError("Negative values in data")
+            zc, zp = ((scans["row_sum"] == 0, scans["col_sum"] == 0) if t.layout == "cm" else (scans["col_sum"] == 0, scans["row_sum"] == 0))
+            Xd = Xd_raw if t.layout == "cm" else Xd_raw.t()
+            s1, n_nonint, nnz, x_max = (float(v) for v in torch.cat((scans["s1"].view(1), scans["facts"])).cpu())
+            t.empty_ch, t.empty_px = zc, zp
+            if bool(zc.any()) or bool(zp.any()):
+                Xd[:, zp] = self.log_shift
+                Xd[zc, :] = self.log_shift
+            else:
+                t.x_facts = XFacts(nonneg=True, sum_x=s1, is_int=bool(n_nonint == 0), x_max=x_max, nnz=int(nnz))
+            t.Xd_raw, t.X_fixed = Xd_raw, None
+        else:
+            t.X_fixed = self.remove_zeros_lines(Xv, self.log_shift)   # (ValueError on negative values)
+            t.empty_ch, t.empty_px = Xv.sum(axis=1) == 0, Xv.sum(axis=0) == 0
+
+    def _transform_engine(self, t, H):
+        """The engine of the new data - the fit's parameters, the new grid, no fixed_H, W held - with (Wf, H0) loaded.  Not cached."""
+        from espm_amd.engine import MUEngine
+        k = self.n_components
+        t.out_dtype = t.Xv.dtype
+        Wf = np.maximum(np.asarray(self.W_, dtype=np.float64) * t.xscale, self.log_shift)   # (W_ is stored un-normalised, base.py:417-418)
+        t.Wf = Wf
+        G = None if self._identity_G else self.G_
+        if H is None:   # updates.py:213-221
+            GW = Wf if G is None else np.asarray(G, dtype=np.float64) @ Wf
+            if t.Xd_raw is not None:
+                import torch
+                Xd = t.Xd_raw if t.layout == "cm" else t.Xd_raw.t()
+                gw = torch.from_numpy(GW).to(Xd.device)
+                H0 = (torch.linalg.pinv(gw) @ (Xd.to(torch.float64) * t.xscale)).abs().cpu().numpy()
+            else:
+                H0 = np.abs(np.linalg.lstsq(GW, np.asarray(t.X_fixed, dtype=np.float64) * t.xscale, rcond=None)[0])
+            if self.simplex_H:
+                H0 = H0 / H0.sum(axis=0, keepdims=True)
+        else:
+            H0 = np.asarray(H.T if self.hspy_comp else H, dtype=np.float64)
+            if H0.shape != (k, t.Xv.shape[1]):
+                raise ValueError(f"H must be {(k, t.Xv.shape[1])}, got {H0.shape}")
+        H0 = np.maximum(H0, self.log_shift)
+        any_ch = bool(t.empty_ch.any())
+        any_px = bool(t.empty_px.any())
+        kw = dict(self._engine_kwargs())
+        kw.pop("frobenius", None)
+        kw.pop("pg_gamma_w", None)
+        eng = MUEngine(t.X_fixed if t.Xd_raw is None else t.Xd_raw, k, G=G, shape_2d=t.shape_2d, simplex_H=self.simplex_H,
+                       simplex_W=False, log_shift=self.log_shift, tol=self.tol, fixed_H=None, fixed_W=None, xscale=t.xscale,
+                       max_iter=self.max_iter, fix_zero_lines=False, filled_channels=t.empty_ch if any_ch or any_px else None,
+                       filled_pixels=t.empty_px if any_ch or any_px else None, layout=t.layout, autotune=False, x_facts=t.x_facts, **kw)
+        t.Xd_raw = t.X_fixed = None
+        eng.load_state(Wf, H0)
+        # which store the new data went on and whether its iteration is one launch (include/espm_mu.h: espm_mu_h_chain_applies)
+        self.transform_path_ = dict(x_store=eng.x_store, n_heavy=int(eng.n_heavy), h_chain=int(eng.h_chain_applies()))
+        return eng
+
+    def _transform_loop(self, t, eng):
+        """_fit_loop's logic (base.py:313-394) without the W step, truth tracking or G refresh: rel_W = 0."""
+        say = print if self.verbose else (lambda *a, **k: None)
+        self.transform_n_iter_ = 0
+        self.transform_losses_, self.transform_rel_ = [], []
+        n, eval_before, eval_init = 0, np.inf, None
+        if self.no_stop_criterion and not self.verbose:
+            eng.iterate_h(self.max_iter, final_loss=True)
+            n = self.max_iter
+            h = eng.history(upto=n)
+            self.transform_losses_ = [float(v) for v in h["loss"][1:n + 1]]
+            self.transform_rel_ = [float(v) for v in h["rel_H"][1:n + 1]]
+            self.transform_n_iter_ = n
+            return
+        eng.advance_h_only()   # the loss of the initial state rides on the first H-step
+        while True:
+            n += 1             # state n is the current one; the H-step FROM it evaluates it (and proposes state n + 1)
+            last = n >= self.max_iter
+            if last:
+                eng.eval_current(advance_h=False)
+            else:
+                eng.advance_h_only()
+            h = eng.history(upto=n)
+            if eval_init is None:
+                eval_init = float(h["loss"][0])
+            eval_after, rel_H = float(h["loss"][n]), float(h["rel_H"][n])
+            self.transform_losses_.append(eval_after)
+            self.transform_rel_.append(rel_H)
+            self.transform_n_iter_ = n
+            stop = False
+            if last:
+                say("exits because max_iteration was reached")
+                break
+            if not self.no_stop_criterion:
+                if rel_H < self.tol:   # (max(rel_H, rel_W) with rel_W = 0)
+                    say("exits because of relative change rel_A {} and rel_P {} < tol ".format(rel_H, 0.0))
+                    stop = True
+                elif abs((eval_before - eval_after) / eval_init) < self.tol:
+                    say("exits because of relative change < tol: {}".format((eval_before - eval_after) / eval_init))
+                    stop = True
+                elif np.isnan(eval_after):
+                    say("exit because of the presence of NaN")
+                    stop = True
+                elif (eval_before - eval_after) < 0:
+                    say("exit because of negative decrease {}: {}, {}".format((eval_before - eval_after), eval_before, eval_after))
+                    stop = True
+            if stop:
+                eng.retreat_h()   # (state n + 1 was proposed, state n is the result)
+                break
+            if self.verbose > 0 and np.mod(n, self.eval_print) == 0:
+                say(f"It {n} / {self.max_iter}: loss {eval_after:3e}")
+            eval_before = eval_after
 
     def inverse_transform(self, W):
         """G W H_ (espm/estimators/base.py:461-477)."""

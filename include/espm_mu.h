@@ -158,7 +158,7 @@ enum { ESPM_LAYOUT_CM = 0 /* (n, p) channel-major */, ESPM_LAYOUT_PM = 1 /* (p, 
  * point that takes a state checks st->struct_size == sizeof(espm_mu_state) and st->abi_version == ESPM_MU_ABI_VERSION
  * first and fails with ESPM_EINVAL otherwise: a binding whose copy of the layout has drifted is refused instead of
  * having its pointers misread.  A binding can also compare its layout field by field with espm_mu_state_layout(). */
-#define ESPM_MU_ABI_VERSION 5
+#define ESPM_MU_ABI_VERSION 6
 
 typedef struct espm_mu_state {
   uint32_t struct_size;   /* sizeof(espm_mu_state) as the CALLER sees it                  */
@@ -325,6 +325,10 @@ typedef struct espm_mu_state {
   const int32_t* ell_hv_grp;     /* (ell_hv_ngrp) channel of each group                     */
   const int32_t* ell_hv_grp_off; /* (ell_hv_ngrp + 1)                                       */
   const int32_t* ell_hv_wm;      /* (ell_hv_n, 2) {pixel, count}, by (W block, channel)     */
+  /* H-only iterations (espm_mu_iterate_h): a second record buffer of hpart's size.  Consecutive H-steps then write their records to
+   * hpart and hpart_alt in turn, and each reduces what it needs of its predecessor's records itself: one launch per iteration
+   * (espm_mu_h_chain_applies).  NULL: espm_mu_iterate_h runs espm_mu_step_h + espm_mu_h_finalize per iteration.  Nothing else reads it. */
+  double* hpart_alt;
 } espm_mu_state;
 
 const char* espm_mu_version(void);
@@ -435,6 +439,21 @@ int espm_mu_w_reduce_finish(const espm_mu_state* st, int src, int slot, int with
  * changes of the update that produced it.  A final loss-only H-step fills the last slot when
  * final_loss != 0. */
 int espm_mu_iterate(espm_mu_state* st, int n_iter, int final_loss, espm_stream_t stream);
+/* n_iter H-only iterations (W held: what the reference computes with fixed_W = W, updates.py:75-76 - the H rule every iteration,
+ * rel_W = 0): w[], gw_s and colsum_gw are not touched; st->cur flips with every iteration as the index of the current H only - W
+ * stays in the buffer it was in (a caller that reads w[st->cur] afterwards keeps the same W in both) - and st->it advances.  No host
+ * synchronisation.
+ * History slot t gets the loss pieces of state t and rel_H of the update that produced it; rel_W of the slots it + 1 .. it + n_iter
+ * is written as 0.  A final loss-only H-step fills the last slot when final_loss != 0.  Never the fused launch of espm_mu_step_hw.
+ * Where espm_mu_h_chain_applies(st) an iteration is ONE launch: the H-step reduces the row sums and maxima it needs from its
+ * predecessor's records itself (the records alternate between hpart and hpart_alt) and an extra workgroup writes the predecessor's
+ * history row and hstat; one espm_mu_h_finalize closes the batch.  Otherwise espm_mu_step_h + espm_mu_h_finalize per iteration.  Same
+ * bits either way.
+ * espm_mu_h_chain_applies: 1 for the default H rule (h_rule = 0, no Bregman variant) with compute_loss and hpart_alt set, on the sparse
+ * store without heavy elements (1..16 components) and on the 8-bit, bf16 and fp32 stores up to 12 components; else 0
+ * (a negative espm_status for a state the library refuses). */
+int espm_mu_iterate_h(espm_mu_state* st, int n_iter, int final_loss, espm_stream_t stream);
+int espm_mu_h_chain_applies(const espm_mu_state* st);
 /* 1 when the W update needs nothing global (G = identity, no simplex over W, ...): the slab / record reduction updates W
  * itself and a tail workgroup finishes (tail_mode above); 0: espm_mu_w_finish does the update, there is no tail. */
 int espm_mu_w_update_is_local(const espm_mu_state* st);
