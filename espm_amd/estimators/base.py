@@ -1181,6 +1181,55 @@ class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
                 say(f"It {n} / {self.max_iter}: loss {eval_after:3e}")
             eval_before = eval_after
 
+    # ---- diagnostics of the fit: where it fails, and an error bar on every abundance ---------------------------------------------
+    def pixel_diagnostics(self, X=None):
+        """Per-pixel deviance and error bars of ``H_`` (``espm_amd.measures.pixel_diagnostics`` on ``G_ @ W_`` and ``H_``; the reference
+        has no analogue - hyperspy's model fitting reports the same two things as ``red_chisq`` and the parameters' ``std``).
+
+        Sets ``deviance_`` (p,): the Poisson deviance 2 sum_c (x ln(x / y) - x + y) of every pixel, and ``H_std_`` (k, p), oriented as
+        ``H_``: the Cramer-Rao bound of every abundance given the fitted spectra, under the constraint sum_i h_i = 1 when the estimator
+        has ``simplex_H``.  Pixels whose Fisher information is numerically singular hold NaN in ``H_std_`` and are counted in
+        ``n_singular``.  The bound ignores the uncertainty of ``W_``, the regularisers (``mu``, ``lambda_L``) and abundances held at
+        the ``log_shift`` floor: it is the error bar given the spectra.  Returns dict(deviance, H_std, n_singular); with ``hspy_comp``
+        the returned ``H_std`` is (p, k), as ``fit_transform`` returns ``H_.T``.
+
+        ``X``: the fitted image in counts - (channels, pixels), or (pixels, channels) with ``hspy_comp``, as for ``unmix`` - in any
+        dtype ``measures.pixel_diagnostics`` reads; ValueError when its channels do not match ``G_`` or its pixels ``H_``.
+        ``X=None`` takes the fit's ``X_`` un-scaled (``X_ / norm_factor_`` under ``normalize``); lines of the image without a count
+        carry the ``log_shift`` fill there, so passing the original X is the exact one.  It is also the cheap one: under ``normalize``
+        ``X=None`` builds the un-scaled image as a host array in ``X_``'s dtype and uploads it as such - for a fit of 8- or 16-bit
+        counts that is 4 or 8 bytes per entry on the host and again on the device (4.3 GB each at 2048 x 512 x 512 in fp64) against 1
+        or 2 for the original counts, so at large sizes pass the X that was fitted.  Computed in fp64 whatever the estimator's
+        precision, on the current device (a ``shard()``ed estimator: every rank holds the whole ``W_`` and ``H_`` and computes all
+        pixels on its own device).  More than 8 components raise NotImplementedError before anything is uploaded."""
+        from espm_amd import measures
+        check_is_fitted(self, "W_")
+        k = int(self.H_.shape[0])
+        if k > 8:
+            raise NotImplementedError(f"pixel_diagnostics: {k} components (the kernel is built for 1..8)")
+        layout = "cm"
+        if X is None:
+            check_is_fitted(self, "X_")
+            X = np.asarray(self._X_fixed())
+        else:
+            if not hasattr(X, "shape") or getattr(X, "ndim", 0) != 2:
+                X = np.asarray(X)
+            if X.ndim != 2:
+                raise ValueError("X must be 2-D")
+            layout = "pm" if self.hspy_comp else "cm"
+            n, p = (X.shape[1], X.shape[0]) if self.hspy_comp else (X.shape[0], X.shape[1])
+            if n != self.G_.shape[0]:
+                raise ValueError(f"X has {n} channels, the fitted G_ has {self.G_.shape[0]}")
+            if p != self.H_.shape[1]:
+                raise ValueError(f"X has {p} pixels, the fitted H_ has {self.H_.shape[1]}")
+        D = np.asarray(self.W_ if self._identity_G else self.G_ @ self.W_, dtype=np.float64)
+        out = measures.pixel_diagnostics(X, D, np.asarray(self.H_, dtype=np.float64), simplex_H=bool(self.simplex_H),
+                                         log_shift=self.log_shift, layout=layout)
+        self.deviance_, self.H_std_ = out["deviance"], out["H_std"]
+        if self.hspy_comp:
+            out = dict(out, H_std=out["H_std"].T)
+        return out
+
     def inverse_transform(self, W):
         """G W H_ (espm/estimators/base.py:461-477)."""
         check_is_fitted(self)

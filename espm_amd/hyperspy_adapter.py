@@ -94,6 +94,19 @@ class SpectrumImage:
         """(k, n) spectra."""
         return self.learning_results.factors.T
 
+    def get_decomposition_diagnostics(self):
+        """(deviance (ny, nx), H_std (k, ny, nx)) of the kept estimator, after its ``pixel_diagnostics()``."""
+        return diagnostic_maps(self.learning_results.decomposition_algorithm, self.shape_2d)
+
+
+def diagnostic_maps(est, shape_2d=None):
+    """``est.deviance_`` and ``est.H_std_`` (set by ``est.pixel_diagnostics()``) in the navigation shape, like the loadings:
+    (ny, nx) and (k, ny, nx).  ``shape_2d``: the image grid, by default the estimator's."""
+    if not hasattr(est, "deviance_"):
+        raise AttributeError("call est.pixel_diagnostics() first: it sets deviance_ and H_std_")
+    ny, nx = (int(v) for v in (shape_2d if shape_2d is not None else est.shape_2d))
+    return np.asarray(est.deviance_).reshape((ny, nx)), np.asarray(est.H_std_).reshape((-1, ny, nx))
+
 
 def register():
     """``espm.estimators.NMFEstimator.register(espm_amd.estimators.NMFEstimator)`` where espm is importable: the reference's

@@ -41,6 +41,8 @@
  *                            + smooth_nmf.py:382-401, :438-447 (its linesearch)
  *   espm_dichotomy_simplex_acc / _pg <- dicotomy.py:57-108 (module-level functions)
  *   espm_surrogate_terms  <- espm/estimators/surrogates.py:6-149 (module-level surrogates)
+ *   espm_pixel_diagnostics<- (new) per-pixel Poisson deviance and Cramer-Rao bound of H given the spectra; no reference analogue
+ *                            (hyperspy's model fitting reports them as red_chisq and the parameters' std)
  *   espm_lu_pl            <- espm/estimators/updates.py:179 -> scikit-learn's _initialize_nmf -> _randomized_range_finder: the LU
  *                            normaliser of its power iterations (scipy.linalg.lu(A, permute_l=True)[0]) on tall device matrices
  *
@@ -689,6 +691,29 @@ int espm_f64_sparse_h_pass(const uint32_t* h_elem, const int64_t* h_off, const i
 int espm_f64_sparse_w_accum(const uint32_t* w_elem, const int64_t* w_off, const uint8_t* ec_flag, const int32_t* ep, const int32_t* ep_off,
                             int n, int p, double xscale, const double* gw, const double* h, int k, double log_shift, double* scratch,
                             double* rh, espm_stream_t stream);
+
+/* ---- pixel diagnostics (csrc/mu_diag.hip; espm_amd.measures.pixel_diagnostics, NMFEstimator.pixel_diagnostics) ---------------
+ * Where a fitted model fails and how well every abundance is known, in one fp64 pass over X.  Plain device pointers, no
+ * espm_mu_state.  x: the image as it was measured, dtype ESPM_DIAG_X_*, (n, p) for x_layout ESPM_LAYOUT_CM or (p, n) for
+ * ESPM_LAYOUT_PM, leading dimension ld (elements).  d (n, k) row-major: the spectra G W in counts; h (k, p).
+ * With Y = max(d h, log_shift), per pixel j:
+ *   dev[j]       = 2 sum_c (x ln(x / y) - x + y), the first term 0 where x == 0: the Poisson (KL) deviance
+ *   F_j          = d^T diag(1 / y[:, j]) d, the expected Fisher information of h[:, j] with the spectra held
+ *   h_std[:, j]  = sqrt(diag(C_j)), C = F^-1, or with simplex != 0 the bound under sum_i h_i = 1:
+ *                  C = F^-1 - F^-1 1 1^T F^-1 / (1^T F^-1 1) (exactly 0 for k = 1)
+ * F_j is factorised by the root-free Cholesky F = L diag(piv) L^T; a pivot that is not above k * 2^-52 * max diag(F_j) makes that
+ * pixel's column of h_std NaN and counts in *n_singular (may be NULL; zeroed by the call) - no error.  dev (p), h_std (k, p).
+ * k = 1..ESPM_DIAG_MAX_K; one launch on `stream`, nothing but that integer count is accumulated atomically.  Only the narrow
+ * build has the kernels; the wide builds return ESPM_EUNSUPPORTED. */
+#define ESPM_DIAG_MAX_K 8
+#define ESPM_DIAG_BLOCK 256    /* pixels (threads) per workgroup                                                              */
+#define ESPM_DIAG_CHUNK 256    /* channels of d staged in LDS per round (k = 8: 16 KB)                                        */
+#define ESPM_DIAG_X_U8 0
+#define ESPM_DIAG_X_U16 1
+#define ESPM_DIAG_X_F32 2
+#define ESPM_DIAG_X_F64 3
+int espm_pixel_diagnostics(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, const double* d, const double* h, int k,
+                           double log_shift, int simplex, double* dev, double* h_std, int32_t* n_singular, espm_stream_t stream);
 
 #ifdef __cplusplus
 }
