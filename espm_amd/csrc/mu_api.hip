@@ -307,7 +307,7 @@ static bool w_update_is_local(const espm_mu_state* st) {
 }
 // The simplex over W with G = identity and every row in the simplex: the multipliers follow from per-component sums over the
 // channels, so the update runs as two many-workgroup launches (slab reduction + those sums, then w_simplex_update_kernel)
-// instead of the reduction and ONE workgroup that finds the multipliers (mu_w_step.hip).  Its tail is the local update's.
+// instead of the reduction and ONE workgroup that finds the multipliers (mu_w_reduce.hip against mu_w_finish.hip).  Its tail is the local update's.
 static bool w_simplex_split(const espm_mu_state* st) {
   return st->m == 0 && st->simplex_w && !st->simplex_rows && !st->breg_sr_ch && !(st->pg_gamma_w > 0.f) && st->n >= 64 &&
          st->w_scratch != nullptr && st->n_pad % 32 == 0 && st->no_fused != 1;

@@ -390,7 +390,7 @@ __global__ __launch_bounds__(256) void shard_pack_kernel(const float* __restrict
 }
 
 // Fixed-order sum over ranks (bit-identical on every rank), global row sums / maxima.
-// With bparts (the simplex over W with G = identity, mu_w_step.hip: w_simplex_update_kernel; n_pad a multiple of 32): every
+// With bparts (the simplex over W with G = identity, mu_w_reduce.hip: w_simplex_update_kernel; n_pad a multiple of 32): every
 // half wave also leaves sum, maximum and count of the positive numerators W A of its 32 entries in bparts[3 * (entry / 32) ..],
 // as w_reduce_kernel does for one GPU.
 __global__ __launch_bounds__(256) void shard_combine_kernel(const unsigned char* __restrict__ recs, int world,

@@ -637,7 +637,7 @@ __device__ __forceinline__ float stencil_hl(const float* hrow, const float* halo
   return (float)deg * hc - acc;
 }
 
-// kernel-side argument blocks and launchers (mu_h_step.hip, mu_w_step.hip, mu_aux.hip)
+// kernel-side argument blocks and launchers (mu_h_step.hip, the mu_w_*.hip units, mu_aux.hip)
 struct HFinalizeArgs {
   const double* hpart;
   const double* colsum_gw;
@@ -999,7 +999,7 @@ int launch_w_update_tail(const WTailArgs& t, hipStream_t stream);
 int launch_w_exchange_update(const WFinishArgs& f, const void* slabs, size_t slab_stride, int nslab, float* a_out, double* hstat_out,
                              const HFinalizeArgs& fin, const struct ::espm_xchg* xc, unsigned int seq, const float* h_new, int nx, int ny,
                              int p_pad, int with_halo, hipStream_t stream, WTailArgs* defer_tail, double* simplex_bparts = nullptr);
-bool w_gsplit_applies(const WFinishArgs& args);   // the W finish with a dictionary G as many-workgroup launches (mu_w_step.hip)
+bool w_gsplit_applies(const WFinishArgs& args);   // the W finish with a dictionary G as many-workgroup launches (mu_w_dict.hip)
 int launch_w_gxchg_update(const WFinishArgs& f, const struct ::espm_xchg* xc, unsigned int seq, const double* hstat_local, double* hstat_out,
                           const float* h_new, int nx, int ny, int p_pad, int with_halo, hipStream_t stream);
 WTailArgs make_w_tail_args(const WFinishArgs& f);

@@ -4,7 +4,7 @@
 // R H'^T are sums over pixels), so the workgroup that has just updated the 1024 pixels of a block can go on and walk the
 // block's channel lists without waiting for anybody else: no grid-wide dependency sits between the two half-steps.
 // What IS global - the row sums of H' in the denominator of W', the sum of the slabs - stays in the reduction launch
-// that follows (w_reduce_update_kernel / w_reduce_kernel, mu_w_step.hip).
+// that follows (w_reduce_update_kernel / w_reduce_kernel, mu_w_reduce.hip).
 //
 //   workgroup = 16 waves = one block of ESPM_ELL_PB = 1024 pixels = two H tiles of 512 pixels (16 pixel-list groups);
 //   images that do not fill the chip with such blocks (and the shards of a sharded image) have blocks of ell_pb = 128 .. 512

@@ -1,4 +1,4 @@
-// The W accumulation kernel template (see mu_w_step.hip); in a header for the tuning harness.
+// The W accumulation kernel template (see mu_w_accum.hip); in a header for the tuning harness.
 #pragma once
 #include "mu_common.hpp"
 

@@ -36,7 +36,7 @@
 //   after its flag shows as `corrupt`) runs under BOTH orders on whatever peers a run has, and ESPM_XCHG_ORDER=release /
 //   espm_xchg_set_order(x, 1) replaces step (4) by a release store at system scope (the compiler's recipe: write back the L2,
 //   wait, store) for a node on which the relaxed form shows a single corrupt record.
-//   (espm_mu_shard_exchange_finish, mu_w_step.hip, does all of this INSIDE the slab-reduction launch, piece by piece, with
+//   (espm_mu_shard_exchange_finish, mu_w_exchange.hip, does all of this INSIDE the slab-reduction launch, piece by piece, with
 //    one flag per reduction workgroup: wgflags)
 //   wait(seq): one workgroup, lane r polls flag[r] (system-scope loads, s_sleep between polls) until it reaches seq or
 //              ~2 s have passed; the kernels that read the records are launched behind it on the same stream.

@@ -515,7 +515,7 @@ int espm_xchg_destroy(espm_xchg* x);
  * own (value and "it is there" in one store); afterwards the records of espm_xchg_records(x, seq & 1) hold what the NEXT
  * launch reads in place - the neighbours' boundary rows (and this rank's own statistics) - not the pieces of A, which went
  * straight into st->a.  The grid need not be resident at once: workgroups are dispatched in index order, each posts before it
- * waits, and waits only for the workgroup of its own index on the other ranks (csrc/mu_w_step.hip). */
+ * waits, and waits only for the workgroup of its own index on the other ranks (csrc/mu_w_exchange.hip). */
 int espm_mu_shard_exchange_finish(const espm_mu_state* st, espm_xchg* x, uint32_t seq, int src, int slot, espm_stream_t stream);
 
 /* espm_mu_iterate with HIP events on the launch stream around the launches of every iteration (diagnostics: bench.py's roofline line).

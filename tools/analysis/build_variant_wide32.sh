@@ -1,7 +1,7 @@
 #!/bin/bash
 # A variant of the 17..32-component library (libespm_mu_wide32.so) that differs from the product's in a few translation units: those are
 # compiled with extra flags (mu_h_step in its four parts), the rest are the product's own objects (espm_amd/lib/wide32_*.o).
-#   bash tools/analysis/build_variant_wide32.sh ct8 "-DESPM_MF_CT32=8" mu_w_step
+#   bash tools/analysis/build_variant_wide32.sh ct8 "-DESPM_MF_CT32=8" mu_w_accum
 # -> tools/analysis/libespm_mu_wide32_<name>.so, selected with ESPM_MU_WIDEST_LIB=<path>.  Not the product.
 set -e
 NAME=$1; FLAGS=$2; shift 2

@@ -9,7 +9,7 @@ R=$(cd "$(dirname "$0")/../.." && pwd)
 O=${TMPDIR:-/tmp}/espm_resource_audit; mkdir -p $O
 OUT=${1:-$R/profiles/resource_audit.txt}
 run() { /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c -I $R/include $2 $R/espm_amd/csrc/$1.hip -o $O/$3.o -Rpass-analysis=kernel-resource-usage 2> $O/$3.txt; }
-run mu_w_step "" w & run mu_aux "" aux & run mu_ell "" ell & run mu_fused "" fused & run mu_fused_plain "" plain & run mu_fused_stream "" stream & run mu_l2 "" l2 &
+run mu_w_accum "" w_accum & run mu_w_reduce "" w_reduce & run mu_w_exchange "" w_exchange & run mu_w_finish "" w_finish & run mu_w_dict "" w_dict & run mu_aux "" aux & run mu_ell "" ell & run mu_fused "" fused & run mu_fused_plain "" plain & run mu_fused_stream "" stream & run mu_l2 "" l2 &
 wait
 for i in 0 1 2 3; do run mu_h_step "-DESPM_H_PARTS=4 -DESPM_H_PART=$i" h$i & done
 run mu_ell_build "" build & run mu_init "" init & run mu_xchg "" xchg & run mu_diag "" diag &
