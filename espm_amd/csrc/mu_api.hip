@@ -133,6 +133,24 @@ static HStepArgs fused_h_args(const espm_mu_state* st, int src) {
   return a;
 }
 
+// ---- argument checks that several entry points share (callers match on the texts) ---------------------------------------------------
+// history slot `slot` exists - and, need_next, slot + 1 too, where the W update's rel_W goes
+static int check_slot(const espm_mu_state* st, int slot, bool need_next) {
+  if (slot >= 0 && slot + (need_next ? 1 : 0) < st->hist_len) return ESPM_OK;
+  return set_error(ESPM_EINVAL, need_next ? "history slot %d + 1 outside [0, %d)" : "history slot %d outside [0, %d)", slot, st->hist_len);
+}
+static int check_room(const espm_mu_state* st, int n_iter) {
+  ESPM_REQUIRE(st->it + n_iter < st->hist_len, "history too short: it=%d + %d >= %d", st->it, n_iter, st->hist_len);
+  return ESPM_OK;
+}
+// the caller's image as (dtype, layout, leading dimension); `what` names the entry point (espm_mu_pack_x words the last one without ld)
+static int check_src_view(const char* what, int dtype, int layout, int64_t ld, int n, int p, bool say_ld = true) {
+  ESPM_REQUIRE(dtype == ESPM_SRC_F32 || dtype == ESPM_SRC_F64, "%s: bad src_dtype %d", what, dtype);
+  ESPM_REQUIRE(layout == ESPM_LAYOUT_CM || layout == ESPM_LAYOUT_PM, "%s: bad layout %d", what, layout);
+  if (ld >= (layout == ESPM_LAYOUT_CM ? p : n)) return ESPM_OK;
+  return say_ld ? set_error(ESPM_EINVAL, "%s: ld=%lld too small", what, (long long)ld) : set_error(ESPM_EINVAL, "%s: leading dimension too small", what);
+}
+
 }  // namespace espm
 
 using namespace espm;
@@ -212,9 +230,7 @@ int espm_mu_pack_x(const void* src, int src_dtype, int src_layout, int64_t ld, i
   ESPM_REQUIRE(src && x_pm, "pack_x: NULL pointer");  // x_cm may be NULL (sparse store ingest needs x_pm only)
   ESPM_REQUIRE(n >= 1 && p >= 1 && n_pad == roundup(n, ESPM_NPAD) && p_pad == roundup(p, ESPM_PPAD),
                "pack_x: bad shape n=%d p=%d n_pad=%d p_pad=%d", n, p, n_pad, p_pad);
-  ESPM_REQUIRE(src_dtype == ESPM_SRC_F32 || src_dtype == ESPM_SRC_F64, "pack_x: bad src_dtype %d", src_dtype);
-  ESPM_REQUIRE(src_layout == ESPM_LAYOUT_CM || src_layout == ESPM_LAYOUT_PM, "pack_x: bad layout %d", src_layout);
-  ESPM_REQUIRE(ld >= (src_layout == ESPM_LAYOUT_CM ? p : n), "pack_x: leading dimension too small");
+  if (int rc = check_src_view("pack_x", src_dtype, src_layout, ld, n, p, false)) return rc;
   ESPM_REQUIRE(x_tile >= 64 && ESPM_PPAD % x_tile == 0, "pack_x: x_tile %d must divide %d", x_tile, ESPM_PPAD);
   ESPM_REQUIRE(n_cm == roundup(n, ESPM_NCM), "pack_x: n_cm must be roundup(n, %d)", ESPM_NCM);
   return launch_pack_x(src, src_dtype, src_layout, ld, n, p, x_cm, x_pm, x_dtype, n_pad, p_pad, x_tile, n_cm,
@@ -277,9 +293,7 @@ int espm_mu_ell_heavy_count(const espm_mu_state* st, const void* x, int src_dtyp
                             uint8_t* x_cm_u8, int32_t* cnt_px, espm_stream_t stream) {
   if (int rc = check_ell_geometry(st)) return rc;
   ESPM_REQUIRE(x && x_pm_u8 && cnt_px, "ell_heavy_count: NULL pointer");
-  ESPM_REQUIRE(src_dtype == ESPM_SRC_F32 || src_dtype == ESPM_SRC_F64, "ell_heavy_count: bad src_dtype %d", src_dtype);
-  ESPM_REQUIRE(src_layout == ESPM_LAYOUT_CM || src_layout == ESPM_LAYOUT_PM, "ell_heavy_count: bad layout %d", src_layout);
-  ESPM_REQUIRE(ld >= (src_layout == ESPM_LAYOUT_CM ? st->p : st->n), "ell_heavy_count: ld=%lld too small", (long long)ld);
+  if (int rc = check_src_view("ell_heavy_count", src_dtype, src_layout, ld, st->n, st->p)) return rc;
   ESPM_REQUIRE(!x_cm_u8 || st->n_cm == roundup(st->n, ESPM_NCM), "ell_heavy_count: x_cm is set but n_cm=%d is not n rounded up to %d", st->n_cm, ESPM_NCM);
   return launch_ell_hv_count(x, src_dtype, src_layout, ld, st->n, st->p, st->n_pad, st->n_cm, x_pm_u8, x_cm_u8, cnt_px,
                              static_cast<hipStream_t>(stream));
@@ -289,9 +303,7 @@ int espm_mu_ell_heavy_fill(const espm_mu_state* st, const void* x, int src_dtype
                            int32_t* hv_pm, espm_stream_t stream) {
   if (int rc = check_ell_geometry(st)) return rc;
   ESPM_REQUIRE(x && px_off && hv_pm, "ell_heavy_fill: NULL pointer");
-  ESPM_REQUIRE(src_dtype == ESPM_SRC_F32 || src_dtype == ESPM_SRC_F64, "ell_heavy_fill: bad src_dtype %d", src_dtype);
-  ESPM_REQUIRE(src_layout == ESPM_LAYOUT_CM || src_layout == ESPM_LAYOUT_PM, "ell_heavy_fill: bad layout %d", src_layout);
-  ESPM_REQUIRE(ld >= (src_layout == ESPM_LAYOUT_CM ? st->p : st->n), "ell_heavy_fill: ld=%lld too small", (long long)ld);
+  if (int rc = check_src_view("ell_heavy_fill", src_dtype, src_layout, ld, st->n, st->p)) return rc;
   return launch_ell_hv_fill(x, src_dtype, src_layout, ld, st->n, st->p, px_off, hv_pm, static_cast<hipStream_t>(stream));
 }
 
@@ -316,8 +328,21 @@ static bool w_simplex_split(const espm_mu_state* st) {
 static double* simplex_bparts(const espm_mu_state* st) {
   return reinterpret_cast<double*>(st->w_scratch) + 3 * (size_t)st->k * ((st->n_pad + 31) / 32);
 }
-// the two launches: st->a_slab -> st->a and the partials; then W', G W' and the tail's partials
-static int w_simplex_reduce_update(const espm_mu_state* st, int src, int slot, const HFinalizeArgs* fin, WTailArgs* defer_tail, hipStream_t s);
+static bool w_update_has_tail(const espm_mu_state* st) { return w_update_is_local(st) || w_simplex_split(st); }
+// Sparse store: the tail of such a W update (column sums of G W', rel_W: one small workgroup, 8 us as a launch of its own) rides in
+// the NEXT H-step's launch as an extra workgroup; that H-step sums the partial column sums itself, and the slab reduction that
+// follows finds colsum_gw written.  The last tail is a launch of its own.  This is the rule of the library's own loops.  A caller
+// that sequences the half-steps itself through tail_mode has ANOTHER one: espm_amd/engine.py (_defers_tail) defers for the local update
+// alone, its simplex split pays the tail's launch.  They stay apart: one rule for both would change a path by a launch per iteration.
+static bool loop_hands_tail_on(const espm_mu_state* st) {
+  return st->x_dtype == ESPM_X_ELL && w_update_has_tail(st) && !(st->pg_q && st->pg_gamma_w > 0.f);
+}
+static int with_halo(const espm_mu_state* st) { return st->grid_mode && st->lambda_l != 0.f; }
+// the simplex over `rows` rows of W has a solution (dicotomy.py:22-23)
+static int simplex_w_feasible(const espm_mu_state* st, double rows) {
+  if (!(st->log_shift > 0.f && rows * (double)st->log_shift >= 1.0)) return ESPM_OK;
+  return set_error(ESPM_ENOSOLUTION, "No solution exists! (rows * log_shift >= 1)");
+}
 
 static WFinishArgs finish_args(const espm_mu_state* st, int src, int hsrc, int slot, int update_w) {
   WFinishArgs a;
@@ -355,41 +380,8 @@ static WFinishArgs finish_args(const espm_mu_state* st, int src, int hsrc, int s
   a.gw_floor = st->gw_floor;
   return a;
 }
-
-static int w_simplex_reduce_update(const espm_mu_state* st, int src, int slot, const HFinalizeArgs* fin, WTailArgs* defer_tail, hipStream_t s) {
-  if (st->log_shift > 0.f && (double)st->n * (double)st->log_shift >= 1.0)
-    return set_error(ESPM_ENOSOLUTION, "No solution exists! (rows * log_shift >= 1)");
-  double* bparts = simplex_bparts(st);
-  if (int rc = launch_w_reduce(st->a_slab, st->a, st->nblk_w, st->k * st->n_pad, fin, s, st->w[src], bparts, st->n, st->k, st->n_pad)) return rc;
-  return launch_w_simplex_update(finish_args(st, src, 1 - src, slot + 1, 1), st->a, bparts, (double)ESPM_W_DICOTOMY_TOL, s, defer_tail);
-}
-
-int espm_mu_build_gw(const espm_mu_state* st, int which, espm_stream_t stream) {
-  if (int rc = check_state(st)) return rc;
-  ESPM_REQUIRE(which == 0 || which == 1, "which must be 0/1");
-  return launch_w_finish(finish_args(st, which, 0, -1, 0), static_cast<hipStream_t>(stream));
-}
-
-int espm_mu_step_h(const espm_mu_state* st, int src, int write_h, espm_stream_t stream) {
-  if (int rc = check_state(st)) return rc;
-  ESPM_REQUIRE(src == 0 || src == 1, "src must be 0/1");
-  if (st->x_dtype == ESPM_X_ELL) {
-    HStepArgs a = make_h_args(st, src, write_h);
-    if (st->tail_mode & ESPM_TAIL_RIDE) {  // the tail of the W update that produced this state rides along (include/espm_mu.h)
-      ESPM_REQUIRE(st->it >= 1 && (w_update_is_local(st) || w_simplex_split(st)), "tail_mode: no local W update produced state %d", st->it);
-      a.tail = make_w_tail_args(finish_args(st, 1 - src, src, st->it, 1));
-      a.cs_parts = a.tail.parts;
-      a.cs_nbk = a.tail.nbk;
-      a.tail_on = 1;
-    }
-    // pixels without counts: the numerator of their log_shift fill first; heavy elements likewise (include/espm_mu.h)
-    if (int rc = ell_pre_h(st, src, static_cast<hipStream_t>(stream))) return rc;
-    if (int rc = launch_h_ell(a, nblk_h(st), static_cast<hipStream_t>(stream))) return rc;
-    return ell_post(st, -1, false, true, static_cast<hipStream_t>(stream));
-  }
-  return dispatch_h_step(make_h_args(st, src, write_h), st->x_dtype, st->tile_px, nblk_h(st),
-                         static_cast<hipStream_t>(stream));
-}
+// the W update of an iteration: w[src] -> w[1 - src] with the row sums of the new H h[1 - src]; state `slot` -> state slot + 1
+static WFinishArgs update_args(const espm_mu_state* st, int src, int slot) { return finish_args(st, src, 1 - src, slot + 1, 1); }
 
 static HFinalizeArgs finalize_args(const espm_mu_state* st, int src, int slot, bool write_hstat) {
   HFinalizeArgs a;
@@ -406,34 +398,125 @@ static HFinalizeArgs finalize_args(const espm_mu_state* st, int src, int slot, b
   a.pg_q = (st->pg_q && st->h_rule == 2 && write_hstat) ? st->pg_q + 2 * (size_t)slot : nullptr;   // (not for loss-only evaluations)
   return a;
 }
+static int record(hipEvent_t e, hipStream_t s) { return e ? check_hip(hipEventRecord(e, s), "iterate_timed: record") : (int)ESPM_OK; }
+
+// ---- the half-steps of an iteration, on a checked state.  Who carries the tail of a W update is an argument: the extern "C"
+//      functions translate the caller's st->tail_mode into it, the library's loops hand a WTailArgs on ------------------------------
+// The H half-step on h[src].  ride: the tail of the W update that produced this state, carried as an extra workgroup (sparse store
+// only).  fused (fused_ok): with the W accumulation.  at_launch: an event of espm_mu_iterate_timed right ahead of the H launch itself.
+static int h_half(const espm_mu_state* st, int src, int write_h, const WTailArgs* ride, bool fused, hipStream_t s, hipEvent_t at_launch = nullptr) {
+  if (st->x_dtype != ESPM_X_ELL) return dispatch_h_step(make_h_args(st, src, write_h), st->x_dtype, st->tile_px, nblk_h(st), s);
+  HStepArgs a = fused ? fused_h_args(st, src) : make_h_args(st, src, write_h);
+  if (ride) a.tail = *ride, a.cs_parts = ride->parts, a.cs_nbk = ride->nbk, a.tail_on = 1;
+  // pixels without counts: the numerator of their log_shift fill first; heavy elements likewise (include/espm_mu.h)
+  if (int rc = ell_pre_h(st, src, s)) return rc;
+  if (int rc = record(at_launch, s)) return rc;
+  if (fused) {
+    if (int rc = launch_fused_ell(a, make_w_args(st), st->nblk_w, s, st->no_fused == 2, st->ell_stream)) return rc;
+    return ell_post(st, 1 - src, true, true, s);
+  }
+  if (int rc = launch_h_ell(a, nblk_h(st), s)) return rc;
+  return ell_post(st, -1, false, true, s);
+}
+// a tail on its way to the H-step that carries it (on: null when there is none)
+struct Ride {
+  WTailArgs tail;
+  const WTailArgs* on = nullptr;
+};
+// ESPM_TAIL_RIDE: the tail that the caller has the H-step on h[src] carry (sparse store)
+static int ride_of_tail_mode(const espm_mu_state* st, int src, Ride* r) {
+  if (st->x_dtype != ESPM_X_ELL || !(st->tail_mode & ESPM_TAIL_RIDE)) return ESPM_OK;
+  ESPM_REQUIRE(st->it >= 1 && w_update_has_tail(st), "tail_mode: no local W update produced state %d", st->it);
+  r->tail = make_w_tail_args(update_args(st, 1 - src, st->it - 1));
+  r->on = &r->tail;
+  return ESPM_OK;
+}
+// ESPM_TAIL_DEFER: where a finish call leaves the tail that the caller has carried later
+static WTailArgs* left_out_of(const espm_mu_state* st, WTailArgs* left_out) { return (st->tail_mode & ESPM_TAIL_DEFER) ? left_out : nullptr; }
+
+static int loss_only(const espm_mu_state* st, int src, int slot, const WTailArgs* ride, hipStream_t s) {
+  if (int rc = h_half(st, src, 0, ride, false, s)) return rc;
+  return launch_h_finalize(finalize_args(st, src, slot, false), s);   // (loss-only: does not touch hstat[1 - src])
+}
+
+static int w_accum(const espm_mu_state* st, hipStream_t s) {
+  ESPM_REQUIRE(st->nblk_w >= 1, "nblk_w must be >= 1");
+  if (st->x_dtype != ESPM_X_ELL) return dispatch_w_accum(make_w_args(st), st->k, st->x_dtype, st->nblk_w, s);
+  if (int rc = launch_w_ell(make_w_args(st), st->k, st->nblk_w, s)) return rc;
+  return ell_post(st, -1, true, false, s);   // (H' = h_t)
+}
+
+static int w_finish(const espm_mu_state* st, int src, int hsrc, int slot, hipStream_t s) {
+  if (st->simplex_w && !st->simplex_rows)
+    if (int rc = simplex_w_feasible(st, st->m > 0 ? st->m : st->n)) return rc;
+  return launch_w_finish(finish_args(st, src, hsrc, slot, 1), s);
+}
+static int simplex_update(const espm_mu_state* st, int src, int slot, WTailArgs* tail_out, hipStream_t s) {
+  return launch_w_simplex_update(update_args(st, src, slot), st->a, simplex_bparts(st), (double)ESPM_W_DICOTOMY_TOL, s, tail_out);
+}
+// The W half-step behind the accumulation: slab reduction and W update w[src] -> w[1 - src].  fin: the reduction of the H-step's
+// records rides in the reduction's launch (null: hstat[1 - src] is already reduced).  tail_out: the update's tail is handed to the
+// caller instead of being launched (null: launched; the one-workgroup finish has no tail).
+static int w_half(const espm_mu_state* st, int src, int slot, const HFinalizeArgs* fin, WTailArgs* tail_out, hipStream_t s) {
+  if (w_update_is_local(st))
+    return launch_w_reduce_update(update_args(st, src, slot), st->a_slab, (size_t)st->k * st->n_pad * sizeof(float), st->nblk_w, st->a,
+                                  fin ? st->hpart : nullptr, nblk_h(st), fin ? nullptr : st->hstat[1 - src], 0, nullptr, fin, s, tail_out);
+  if (w_simplex_split(st)) {   // st->a_slab -> st->a and the bracket's partials; then the update
+    if (int rc = simplex_w_feasible(st, st->n)) return rc;
+    if (int rc = launch_w_reduce(st->a_slab, st->a, st->nblk_w, st->k * st->n_pad, fin, s, st->w[src], simplex_bparts(st), st->n, st->k, st->n_pad)) return rc;
+    return simplex_update(st, src, slot, tail_out, s);
+  }
+  if (int rc = launch_w_reduce(st->a_slab, st->a, st->nblk_w, st->k * st->n_pad, fin, s)) return rc;
+  return w_finish(st, src, 1 - src, slot + 1, s);
+}
+// the same from the gathered records of `world` ranks: their sum, the global statistics of the new H, the W update
+static int shard_combine_finish(const espm_mu_state* st, const void* records, int world, int src, int slot, WTailArgs* tail_out, hipStream_t s) {
+  const size_t stride = espm_mu_shard_record_bytes(st);
+  if (w_update_is_local(st))
+    return launch_w_reduce_update(update_args(st, src, slot), records, stride, world, st->a, nullptr, 0, nullptr,
+                                  (size_t)st->k * st->n_pad * sizeof(float), st->hstat[1 - src], nullptr, s, tail_out);
+  if (w_simplex_split(st)) {   // the sum over the ranks leaves the bracket's sums, many workgroups update
+    if (int rc = simplex_w_feasible(st, st->n)) return rc;
+    if (int rc = launch_shard_combine(records, world, stride, st->k * st->n_pad, st->a, st->hstat[1 - src], s, st->w[src], simplex_bparts(st), st->n, st->k, st->n_pad)) return rc;
+    return simplex_update(st, src, slot, tail_out, s);
+  }
+  if (int rc = launch_shard_combine(records, world, stride, st->k * st->n_pad, st->a, st->hstat[1 - src], s)) return rc;
+  return w_finish(st, src, 1 - src, slot + 1, s);
+}
+
+int espm_mu_build_gw(const espm_mu_state* st, int which, espm_stream_t stream) {
+  if (int rc = check_state(st)) return rc;
+  ESPM_REQUIRE(which == 0 || which == 1, "which must be 0/1");
+  return launch_w_finish(finish_args(st, which, 0, -1, 0), static_cast<hipStream_t>(stream));
+}
+
+int espm_mu_step_h(const espm_mu_state* st, int src, int write_h, espm_stream_t stream) {
+  if (int rc = check_state(st)) return rc;
+  ESPM_REQUIRE(src == 0 || src == 1, "src must be 0/1");
+  Ride r;
+  if (int rc = ride_of_tail_mode(st, src, &r)) return rc;
+  return h_half(st, src, write_h, r.on, false, static_cast<hipStream_t>(stream));
+}
 
 int espm_mu_h_finalize(const espm_mu_state* st, int src, int slot, espm_stream_t stream) {
   if (int rc = check_state(st)) return rc;
   ESPM_REQUIRE(src == 0 || src == 1, "src must be 0/1");
-  ESPM_REQUIRE(slot >= 0 && slot < st->hist_len, "history slot %d outside [0, %d)", slot, st->hist_len);
+  if (int rc = check_slot(st, slot, false)) return rc;
   return launch_h_finalize(finalize_args(st, src, slot, true), static_cast<hipStream_t>(stream));
-}
-
-/* loss-only variant: does not touch hstat[1-src] */
-static int h_finalize_loss_only(const espm_mu_state* st, int src, int slot, hipStream_t stream) {
-  return launch_h_finalize(finalize_args(st, src, slot, false), stream);
 }
 
 int espm_mu_loss_only(const espm_mu_state* st, int src, int slot, espm_stream_t stream) {
   if (int rc = check_state(st)) return rc;
-  ESPM_REQUIRE(slot >= 0 && slot < st->hist_len, "history slot %d outside [0, %d)", slot, st->hist_len);
-  if (int rc = espm_mu_step_h(st, src, 0, stream)) return rc;
-  return h_finalize_loss_only(st, src, slot, static_cast<hipStream_t>(stream));
+  if (int rc = check_slot(st, slot, false)) return rc;
+  ESPM_REQUIRE(src == 0 || src == 1, "src must be 0/1");
+  Ride r;
+  if (int rc = ride_of_tail_mode(st, src, &r)) return rc;
+  return loss_only(st, src, slot, r.on, static_cast<hipStream_t>(stream));
 }
 
 int espm_mu_w_accum(const espm_mu_state* st, espm_stream_t stream) {
   if (int rc = check_state(st)) return rc;
-  ESPM_REQUIRE(st->nblk_w >= 1, "nblk_w must be >= 1");
-  if (st->x_dtype == ESPM_X_ELL) {
-    if (int rc = launch_w_ell(make_w_args(st), st->k, st->nblk_w, static_cast<hipStream_t>(stream))) return rc;
-    return ell_post(st, -1, true, false, static_cast<hipStream_t>(stream));   // (H' = h_t)
-  }
-  return dispatch_w_accum(make_w_args(st), st->k, st->x_dtype, st->nblk_w, static_cast<hipStream_t>(stream));
+  return w_accum(st, static_cast<hipStream_t>(stream));
 }
 
 int espm_mu_fused_applies(const espm_mu_state* st) {
@@ -444,22 +527,12 @@ int espm_mu_fused_applies(const espm_mu_state* st) {
 int espm_mu_step_hw(const espm_mu_state* st, int src, espm_stream_t stream) {
   if (int rc = check_state(st)) return rc;
   ESPM_REQUIRE(src == 0 || src == 1, "src must be 0/1");
-  if (!fused_ok(st)) {
-    if (int rc = espm_mu_step_h(st, src, 1, stream)) return rc;
-    return espm_mu_w_accum(st, stream);
-  }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  HStepArgs a = fused_h_args(st, src);
-  if (st->tail_mode & ESPM_TAIL_RIDE) {  // the tail of the W update that produced this state rides along (include/espm_mu.h)
-    ESPM_REQUIRE(st->it >= 1 && (w_update_is_local(st) || w_simplex_split(st)), "tail_mode: no local W update produced state %d", st->it);
-    a.tail = make_w_tail_args(finish_args(st, 1 - src, src, st->it, 1));
-    a.cs_parts = a.tail.parts;
-    a.cs_nbk = a.tail.nbk;
-    a.tail_on = 1;
-  }
-  if (int rc = ell_pre_h(st, src, s)) return rc;
-  if (int rc = launch_fused_ell(a, make_w_args(st), st->nblk_w, s, st->no_fused == 2, st->ell_stream)) return rc;
-  return ell_post(st, 1 - src, true, true, s);
+  const bool fused = fused_ok(st);
+  Ride r;
+  if (int rc = ride_of_tail_mode(st, src, &r)) return rc;
+  if (int rc = h_half(st, src, 1, r.on, fused, s)) return rc;
+  return fused ? ESPM_OK : w_accum(st, s);
 }
 
 int espm_mu_w_reduce(const espm_mu_state* st, espm_stream_t stream) {
@@ -470,7 +543,7 @@ int espm_mu_w_reduce(const espm_mu_state* st, espm_stream_t stream) {
 int espm_mu_w_reduce_finalize(const espm_mu_state* st, int src, int slot, espm_stream_t stream) {
   if (int rc = check_state(st)) return rc;
   ESPM_REQUIRE(src == 0 || src == 1, "src must be 0/1");
-  ESPM_REQUIRE(slot >= 0 && slot < st->hist_len, "history slot %d outside [0, %d)", slot, st->hist_len);
+  if (int rc = check_slot(st, slot, false)) return rc;
   const HFinalizeArgs fin = finalize_args(st, src, slot, true);
   return launch_w_reduce(st->a_slab, st->a, st->nblk_w, st->k * st->n_pad, &fin, static_cast<hipStream_t>(stream));
 }
@@ -478,57 +551,25 @@ int espm_mu_w_reduce_finalize(const espm_mu_state* st, int src, int slot, espm_s
 int espm_mu_w_finish(const espm_mu_state* st, int src, int hsrc, int slot, espm_stream_t stream) {
   if (int rc = check_state(st)) return rc;
   ESPM_REQUIRE((src == 0 || src == 1) && (hsrc == 0 || hsrc == 1), "src/hsrc must be 0/1");
-  ESPM_REQUIRE(slot < st->hist_len, "history slot %d outside [0, %d)", slot, st->hist_len);
-  if (st->simplex_w && st->log_shift > 0.f) {
-    const double rows = st->m > 0 ? st->m : st->n;
-    if (!st->simplex_rows && rows * (double)st->log_shift >= 1.0)
-      return set_error(ESPM_ENOSOLUTION, "No solution exists! (rows * log_shift >= 1)");
-  }
-  return launch_w_finish(finish_args(st, src, hsrc, slot, 1), static_cast<hipStream_t>(stream));
+  ESPM_REQUIRE(slot < st->hist_len, "history slot %d outside [0, %d)", slot, st->hist_len);   // (slot < 0: no history row, no rel_W)
+  return w_finish(st, src, hsrc, slot, static_cast<hipStream_t>(stream));
 }
 
 int espm_mu_w_reduce_finish(const espm_mu_state* st, int src, int slot, int with_finalize, espm_stream_t stream) {
   if (int rc = check_state(st)) return rc;
   ESPM_REQUIRE(src == 0 || src == 1, "src must be 0/1");
-  ESPM_REQUIRE(slot >= 0 && slot + 1 < st->hist_len, "history slot %d + 1 outside [0, %d)", slot, st->hist_len);
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = check_slot(st, slot, true)) return rc;
   const HFinalizeArgs fin = finalize_args(st, src, slot, true);
-  WTailArgs left_out;   // ESPM_TAIL_DEFER: the caller has the tail carried by the next H-step (or espm_mu_w_update_tail)
-  if (w_update_is_local(st)) {
-    return launch_w_reduce_update(finish_args(st, src, 1 - src, slot + 1, 1), st->a_slab, (size_t)st->k * st->n_pad * sizeof(float),
-                                  st->nblk_w, st->a, with_finalize ? st->hpart : nullptr, nblk_h(st), with_finalize ? nullptr : st->hstat[1 - src],
-                                  0, nullptr, with_finalize ? &fin : nullptr, s,   // (no riding finalize: hstat[1-src] is already reduced)
-                                  (st->tail_mode & ESPM_TAIL_DEFER) ? &left_out : nullptr);
-  }
-  if (w_simplex_split(st))
-    return w_simplex_reduce_update(st, src, slot, with_finalize ? &fin : nullptr, (st->tail_mode & ESPM_TAIL_DEFER) ? &left_out : nullptr, s);
-  if (int rc = launch_w_reduce(st->a_slab, st->a, st->nblk_w, st->k * st->n_pad, with_finalize ? &fin : nullptr, s)) return rc;
-  return espm_mu_w_finish(st, src, 1 - src, slot + 1, stream);
+  WTailArgs left_out;
+  return w_half(st, src, slot, with_finalize ? &fin : nullptr, left_out_of(st, &left_out), static_cast<hipStream_t>(stream));
 }
 
-int espm_mu_shard_combine_finish(const espm_mu_state* st, const void* records, int world, int src, int slot,
-                                 espm_stream_t stream) {
+int espm_mu_shard_combine_finish(const espm_mu_state* st, const void* records, int world, int src, int slot, espm_stream_t stream) {
   if (int rc = check_state(st)) return rc;
   ESPM_REQUIRE(records && world >= 1 && (src == 0 || src == 1), "shard_combine_finish: bad arguments");
-  ESPM_REQUIRE(slot >= 0 && slot + 1 < st->hist_len, "history slot %d + 1 outside [0, %d)", slot, st->hist_len);
+  if (int rc = check_slot(st, slot, true)) return rc;
   WTailArgs left_out;
-  if (w_update_is_local(st)) {
-    return launch_w_reduce_update(finish_args(st, src, 1 - src, slot + 1, 1), records, espm_mu_shard_record_bytes(st), world, st->a,
-                                  nullptr, 0, nullptr, (size_t)st->k * st->n_pad * sizeof(float), st->hstat[1 - src], nullptr,
-                                  static_cast<hipStream_t>(stream), (st->tail_mode & ESPM_TAIL_DEFER) ? &left_out : nullptr);
-  }
-  if (w_simplex_split(st)) {   // the simplex over W with G = identity: the sum over the ranks leaves the bracket's sums, many workgroups update
-    if (st->log_shift > 0.f && (double)st->n * (double)st->log_shift >= 1.0)
-      return set_error(ESPM_ENOSOLUTION, "No solution exists! (rows * log_shift >= 1)");
-    double* bparts = simplex_bparts(st);
-    if (int rc = launch_shard_combine(records, world, espm_mu_shard_record_bytes(st), st->k * st->n_pad, st->a, st->hstat[1 - src],
-                                      static_cast<hipStream_t>(stream), st->w[src], bparts, st->n, st->k, st->n_pad))
-      return rc;
-    return launch_w_simplex_update(finish_args(st, src, 1 - src, slot + 1, 1), st->a, bparts, (double)ESPM_W_DICOTOMY_TOL,
-                                   static_cast<hipStream_t>(stream), (st->tail_mode & ESPM_TAIL_DEFER) ? &left_out : nullptr);
-  }
-  if (int rc = espm_mu_shard_combine(st, records, world, 1 - src, stream)) return rc;
-  return espm_mu_w_finish(st, src, 1 - src, slot + 1, stream);
+  return shard_combine_finish(st, records, world, src, slot, left_out_of(st, &left_out), static_cast<hipStream_t>(stream));
 }
 
 int espm_mu_w_update_is_local(const espm_mu_state* st) {
@@ -538,13 +579,44 @@ int espm_mu_w_update_is_local(const espm_mu_state* st) {
 
 int espm_mu_w_update_tail(const espm_mu_state* st, int src, int slot, espm_stream_t stream) {
   if (int rc = check_state(st)) return rc;
-  ESPM_REQUIRE((src == 0 || src == 1) && slot >= 0 && slot + 1 < st->hist_len && (w_update_is_local(st) || w_simplex_split(st)), "w_update_tail: bad arguments");
-  return launch_w_update_tail(make_w_tail_args(finish_args(st, src, 1 - src, slot + 1, 1)), static_cast<hipStream_t>(stream));
+  ESPM_REQUIRE((src == 0 || src == 1) && slot >= 0 && slot + 1 < st->hist_len && w_update_has_tail(st), "w_update_tail: bad arguments");
+  return launch_w_update_tail(make_w_tail_args(update_args(st, src, slot)), static_cast<hipStream_t>(stream));
 }
 
 // ev (espm_mu_iterate_timed only): 3 HIP events per iteration, recorded on the launch stream ahead of the iteration's first launch,
 // between its first launch (the H update - with the W accumulation where the fused kernel applies) and what follows, and behind its last.
-static int iterate_impl(espm_mu_state* st, int n_iter, int final_loss, espm_stream_t stream, hipEvent_t* ev);
+// (st->tail_mode is the input of callers that sequence the half-steps themselves: the loop neither reads nor writes it)
+static int iterate_impl(espm_mu_state* st, int n_iter, int final_loss, espm_stream_t stream, hipEvent_t* ev) {
+  if (int rc = check_state(st)) return rc;
+  ESPM_REQUIRE(n_iter >= 0, "n_iter must be >= 0");
+  if (int rc = check_room(st, n_iter)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool hand_on = loop_hands_tail_on(st);
+  // Both half-steps in one launch where the fused kernel applies (mu_fused_kernel.hpp): 2 launches per iteration instead of 3.
+  const bool fused = fused_ok(st);
+  Ride r;   // the tail of the last W update while an H-step is still to carry it
+  int rc;
+  for (int i = 0; i < n_iter; ++i) {
+    const int cur = st->cur, slot = st->it;
+    auto mark = [&](int j) { return record(ev ? ev[3 * i + j] : nullptr, s); };
+    // (where the tail is handed on, the first event has always sat behind the sparse store's preparatory passes and the second ahead
+    //  of a W accumulation of its own; elsewhere around the whole of what espm_mu_step_hw issues)
+    if (!hand_on && (rc = mark(0))) return rc;
+    if ((rc = h_half(st, cur, 1, r.on, fused, s, hand_on && ev ? ev[3 * i] : nullptr))) return rc;
+    if (hand_on && (rc = mark(1))) return rc;
+    if (!fused && (rc = w_accum(st, s))) return rc;   // (with the heavy elements' part of the slabs)
+    if (!hand_on && (rc = mark(1))) return rc;
+    // slab reduction with the H-step's finalize riding in the same launch, then (or, when W' is local, in it) the W update
+    const HFinalizeArgs fin = finalize_args(st, cur, slot, true);
+    if ((rc = w_half(st, cur, slot, &fin, hand_on ? &r.tail : nullptr, s))) return rc;
+    if ((rc = mark(2))) return rc;
+    r.on = hand_on ? &r.tail : nullptr;
+    st->cur = 1 - cur;
+    st->it = slot + 1;
+  }
+  if (r.on && (rc = launch_w_update_tail(r.tail, s))) return rc;
+  return final_loss ? loss_only(st, st->cur, st->it, nullptr, s) : (int)ESPM_OK;
+}
 
 int espm_mu_iterate(espm_mu_state* st, int n_iter, int final_loss, espm_stream_t stream) { return iterate_impl(st, n_iter, final_loss, stream, nullptr); }
 
@@ -566,69 +638,6 @@ int espm_mu_iterate_timed(espm_mu_state* st, int n_iter, float* first_ms, float*
   return rc;
 }
 
-static int iterate_impl(espm_mu_state* st, int n_iter, int final_loss, espm_stream_t stream, hipEvent_t* ev) {
-  if (int rc = check_state(st)) return rc;
-  ESPM_REQUIRE(n_iter >= 0, "n_iter must be >= 0");
-  ESPM_REQUIRE(st->it + n_iter < st->hist_len, "history too short: it=%d + %d >= %d", st->it, n_iter, st->hist_len);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  // Sparse store with a local W update: the tail of the W update (column sums of G W', rel_W: one small workgroup, 8 us as
-  // a launch of its own) rides in the NEXT H-step's launch as an extra workgroup; that H-step sums the partial column sums
-  // itself, and the slab reduction that follows finds colsum_gw written.  The last tail is a launch of its own.
-  const bool split = w_simplex_split(st);   // (the simplex over W with G = identity: two launches after the accumulation, same tail)
-  const bool defer = st->x_dtype == ESPM_X_ELL && (w_update_is_local(st) || split) && !(st->pg_q && st->pg_gamma_w > 0.f);
-  // Both half-steps in one launch where the fused kernel applies (mu_fused_kernel.hpp): 2 launches per iteration instead of 3.
-  const bool fused = fused_ok(st);
-  bool pending = false;
-  WTailArgs tail;
-  for (int i = 0; i < n_iter; ++i) {
-    const int cur = st->cur, slot = st->it;
-    int rc;
-    if (defer) {
-      HStepArgs a = fused ? fused_h_args(st, cur) : make_h_args(st, cur, 1);
-      if ((rc = ell_pre_h(st, cur, s))) return rc;
-      if (pending) {
-        a.cs_parts = tail.parts;
-        a.cs_nbk = tail.nbk;
-        a.tail_on = 1;
-        a.tail = tail;
-      }
-      if (ev && (rc = check_hip(hipEventRecord(ev[3 * i], s), "iterate_timed: record"))) return rc;
-      if (fused) {
-        if ((rc = launch_fused_ell(a, make_w_args(st), st->nblk_w, s, st->no_fused == 2, st->ell_stream))) return rc;
-        if ((rc = ell_post(st, 1 - cur, true, true, s))) return rc;
-        if (ev && (rc = check_hip(hipEventRecord(ev[3 * i + 1], s), "iterate_timed: record"))) return rc;
-      } else {
-        if ((rc = launch_h_ell(a, nblk_h(st), s))) return rc;
-        if ((rc = ell_post(st, -1, false, true, s))) return rc;
-        if (ev && (rc = check_hip(hipEventRecord(ev[3 * i + 1], s), "iterate_timed: record"))) return rc;
-        if ((rc = espm_mu_w_accum(st, stream))) return rc;   // (with the heavy elements' part of the slabs)
-      }
-      const HFinalizeArgs fin = finalize_args(st, cur, slot, true);
-      if (split) {
-        if ((rc = w_simplex_reduce_update(st, cur, slot, &fin, &tail, s))) return rc;
-      } else if ((rc = launch_w_reduce_update(finish_args(st, cur, 1 - cur, slot + 1, 1), st->a_slab, (size_t)st->k * st->n_pad * sizeof(float),
-                                              st->nblk_w, st->a, st->hpart, nblk_h(st), nullptr, 0, nullptr, &fin, s, &tail))) {
-        return rc;
-      }
-      if (ev && (rc = check_hip(hipEventRecord(ev[3 * i + 2], s), "iterate_timed: record"))) return rc;
-      pending = true;
-    } else {
-      if (ev && (rc = check_hip(hipEventRecord(ev[3 * i], s), "iterate_timed: record"))) return rc;
-      if ((rc = espm_mu_step_hw(st, cur, stream))) return rc;   // (one launch where the fused kernel applies, else H-step + W accumulation)
-      if (ev && (rc = check_hip(hipEventRecord(ev[3 * i + 1], s), "iterate_timed: record"))) return rc;
-      // slab reduction with the H-step's finalize riding in the same launch, then (or, when W' is local, in it) the W update
-      if ((rc = espm_mu_w_reduce_finish(st, cur, slot, 1, stream))) return rc;
-      if (ev && (rc = check_hip(hipEventRecord(ev[3 * i + 2], s), "iterate_timed: record"))) return rc;
-    }
-    st->cur = 1 - cur;
-    st->it = slot + 1;
-  }
-  if (pending)
-    if (int rc = launch_w_update_tail(tail, s)) return rc;
-  if (final_loss) return espm_mu_loss_only(st, st->cur, st->it, stream);
-  return ESPM_OK;
-}
-
 // ---- H-only iterations (include/espm_mu.h) -------------------------------------------------------------------------------------
 static bool h_chain_ok(const espm_mu_state* st) { return st->hpart_alt != nullptr && h_chain_built(st); }
 
@@ -640,7 +649,7 @@ int espm_mu_h_chain_applies(const espm_mu_state* st) {
 int espm_mu_iterate_h(espm_mu_state* st, int n_iter, int final_loss, espm_stream_t stream) {
   if (int rc = check_state(st)) return rc;
   ESPM_REQUIRE(n_iter >= 0, "n_iter must be >= 0");
-  ESPM_REQUIRE(st->it + n_iter < st->hist_len, "history too short: it=%d + %d >= %d", st->it, n_iter, st->hist_len);
+  if (int rc = check_room(st, n_iter)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (n_iter > 0)   // rel_W of an update that leaves W alone (base.py:323)
     if (int rc = check_hip(hipMemset2DAsync(st->hist + (size_t)(st->it + 1) * ESPM_HI_STRIDE + ESPM_HI_REL_W, ESPM_HI_STRIDE * sizeof(double), 0,
@@ -680,98 +689,89 @@ int espm_mu_iterate_h(espm_mu_state* st, int n_iter, int final_loss, espm_stream
       st->it = slot + 1;
     }
   }
-  if (final_loss) return espm_mu_loss_only(st, st->cur, st->it, stream);
+  return final_loss ? espm_mu_loss_only(st, st->cur, st->it, stream) : (int)ESPM_OK;
+}
+
+// the exchange context was created for this state's records
+static int check_record_bytes(const char* what, const espm_mu_state* st, const espm_xchg* x) {
+  ESPM_REQUIRE(x->record_bytes == espm_mu_shard_record_bytes(st), "%s: the exchange was created for records of %zu bytes, the state packs %zu", what,
+               x->record_bytes, espm_mu_shard_record_bytes(st));
   return ESPM_OK;
+}
+
+// The sharded W half-step behind the accumulation; fin rides always, tail_out as in w_half.
+static int shard_exchange_finish(const espm_mu_state* st, espm_xchg* x, uint32_t seq, int src, int slot, WTailArgs* tail_out, hipStream_t s) {
+  const HFinalizeArgs fin = finalize_args(st, src, slot, true);
+  const WFinishArgs f = update_args(st, src, slot);
+  const size_t slab_bytes = (size_t)st->k * st->n_pad * sizeof(float);
+  if (!w_update_is_local(st) && st->no_fused != 1 && w_gsplit_applies(f)) {
+    // a dictionary G without a simplex over W: every rank contracts its own A with G and the m k results cross the links as
+    // granules (w_gxchg_update_kernel): slab reduction + record reduction, exchange + W update, rows of G W' - three launches
+    // (this rank's statistics go to its own record in its own mailbox: the exchange launch sends them on, and writes the global ones)
+    double* local = reinterpret_cast<double*>(x->mailbox + (size_t)(seq & 1u) * x->world * x->record_bytes + (size_t)x->rank * x->record_bytes + slab_bytes);
+    HFinalizeArgs fin_local = fin;
+    fin_local.hstat_out = local;
+    if (int rc = launch_w_reduce(st->a_slab, st->a, st->nblk_w, st->k * st->n_pad, &fin_local, s)) return rc;
+    return launch_w_gxchg_update(f, x, seq, local, st->hstat[1 - src], st->h[1 - src], st->nx, st->ny, st->p_pad, with_halo(st), s);
+  }
+  const bool split = w_simplex_split(st) && nblk_h(st) > 0;
+  if (!split && (!w_update_is_local(st) || st->no_fused == 1)) {   // W' needs a global finish (G given, simplex over W): the four steps
+    if (int rc = espm_mu_w_reduce_pack(st, src, slot, x->staging, s)) return rc;
+    if (int rc = espm_xchg_post(x, seq, s)) return rc;
+    if (int rc = espm_xchg_wait(x, seq, s)) return rc;
+    return shard_combine_finish(st, espm_xchg_records(x, (int)(seq & 1u)), x->world, src, slot, tail_out, s);
+  }
+  // One launch when W' is local.  The simplex over W with G = identity (the estimator's default constraints): the pieces of A cross
+  // the links as granules like the local update's, the workgroup that sums 32 entries leaves the bracket's partials,
+  // w_simplex_update_kernel follows and owns the tail - two launches
+  if (split)
+    if (int rc = simplex_w_feasible(st, st->n)) return rc;
+  if (int rc = launch_w_exchange_update(f, st->a_slab, slab_bytes, st->nblk_w, st->a, st->hstat[1 - src], fin, x, seq, st->h[1 - src], st->nx, st->ny,
+                                        st->p_pad, with_halo(st), s, split ? nullptr : tail_out, split ? simplex_bparts(st) : nullptr))
+    return rc;
+  return split ? simplex_update(st, src, slot, tail_out, s) : ESPM_OK;
 }
 
 int espm_mu_shard_exchange_finish(const espm_mu_state* st, espm_xchg* x, uint32_t seq, int src, int slot, espm_stream_t stream) {
   if (int rc = check_state(st)) return rc;
   ESPM_REQUIRE(x && (src == 0 || src == 1), "shard_exchange_finish: bad arguments");
-  ESPM_REQUIRE(slot >= 0 && slot + 1 < st->hist_len, "history slot %d + 1 outside [0, %d)", slot, st->hist_len);
-  ESPM_REQUIRE(x->record_bytes == espm_mu_shard_record_bytes(st), "shard_exchange_finish: the exchange was created for records of %zu bytes, the state packs %zu",
-               x->record_bytes, espm_mu_shard_record_bytes(st));
-  if (!w_update_is_local(st) && st->no_fused != 1) {
-    // a dictionary G without a simplex over W: every rank contracts its own A with G and the m k results cross the links as
-    // granules (w_gxchg_update_kernel): slab reduction + record reduction, exchange + W update, rows of G W' - three launches
-    const WFinishArgs f = finish_args(st, src, 1 - src, slot + 1, 1);
-    if (w_gsplit_applies(f)) {
-      HFinalizeArgs fin = finalize_args(st, src, slot, true);
-      // (this rank's statistics go to its own record in its own mailbox: the exchange launch sends them on, and writes the global ones)
-      double* local = reinterpret_cast<double*>(x->mailbox + (size_t)(seq & 1u) * x->world * x->record_bytes + (size_t)x->rank * x->record_bytes +
-                                                (size_t)st->k * st->n_pad * 4);
-      fin.hstat_out = local;
-      if (int rc = launch_w_reduce(st->a_slab, st->a, st->nblk_w, st->k * st->n_pad, &fin, static_cast<hipStream_t>(stream))) return rc;
-      const int with_halo_g = st->grid_mode && st->lambda_l != 0.f;
-      return launch_w_gxchg_update(f, x, seq, local, st->hstat[1 - src], st->h[1 - src], st->nx, st->ny, st->p_pad, with_halo_g,
-                                   static_cast<hipStream_t>(stream));
-    }
-  }
-  if (w_simplex_split(st) && nblk_h(st) > 0) {
-    // the simplex over W with G = identity (the estimator's default constraints): the pieces of A cross the links as granules like
-    // the local update's, the workgroup that sums 32 entries leaves the bracket's partials, w_simplex_update_kernel follows - two launches
-    if (st->log_shift > 0.f && (double)st->n * (double)st->log_shift >= 1.0)
-      return set_error(ESPM_ENOSOLUTION, "No solution exists! (rows * log_shift >= 1)");
-    const HFinalizeArgs fin = finalize_args(st, src, slot, true);
-    WTailArgs left_out;
-    const int with_halo = st->grid_mode && st->lambda_l != 0.f;
-    double* bparts = simplex_bparts(st);
-    if (int rc = launch_w_exchange_update(finish_args(st, src, 1 - src, slot + 1, 1), st->a_slab, (size_t)st->k * st->n_pad * sizeof(float), st->nblk_w,
-                                          st->a, st->hstat[1 - src], fin, x, seq, st->h[1 - src], st->nx, st->ny, st->p_pad, with_halo,
-                                          static_cast<hipStream_t>(stream), nullptr, bparts))
-      return rc;
-    return launch_w_simplex_update(finish_args(st, src, 1 - src, slot + 1, 1), st->a, bparts, (double)ESPM_W_DICOTOMY_TOL,
-                                   static_cast<hipStream_t>(stream), (st->tail_mode & ESPM_TAIL_DEFER) ? &left_out : nullptr);
-  }
-  if (!w_update_is_local(st) || st->no_fused == 1) {   // W' needs a global finish (G given, simplex over W): the four steps
-    if (int rc = espm_mu_w_reduce_pack(st, src, slot, x->staging, stream)) return rc;
-    if (int rc = espm_xchg_post(x, seq, stream)) return rc;
-    if (int rc = espm_xchg_wait(x, seq, stream)) return rc;
-    return espm_mu_shard_combine_finish(st, espm_xchg_records(x, (int)(seq & 1u)), x->world, src, slot, stream);
-  }
-  const HFinalizeArgs fin = finalize_args(st, src, slot, true);
+  if (int rc = check_slot(st, slot, true)) return rc;
+  if (int rc = check_record_bytes("shard_exchange_finish", st, x)) return rc;
   WTailArgs left_out;
-  const int with_halo = st->grid_mode && st->lambda_l != 0.f;
-  return launch_w_exchange_update(finish_args(st, src, 1 - src, slot + 1, 1), st->a_slab, (size_t)st->k * st->n_pad * sizeof(float), st->nblk_w,
-                                  st->a, st->hstat[1 - src], fin, x, seq, st->h[1 - src], st->nx, st->ny, st->p_pad, with_halo,
-                                  static_cast<hipStream_t>(stream), (st->tail_mode & ESPM_TAIL_DEFER) ? &left_out : nullptr);
+  return shard_exchange_finish(st, x, seq, src, slot, left_out_of(st, &left_out), static_cast<hipStream_t>(stream));
 }
 
+// (st->tail_mode is read once: ESPM_TAIL_RIDE hands over a deferred tail of the caller's own last update.  Never written.)
 int espm_mu_iterate_sharded(espm_mu_state* st, espm_xchg* x, uint32_t* seq, int n_iter, int final_loss, espm_stream_t stream) {
   if (int rc = check_state(st)) return rc;
   ESPM_REQUIRE(x && seq && n_iter >= 0, "iterate_sharded: bad arguments");
-  ESPM_REQUIRE(st->it + n_iter < st->hist_len, "history too short: it=%d + %d >= %d", st->it, n_iter, st->hist_len);
-  ESPM_REQUIRE(x->record_bytes == espm_mu_shard_record_bytes(st), "iterate_sharded: the exchange was created for records of %zu bytes, the state packs %zu",
-               x->record_bytes, espm_mu_shard_record_bytes(st));
-  const bool defer = st->x_dtype == ESPM_X_ELL && (w_update_is_local(st) || w_simplex_split(st)) && !(st->pg_q && st->pg_gamma_w > 0.f);
-  const bool with_halo = st->grid_mode && st->lambda_l != 0.f;
+  if (int rc = check_room(st, n_iter)) return rc;
+  if (int rc = check_record_bytes("iterate_sharded", st, x)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool hand_on = loop_hands_tail_on(st), fused = fused_ok(st);
   // byte offsets inside a record: [A | statistics | first owned image row | last owned image row]
   const size_t off_top = (size_t)st->k * st->n_pad * 4 + ESPM_HS_STRIDE * 8, off_bot = off_top + (size_t)st->k * (st->ny > 0 ? st->ny : 0) * 4;
-  bool pending = (st->tail_mode & ESPM_TAIL_RIDE) != 0;   // the caller may hand over a deferred tail of its own last update
-  int rc = ESPM_OK;
+  Ride r;
+  int rc = ride_of_tail_mode(st, st->cur, &r);
   for (int i = 0; i < n_iter && !rc; ++i) {
     const int cur = st->cur, slot = st->it;
-    st->tail_mode = pending ? ESPM_TAIL_RIDE : 0;
-    rc = espm_mu_step_hw(st, cur, stream);
-    st->tail_mode = 0;
-    const uint32_t s = ++*seq;
-    const unsigned char* recs = static_cast<const unsigned char*>(espm_xchg_records(x, (int)(s & 1u)));
-    st->tail_mode = defer ? ESPM_TAIL_DEFER : 0;
+    rc = h_half(st, cur, 1, r.on, fused, s);
+    if (!rc && !fused) rc = w_accum(st, s);
+    const uint32_t q = ++*seq;
+    const unsigned char* recs = static_cast<const unsigned char*>(espm_xchg_records(x, (int)(q & 1u)));
     // slab reduction, exchange of the records and W update: one launch when W' needs nothing but the global row sums
-    if (!rc) rc = espm_mu_shard_exchange_finish(st, x, s, cur, slot, stream);
-    st->tail_mode = 0;
-    pending = defer;
-    if (with_halo) {   // the row above this block is the LAST owned row of rank - 1, the row below the FIRST of rank + 1
+    if (!rc) rc = shard_exchange_finish(st, x, q, cur, slot, hand_on ? &r.tail : nullptr, s);
+    r.on = hand_on ? &r.tail : nullptr;
+    if (with_halo(st)) {   // the row above this block is the LAST owned row of rank - 1, the row below the FIRST of rank + 1
       st->halo_top = x->rank > 0 ? reinterpret_cast<const float*>(recs + (size_t)(x->rank - 1) * x->record_bytes + off_bot) : nullptr;
       st->halo_bot = x->rank < x->world - 1 ? reinterpret_cast<const float*>(recs + (size_t)(x->rank + 1) * x->record_bytes + off_top) : nullptr;
     }
     st->cur = 1 - cur;
     st->it = slot + 1;
   }
-  if (rc) return rc;
-  if (pending)
-    if ((rc = espm_mu_w_update_tail(st, 1 - st->cur, st->it - 1, stream))) return rc;
-  if (final_loss) return espm_mu_loss_only(st, st->cur, st->it, stream);
-  return ESPM_OK;
+  if (!rc && r.on) rc = launch_w_update_tail(r.tail, s);
+  if (rc || !final_loss) return rc;
+  return loss_only(st, st->cur, st->it, nullptr, s);
 }
 
 int espm_dichotomy_simplex(const double* num, const double* den, int k, int p, int den_cols, double log_shift,
@@ -901,19 +901,17 @@ size_t espm_mu_shard_record_bytes(const espm_mu_state* st) {
 int espm_mu_shard_pack(const espm_mu_state* st, int hnew, void* record, espm_stream_t stream) {
   if (int rc = check_state(st)) return rc;
   ESPM_REQUIRE(record && (hnew == 0 || hnew == 1), "shard_pack: bad arguments");
-  const int with_halo = st->grid_mode && st->lambda_l != 0.f;
   return launch_shard_pack(st->a, st->hstat[hnew], st->h[hnew], st->k, st->n_pad, st->nx, st->ny, st->p_pad,
-                           with_halo, record, static_cast<hipStream_t>(stream));
+                           with_halo(st), record, static_cast<hipStream_t>(stream));
 }
 
 int espm_mu_w_reduce_pack(const espm_mu_state* st, int src, int slot, void* record, espm_stream_t stream) {
   if (int rc = check_state(st)) return rc;
   ESPM_REQUIRE(record && (src == 0 || src == 1), "w_reduce_pack: bad arguments");
-  ESPM_REQUIRE(slot >= 0 && slot < st->hist_len, "history slot %d outside [0, %d)", slot, st->hist_len);
+  if (int rc = check_slot(st, slot, false)) return rc;
   HFinalizeArgs fin = finalize_args(st, src, slot, true);
   fin.hstat_out = reinterpret_cast<double*>(static_cast<unsigned char*>(record) + (size_t)st->k * st->n_pad * 4);
-  const int with_halo = st->grid_mode && st->lambda_l != 0.f;
-  return launch_w_reduce_pack(st->a_slab, st->nblk_w, st->k, st->n_pad, fin, st->h[1 - src], st->nx, st->ny, st->p_pad, with_halo,
+  return launch_w_reduce_pack(st->a_slab, st->nblk_w, st->k, st->n_pad, fin, st->h[1 - src], st->nx, st->ny, st->p_pad, with_halo(st),
                               record, static_cast<hipStream_t>(stream));
 }
 

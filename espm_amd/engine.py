@@ -18,6 +18,7 @@ Data layout in HBM (all caller-visible arrays are plain torch tensors):
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import sys
@@ -501,6 +502,10 @@ class MUEngine:
         st.hist, st.hist_len = self.hist.data_ptr(), self.hist_len
         st.pg_q = self.pg_q.data_ptr() if self.pg_q is not None else None
         st.cur, st.it = 0, 0
+        # what a host-sequenced iteration has left for a later launch to carry (eval_current, finish_iteration, _flush_finalize)
+        self._pending_finalize = None   # (cur, it) of an H-step whose records are not reduced yet
+        self._pending_tail = False      # the last W update's tail is still to run (include/espm_mu.h: tail_mode)
+        self._accum_done = False        # the W accumulation rode in the H-step's launch
 
     def _launch_policy(self, fused, autotune, max_iter):
         """How the iteration is launched: fused or not, streamed list loads, whether the first load_state times the plans."""
@@ -514,7 +519,6 @@ class MUEngine:
         # ESPM_ELL_STREAM_MB: another threshold, for A/B - 0 streams always, a huge one never)
         limit = float(os.environ["ESPM_ELL_STREAM_MB"]) * 2 ** 20 if os.environ.get("ESPM_ELL_STREAM_MB") else _lib.ELL_STREAM_BYTES
         st.ell_stream = int(self.x_store == "ell" and self.x_bytes > limit)
-        self._accum_done = False
         # autotune: at the first load_state the launch plans that apply to this problem are timed on the ingested image and
         # the fastest is kept (see autotune_plan)
         # "auto": the policy of the product (SmoothNMF.fit hands it down, bench.py too): timing the plans costs ~35 ms of device
@@ -779,24 +783,53 @@ class MUEngine:
         self._flush_finalize(tail=False)
         if self.frobenius:
             self._frobenius_of_current()
-        # the tail of the W update that produced this state (column sums of G W', rel_W) rides in this launch (tail_mode,
-        # include/espm_mu.h) instead of costing one of its own
-        carry = getattr(self, "_pending_tail", False)
-        st.tail_mode = _lib.TAIL_RIDE if carry else 0
-        self._pending_tail = False
-        try:
-            if advance_h:
-                # (the W accumulation rides in the same launch where the fused kernel applies; finish_iteration then skips it)
-                self._accum_done = (not self.frobenius) and bool(self.lib.espm_mu_fused_applies(C.byref(st)))
-                if self._accum_done:
-                    self._check(self.lib.espm_mu_step_hw(C.byref(st), st.cur, _stream()))
-                else:
-                    self._check(self.lib.espm_mu_step_h(C.byref(st), st.cur, 1, _stream()))
-                self._pending_finalize = (st.cur, st.it)
-            else:
+        if advance_h:
+            # (the W accumulation rides in the same launch where the fused kernel applies; finish_iteration then skips it)
+            self._advance_h(with_accum=(not self.frobenius) and bool(self.lib.espm_mu_fused_applies(C.byref(st))))
+        else:
+            with self._riding_tail():
                 self._check(self.lib.espm_mu_loss_only(C.byref(st), st.cur, st.it, _stream()))
+
+    @contextlib.contextmanager
+    def _tail_mode(self, mode):
+        """st.tail_mode = mode for the calls inside, 0 again behind them (include/espm_mu.h: the caller sets the bits per call)."""
+        self.st.tail_mode = mode
+        try:
+            yield
         finally:
-            st.tail_mode = 0
+            self.st.tail_mode = 0
+
+    def _riding_tail(self):
+        """For one H-step launch: the tail of the W update that produced this state (column sums of G W', rel_W), if it is still
+        pending, rides in that launch (ESPM_TAIL_RIDE) instead of costing one of its own."""
+        carry, self._pending_tail = self._pending_tail, False
+        return self._tail_mode(_lib.TAIL_RIDE if carry else 0)
+
+    def _defers_tail(self):
+        """Whether finish_iteration leaves the W update's tail to the next H-step's launch (or to _flush_finalize): sparse store,
+        local W update.  The library's own loops also defer for the simplex split (csrc/mu_api.hip: loop_hands_tail_on); this
+        path does not, and pays that tail's launch."""
+        return self.ell is not None and self.pg_q is None and bool(self.lib.espm_mu_w_update_is_local(C.byref(self.st)))
+
+    def _advance_h(self, with_accum):
+        """The H-step from the current state, its record reduction left pending; with_accum: espm_mu_step_hw, the W accumulation
+        with it (one launch where the fused kernel applies)."""
+        st = self.st
+        with self._riding_tail():
+            if with_accum:
+                self._check(self.lib.espm_mu_step_hw(C.byref(st), st.cur, _stream()))
+            else:
+                self._check(self.lib.espm_mu_step_h(C.byref(st), st.cur, 1, _stream()))
+        self._accum_done = with_accum
+        self._pending_finalize = (st.cur, st.it)
+
+    def _begin_batch(self, n_iter):
+        """Ahead of n_iter iterations enqueued in one go: room in the history, nothing pending (a pending fused H update is simply
+        redone by the loop)."""
+        if self.st.it + int(n_iter) + 1 > self.hist_len:
+            raise ValueError("history buffer exhausted: raise max_iter")
+        self._flush_finalize()
+        self._accum_done = False
 
     def _frobenius_of_current(self, rows=32768):
         """||X - G W H||_F^2 of the current state (espm/measures.py:350-384) into its history slot: residual in fp32 over
@@ -838,11 +871,11 @@ class MUEngine:
         st.cur, st.it = 1 - cur, slot + 1
 
     def _flush_finalize(self, tail=True):
-        pend = getattr(self, "_pending_finalize", None)
+        pend = self._pending_finalize
         if pend is not None:
             self._pending_finalize = None
             self._check(self.lib.espm_mu_h_finalize(C.byref(self.st), pend[0], pend[1], _stream()))
-        if tail and getattr(self, "_pending_tail", False):   # no H-step will carry the tail of the last W update: a launch of its own
+        if tail and self._pending_tail:   # no H-step will carry the tail of the last W update: a launch of its own
             self._pending_tail = False
             self._check(self.lib.espm_mu_w_update_tail(C.byref(self.st), 1 - self.st.cur, self.st.it - 1, _stream()))
 
@@ -858,35 +891,33 @@ class MUEngine:
         if not self._accum_done:   # (fused: the W accumulation of this H update rode in eval_current's launch, and h_t was not written)
             self._check(self.lib.espm_mu_w_accum(C.byref(st), s))
         self._accum_done = False
-        ride = getattr(self, "_pending_finalize", None) == (cur, slot)   # the H-step's record reduction rides along
+        ride = self._pending_finalize == (cur, slot)   # the H-step's record reduction rides along
         if ride:
             self._pending_finalize = None
         else:
             self._flush_finalize()
-        # sparse store, local W update: its tail is left to the next H-step's launch (eval_current) or to _flush_finalize
-        defer = (self.ell is not None and self.pg_q is None and bool(self.lib.espm_mu_w_update_is_local(C.byref(st))))
-        st.tail_mode = _lib.TAIL_DEFER if defer else 0
-        if self.sharded and self.exchange.ctx is not None and ride:
-            # one-shot transport, and the H-step's records are still the workspace's content (their reduction is pending): the
-            # library's exchange launch(es), as in the batch loop (espm_mu_iterate_sharded) - slab reduction, record reduction,
-            # granule exchange, W update.  (Once the records have been reduced, other launches may have reused the workspace -
-            # the projected gradient's linesearch evaluates a loss in between - and the pieces below carry the statistics along.)
-            self.exchange.seq.value += 1
-            self._check(self.lib.espm_mu_shard_exchange_finish(C.byref(st), self.exchange.ctx, self.exchange.seq, cur, slot, s))
-            self._set_halo_from_records()
-        elif self.sharded:
-            if ride:   # slab reduction + record reduction + this rank's record, one launch
-                self._check(self.lib.espm_mu_w_reduce_pack(C.byref(st), cur, slot, C.c_void_p(self.exchange.send_ptr), s))
+        defer = self._defers_tail()   # (its tail is left to the next H-step's launch - eval_current - or to _flush_finalize)
+        with self._tail_mode(_lib.TAIL_DEFER if defer else 0):
+            if self.sharded and self.exchange.ctx is not None and ride:
+                # one-shot transport, and the H-step's records are still the workspace's content (their reduction is pending): the
+                # library's exchange launch(es), as in the batch loop (espm_mu_iterate_sharded) - slab reduction, record reduction,
+                # granule exchange, W update.  (Once the records have been reduced, other launches may have reused the workspace -
+                # the projected gradient's linesearch evaluates a loss in between - and the pieces below carry the statistics along.)
+                self.exchange.seq.value += 1
+                self._check(self.lib.espm_mu_shard_exchange_finish(C.byref(st), self.exchange.ctx, self.exchange.seq, cur, slot, s))
+                self._set_halo_from_records()
+            elif self.sharded:
+                if ride:   # slab reduction + record reduction + this rank's record, one launch
+                    self._check(self.lib.espm_mu_w_reduce_pack(C.byref(st), cur, slot, C.c_void_p(self.exchange.send_ptr), s))
+                else:
+                    self._check(self.lib.espm_mu_w_reduce(C.byref(st), s))
+                    self._check(self.lib.espm_mu_shard_pack(C.byref(st), 1 - cur, C.c_void_p(self.exchange.send_ptr), s))
+                self.exchange.gather()
+                # sum over the ranks + W update (one launch when W' needs nothing global, include/espm_mu.h)
+                self._check(self.lib.espm_mu_shard_combine_finish(C.byref(st), C.c_void_p(self.exchange.recv_ptr), self.world, cur, slot, s))
+                self._set_halo_from_records()
             else:
-                self._check(self.lib.espm_mu_w_reduce(C.byref(st), s))
-                self._check(self.lib.espm_mu_shard_pack(C.byref(st), 1 - cur, C.c_void_p(self.exchange.send_ptr), s))
-            self.exchange.gather()
-            # sum over the ranks + W update (one launch when W' needs nothing global, include/espm_mu.h)
-            self._check(self.lib.espm_mu_shard_combine_finish(C.byref(st), C.c_void_p(self.exchange.recv_ptr), self.world, cur, slot, s))
-            self._set_halo_from_records()
-        else:
-            self._check(self.lib.espm_mu_w_reduce_finish(C.byref(st), cur, slot, int(ride), s))
-        st.tail_mode = 0
+                self._check(self.lib.espm_mu_w_reduce_finish(C.byref(st), cur, slot, int(ride), s))
         self._pending_tail = defer
         st.cur, st.it = 1 - cur, slot + 1
 
@@ -988,10 +1019,7 @@ class MUEngine:
     def iterate(self, n_iter, final_loss=True):
         """``n_iter`` iterations without host synchronisation (no stop criterion)."""
         st = self.st
-        if st.it + n_iter + 1 > self.hist_len:
-            raise ValueError("history buffer exhausted: raise max_iter")
-        self._flush_finalize()
-        self._accum_done = False   # (a pending fused H update is simply redone by the loop)
+        self._begin_batch(n_iter)
         if not self.sharded and not self.frobenius:
             self._check(self.lib.espm_mu_iterate(C.byref(st), int(n_iter), int(bool(final_loss)), _stream()))
         elif self.sharded and self.exchange.ctx is not None and not self.frobenius:
@@ -1006,12 +1034,12 @@ class MUEngine:
                 self.eval_current(False)
 
     # ---- H-only iterations: W held (what the reference computes with fixed_W = W, updates.py:75-76) ------------------------------
-    def _hold_w(self):
-        """Both W buffers hold the current W: st.cur flips with every H-only iteration as the index of the current H."""
+    def _hold_w(self, n_iter):
+        """Ahead of n_iter H-only iterations: both W buffers hold the current W (st.cur flips with every H-only iteration as the
+        index of the current H)."""
+        self._begin_batch(n_iter)
         if self.sharded or self.frobenius:
             raise NotImplementedError("H-only iterations: one GPU, not the Frobenius fit")
-        self._flush_finalize()
-        self._accum_done = False
         cur = self.st.cur
         self.w[1 - cur].copy_(self.w[cur])
 
@@ -1025,9 +1053,7 @@ class MUEngine:
         ``eval_current(advance_h=True)`` on the two-launch path, without the W step that would follow."""
         st = self.st
         cur, slot = st.cur, st.it
-        if slot + 1 >= self.hist_len:
-            raise ValueError("history buffer exhausted: raise max_iter")
-        self._hold_w()
+        self._hold_w(1)
         self._check(self.lib.espm_mu_step_h(C.byref(st), cur, 1, _stream()))
         self._check(self.lib.espm_mu_h_finalize(C.byref(st), cur, slot, _stream()))
         self.hist[slot + 1, _lib.HI_REL_W] = 0.0   # base.py:323 of an update that leaves W alone
@@ -1045,9 +1071,7 @@ class MUEngine:
         """``n_iter`` H-only iterations without host synchronisation (``espm_mu_iterate_h``: one launch per iteration where the
         chained H-step applies)."""
         st = self.st
-        if st.it + int(n_iter) + 1 > self.hist_len:
-            raise ValueError("history buffer exhausted: raise max_iter")
-        self._hold_w()
+        self._hold_w(n_iter)
         self._check(self.lib.espm_mu_iterate_h(C.byref(st), int(n_iter), int(bool(final_loss)), _stream()))
 
     def iterate_timed(self, n_iter):
@@ -1057,12 +1081,9 @@ class MUEngine:
         for the Frobenius fit.  Synchronises."""
         st = self.st
         n_iter = int(n_iter)
-        if st.it + n_iter + 1 > self.hist_len:
-            raise ValueError("history buffer exhausted: raise max_iter")
+        self._begin_batch(n_iter)
         if self.sharded or self.frobenius:
             raise NotImplementedError("iterate_timed: the unsharded multiplicative loop (timed_iterations serves a sharded engine)")
-        self._flush_finalize()
-        self._accum_done = False
         first, rest = (C.c_float * n_iter)(), (C.c_float * n_iter)()
         self._check(self.lib.espm_mu_iterate_timed(C.byref(st), n_iter, first, rest, _stream()))
         return np.array(first[:], dtype=np.float64) * 1e3, np.array(rest[:], dtype=np.float64) * 1e3
@@ -1074,47 +1095,21 @@ class MUEngine:
         slab reduction, the record exchange (this is where a rank WAITS for its peers) and the W update.  The same entry
         points, in the same order, as ``iterate`` (for the one-shot transport the two launches espm_mu_iterate_sharded
         enqueues per iteration), sequenced from Python; the events cost ~2 us per iteration."""
-        st = self.st
         n_iter = int(n_iter)
-        if st.it + n_iter + 1 > self.hist_len:
-            raise ValueError("history buffer exhausted: raise max_iter")
+        self._begin_batch(n_iter)
         if self.frobenius:
             raise NotImplementedError("timed_iterations: not for the Frobenius fit")
-        self._flush_finalize()
-        self._accum_done = False
-        s = _stream()
         ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(n_iter)]
         oneshot = self.sharded and self.exchange.ctx is not None
-        if oneshot:
-            defer = self.ell is not None and self.pg_q is None and bool(self.lib.espm_mu_w_update_is_local(C.byref(st)))
-            pending = False
-            for e0, e1, e2 in ev:
-                cur, slot = st.cur, st.it
-                st.tail_mode = _lib.TAIL_RIDE if pending else 0
-                e0.record()
-                try:
-                    self._check(self.lib.espm_mu_step_hw(C.byref(st), cur, s))
-                finally:
-                    st.tail_mode = 0
-                e1.record()
-                self.exchange.seq.value += 1
-                st.tail_mode = _lib.TAIL_DEFER if defer else 0
-                try:
-                    self._check(self.lib.espm_mu_shard_exchange_finish(C.byref(st), self.exchange.ctx, self.exchange.seq, cur, slot, s))
-                finally:
-                    st.tail_mode = 0
-                e2.record()
-                pending = defer
-                self._set_halo_from_records()
-                st.cur, st.it = 1 - cur, slot + 1
-            self._pending_tail = pending
-        else:
-            for e0, e1, e2 in ev:
-                e0.record()
+        for e0, e1, e2 in ev:
+            e0.record()
+            if oneshot:   # espm_mu_step_hw whether fused or not, so that espm_mu_shard_exchange_finish follows: the batch loop's two calls
+                self._advance_h(with_accum=True)
+            else:
                 self.eval_current(True)
-                e1.record()
-                self.finish_iteration()
-                e2.record()
+            e1.record()
+            self.finish_iteration()
+            e2.record()
         torch.cuda.synchronize()
         return (np.array([a.elapsed_time(b) * 1e3 for a, b, _ in ev]), np.array([b.elapsed_time(c) * 1e3 for _, b, c in ev]))
 
@@ -1131,9 +1126,8 @@ class MUEngine:
         if l2:  # Frobenius branch, updates.py:109-118
             work, scratch = self._l2_buffers()
             self._check(self.lib.espm_mu_l2_step_h(C.byref(st), st.cur, _ptr(work), _ptr(scratch), scratch.numel(), _stream()))
-            self._check(self.lib.espm_mu_h_finalize(C.byref(st), st.cur, st.it, _stream()))
-            return self._h_numpy(1 - st.cur)
-        self._check(self.lib.espm_mu_step_h(C.byref(st), st.cur, 1, _stream()))
+        else:
+            self._check(self.lib.espm_mu_step_h(C.byref(st), st.cur, 1, _stream()))
         self._check(self.lib.espm_mu_h_finalize(C.byref(st), st.cur, st.it, _stream()))
         return self._h_numpy(1 - st.cur)
 
