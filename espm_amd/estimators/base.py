@@ -19,8 +19,10 @@ from sklearn.utils.metaestimators import available_if
 from sklearn.utils.validation import check_is_fitted, validate_data
 
 from espm_amd.conf import log_shift
+from espm_amd.estimators import ingest
+from espm_amd.estimators.ingest import _DEVICE_PREP_MIN_SIZE, _HostCopy  # noqa: F401 - (their names before ingest.py, kept importable)
 from espm_amd.estimators.updates import initialize_algorithms
-from espm_amd.store import XFacts
+from espm_amd.sharding import FitShard as _Shard   # (its name while it lived here, kept importable)
 from espm_amd.utils import create_laplacian_matrix, identity_laplacian, rescaled_DH
 
 
@@ -30,281 +32,24 @@ def normalization_factor(X, nc):
     return nc / (m * X.shape[0])
 
 
-# X with at least this many entries is uploaded once and prepared on the device (see fit_transform)
-_DEVICE_PREP_MIN_SIZE = 4_000_000
-
-
 def _is_physical_model(G):
     return G is not None and not isinstance(G, np.ndarray) and hasattr(G, "NMF_update")
 
 
-def _upload_with_scans(host, device, log_shift):
-    """Uploads a C-contiguous host array in row chunks and has the device scan every chunk while the next one is on the bus: the
-    passes the reference makes over X before its loop (finiteness - validate_data was told to skip it -, sign, line sums for the
-    empty-line test base.py:519-528, the mean for `normalize`, const_KL_ = sum(X log X - X) in fp64, base.py:200-201) cost 16 ms
-    as passes over the uploaded image; behind the 38 ms upload (a blocking copy from pageable memory per chunk, the device idle
-    otherwise) they cost nothing.  Returns the device array and the scans' results as device tensors (nothing is read back here):
-    row_sum / col_sum of the array as it lies in memory, `bad` = [non-finite entries, NaNs, negative entries], s1 = sum x and
-    s2 = sum x log(max(x, log_shift)), both fp64; `facts` = [entries that are not integers, non-zero entries, largest entry]."""
-    import threading
-    import torch
-    rows, cols = host.shape
-    out = torch.empty(host.shape, dtype=torch.from_numpy(host[:0]).dtype, device=device)
-    # 128 MB chunks, the last one halved down to 32 MB: the scans of the LAST chunk are what the fit waits for after the bus has
-    # gone quiet - 3.3 ms behind 256 MB chunks, 1.4 behind 128, 0.3 behind 32, while many small chunks cost the bus a little
-    # (upload 40.2 ms in 256 MB chunks, 41.2 in 32 MB ones; profiles/r05z_fit_timing_chunk*.log)
-    row_bytes = max(1, cols * host.itemsize)
-    step = max(1, (int(os.environ.get("ESPM_UPLOAD_CHUNK_MB", "128")) << 20) // row_bytes)
-    f64 = dict(dtype=torch.float64, device=device)
-    row_sum = torch.empty(rows, **f64)
-    col_sum = torch.zeros(cols, **f64)
-    bad = torch.zeros(3, dtype=torch.int64, device=device)
-    s1, s2 = torch.zeros((), **f64), torch.zeros((), **f64)
-    facts = torch.zeros(3, **f64)                                # entries that are not integers, non-zero entries, the largest entry
-    chunks = [(a, min(rows, a + step)) for a in range(0, rows, step)]
-    small = max(1, (32 << 20) // row_bytes)
-    while len(chunks) > 1 and chunks[-1][1] - chunks[-1][0] >= 2 * small and os.environ.get("ESPM_UPLOAD_TAIL", "1") != "0":
-        a, b = chunks.pop()
-        mid = a + (b - a + 1) // 2
-        chunks += [(a, mid), (mid, b)]       # (the first half stays as it is, the second is looked at again)
-    # the copies go back to back from a thread of their own (a blocking copy from pageable memory per chunk, the GIL released
-    # inside it); this thread queues the scans of a chunk as soon as it has arrived
-    main = torch.cuda.current_stream(device)
-    side = torch.cuda.Stream(device=device)
-    side.wait_stream(main)                                        # (the allocator may hand out memory with work still queued on it)
-    arrived = [threading.Event() for _ in chunks]
-    done = [torch.cuda.Event() for _ in chunks]
-    err = []
-
-    def copier():
-        try:
-            with torch.cuda.stream(side):
-                for i, (a, b) in enumerate(chunks):
-                    out[a:b].copy_(torch.from_numpy(host[a:b]))
-                    done[i].record(side)
-                    arrived[i].set()
-        except BaseException as e:   # noqa: BLE001 - re-raised below
-            err.append(e)
-            for ev in arrived:
-                ev.set()
-    th = threading.Thread(target=copier, daemon=True)
-    th.start()
-    for i, (a, b) in enumerate(chunks):
-        arrived[i].wait()
-        if err:
-            break
-        main.wait_event(done[i])
-        x = out[a:b]
-        fin = torch.isfinite(x)
-        bad += torch.stack(((~fin).sum(), torch.isnan(x).sum(), (x < 0).sum()))
-        xd = x.to(torch.float64)
-        rs = xd.sum(dim=1)
-        row_sum[a:b] = rs
-        col_sum += xd.sum(dim=0)
-        s1 += rs.sum()
-        s2 += (xd * torch.log(xd.clamp_min(log_shift))).sum()
-        # (what the engine's choice of a store asks of X - integer counts up to 255, how many non-zero: store.XFacts - while the data pass by)
-        facts[:2] += torch.stack(((x != x.round()).sum(), (x != 0).sum())).to(torch.float64)
-        facts[2] = torch.maximum(facts[2], x.max().to(torch.float64))
-        del x, fin, xd, rs
-    th.join()
-    if err:
-        raise err[0]
-    return out, dict(row_sum=row_sum, col_sum=col_sum, bad=bad, s1=s1, s2=s2, facts=facts)
-
-
-class _HostCopy:
-    """``X_`` of a large fit in the making.  The reference keeps its own copy of the data (remove_zeros_lines copies,
-    base.py:519-528; normalize scales it, base.py:264-267): at 2048 x 512^2 fp32 those host passes are 0.2-0.4 s of a fit whose
-    200 iterations take 0.03 s.  They run on worker threads (numpy releases the GIL) while the device initialises and
-    iterates; the fit joins them at its end.  Until then this object stands in for the array: shape and dtype are known at once,
-    anything else (``__array__``, ``.T``, indexing ...) waits for the copy.
-
-    ``finish`` hands over what the device scans found, ``start`` lets the copy run - ONE pass over row blocks on a few threads:
-    copy, scale, fill - behind the upload (overlapping the upload the two halved each other's host bandwidth)."""
-
-    THREADS = 4
-
-    class _State:   # what the worker holds (not the stand-in itself: a stand-in nobody references any more lets its worker go)
-        __slots__ = ("src", "layout", "params", "go", "out", "err")
-
-    def __init__(self, src, layout):
-        import threading
-        self.shape, self.dtype, self.size, self.ndim = src.shape, src.dtype, src.size, src.ndim
-        st = self._st = _HostCopy._State()
-        st.src, st.layout = src, layout
-        st.params = None            # (pixel mask, channel mask, fill, scale), set by finish()
-        st.go, st.out, st.err = threading.Event(), None, None
-        self._thread = threading.Thread(target=_HostCopy._run, args=(st,), daemon=True)
-        self._thread.start()
-
-    def __del__(self):
-        st = self.__dict__.get("_st")
-        if st is not None and not st.go.is_set():   # never started (a fit that raised before its loop): nothing to copy for
-            st.params = None
-            st.go.set()
-
-    @staticmethod
-    def _run(st):
-        import threading
-        try:
-            st.go.wait()
-            if st.params is None:   # cancelled
-                st.src = None
-                return
-            zp, zc, fill, scale = st.params
-            # the memory as it lies (for a pixel-major input: its transposed view), not a strided gather
-            src = st.src if st.layout == "cm" else st.src.T
-            st.src = None
-            base = np.empty(src.shape, dtype=src.dtype)
-            row_mask, col_mask = (zc, zp) if st.layout == "cm" else (zp, zc)   # masks over the rows / columns of `base`
-            # an empty line holds fill, then everything is scaled (base.py:519-528, :264-267): fill * scale in the array's precision
-            filled = None
-            if zp is not None:
-                filled = np.full(1, fill, dtype=src.dtype)
-                if scale is not None:
-                    np.multiply(filled, scale, out=filled)
-            errs = []
-
-            def block(a, b):
-                try:
-                    if scale is not None:
-                        np.multiply(src[a:b], scale, out=base[a:b])
-                    else:
-                        np.copyto(base[a:b], src[a:b])
-                    if filled is not None:
-                        base[a:b][:, col_mask] = filled[0]
-                        base[a:b][row_mask[a:b]] = filled[0]
-                except BaseException as e:  # noqa: BLE001
-                    errs.append(e)
-
-            nt = max(1, min(_HostCopy.THREADS, src.shape[0]))
-            edges = np.linspace(0, src.shape[0], nt + 1).astype(int)
-            helpers = [threading.Thread(target=block, args=(int(edges[i]), int(edges[i + 1])), daemon=True) for i in range(1, nt)]
-            for t in helpers:
-                t.start()
-            block(int(edges[0]), int(edges[1]))
-            for t in helpers:
-                t.join()
-            if errs:
-                raise errs[0]
-            st.out = base if st.layout == "cm" else base.T
-        except BaseException as e:  # noqa: BLE001 - re-raised by result()
-            st.err = e
-
-    def finish(self, zp=None, zc=None, fill=None, scale=None):
-        """What the device scans found: empty pixels / channels to fill (base.py:519-528), the normalisation factor."""
-        self._st.params = (zp, zc, fill, scale)
-
-    def start(self):
-        """Lets the copy run (once the upload is through and the scans of X have said what to fill; at the latest when the fit
-        enters its iteration loop)."""
-        self._st.go.set()
-
-    def cancel(self):
-        self._st.params = None
-        self._st.go.set()
-
-    def result(self):
-        self._st.go.set()   # (asked for before the loop - e.g. a least-squares initialisation reads X_ - or never started)
-        self._thread.join()
-        if self._st.err is not None:
-            raise self._st.err
-        return self._st.out
-
-    def __array__(self, dtype=None, copy=None):
-        out = self.result()
-        return out if dtype is None else out.astype(dtype, copy=False)
-
-    def __getattr__(self, name):   # (only reached for what the stand-in does not have: .T, .sum, ...)
-        if name.startswith("_"):
-            raise AttributeError(name)
-        return getattr(self.result(), name)
-
-    def __getitem__(self, key):
-        return self.result()[key]
-
-
-class _Shard:
-    """Pixel-row sharding of ONE fit over the ranks of a process group (espm_amd/sharding.py): every rank
-    runs the same script on the same X; its engine holds a contiguous block of image rows (X and H sharded, W / G replicated)
-    and the results are assembled on every rank."""
-
-    def __init__(self, group, shape_2d, p):
-        import torch.distributed as dist
-        from espm_amd.sharding import split_rows
-        self.group, self.world, self.rank = group, dist.get_world_size(group), dist.get_rank(group)
-        self.src = dist.get_global_rank(group, 0)
-        if shape_2d is not None:
-            nx, ny = int(shape_2d[0]), int(shape_2d[1])
-            if nx * ny != p:
-                raise ValueError(f"shape_2d {shape_2d} does not match the {p} pixels of X")
-            blocks = [split_rows(nx, self.world, r) for r in range(self.world)]
-            self.counts = [rows * ny for _, rows in blocks]
-            row0, rows = blocks[self.rank]
-            self.sl, self.shape_2d = slice(row0 * ny, (row0 + rows) * ny), (rows, ny)
-        else:   # no image grid (L = identity, base.py:289-291): any contiguous split of the pixels
-            blocks = [split_rows(p, self.world, r) for r in range(self.world)]
-            self.counts = [rows for _, rows in blocks]
-            row0, rows = blocks[self.rank]
-            self.sl, self.shape_2d = slice(row0, row0 + rows), None
-
-    def combine_scans(self, scans, layout):
-        """The upload's scans of this rank's block (_upload_with_scans) turned into the image's: counts and sums added over the
-        ranks, the largest entry their maximum, the channel sums added (the rows of the array as it lies in the channel-major
-        layout, its columns in the pixel-major one); the pixel sums stay the block's."""
-        import torch
-        dist = torch.distributed
-        ch = "row_sum" if layout == "cm" else "col_sum"
-        vec = torch.cat((scans["bad"].to(torch.float64), scans["s1"].view(1), scans["s2"].view(1), scans["facts"][:2]))
-        dist.all_reduce(vec, group=self.group)
-        xmax = scans["facts"][2:3].clone()
-        dist.all_reduce(xmax, op=dist.ReduceOp.MAX, group=self.group)
-        chs = scans[ch].clone()
-        dist.all_reduce(chs, group=self.group)
-        out = dict(scans)
-        out["bad"] = vec[:3].round().to(torch.int64)
-        out["s1"], out["s2"] = vec[3], vec[4]
-        out["facts"] = torch.cat((vec[5:7], xmax))
-        out[ch] = chs
-        return out
-
-    def agree(self, ok, what, err=None):
-        """Every rank learns whether every rank succeeded (all-reduce MIN of a flag) before anybody raises: the failing rank re-raises
-        its own exception, the others a RuntimeError naming the step - nobody is left in the next collective waiting for a rank that
-        has gone."""
-        import torch
-        dev = f"cuda:{torch.cuda.current_device()}" if torch.distributed.get_backend(self.group) != "gloo" else "cpu"
-        flag = torch.tensor([1 if ok else 0], dtype=torch.int32, device=dev)
-        torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN, group=self.group)
-        if err is not None:
-            raise err
-        if int(flag.item()) == 0:
-            raise RuntimeError(f"sharded fit: {what} failed on another rank")
-
-    def cols(self, a):
-        """This rank's columns of an (.., p) array (None stays None)."""
-        return None if a is None else a[..., self.sl]
-
-    def broadcast(self, arrays, device):
-        """Rank 0's arrays on every rank (the initial W, H, G: bit-identical starts whatever the ranks' own init gave)."""
-        import torch
-        out = []
-        for a in arrays:
-            t = torch.from_numpy(np.ascontiguousarray(a)).to(device)
-            torch.distributed.broadcast(t, src=self.src, group=self.group)
-            out.append(t.cpu().numpy())
-        return out
-
-    def gather_cols(self, local):
-        """(k, p) numpy array from every rank's (k, p_local) device tensor, in rank order."""
-        import torch
-        width = max(self.counts)
-        mine = torch.zeros((local.shape[0], width), dtype=local.dtype, device=local.device)
-        mine[:, :local.shape[1]] = local
-        parts = [torch.empty_like(mine) for _ in range(self.world)]
-        torch.distributed.all_gather(parts, mine, group=self.group)
-        return np.concatenate([part[:, :c].cpu().numpy() for part, c in zip(parts, self.counts)], axis=1)
+def stop_message(rel_W, rel_H, eval_before, eval_after, eval_init, tol):
+    """The stop rules of the reference's loop (base.py:354-378) in its order - relative change of W and H, relative change of the loss, NaN,
+    a loss that went up - with the message the reference prints, or None while none of them holds.  (The iteration limit, and who prints,
+    are the loop's.)"""
+    decrease = eval_before - eval_after
+    if max(rel_H, rel_W) < tol:
+        return "exits because of relative change rel_A {} and rel_P {} < tol ".format(rel_H, rel_W)
+    if abs(decrease / eval_init) < tol:
+        return "exits because of relative change < tol: {}".format(decrease / eval_init)
+    if np.isnan(eval_after):
+        return "exit because of the presence of NaN"
+    if decrease < 0:
+        return "exit because of negative decrease {}: {}, {}".format(decrease, eval_before, eval_after)
+    return None
 
 
 def _rows_are_pixels(est):
@@ -433,7 +178,7 @@ class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
     # ---- loss -----------------------------------------------------------------------------------------
     def _make_engine(self, X_fixed, xscale, G, filled_channels=None, filled_pixels=None, layout="cm", autotune=False, shard=None, x_facts=None,
                      x_local=False):
-        """The device engine of a fit; with ``shard`` (a _Shard) X_fixed is the WHOLE image and the engine takes this rank's
+        """The device engine of a fit; with ``shard`` (a sharding.FitShard) X_fixed is the WHOLE image and the engine takes this rank's
         block of it - or, with ``x_local``, that block already (then ``filled_pixels`` is the block's mask too)."""
         from espm_amd.engine import MUEngine
         shape_2d, fixed_H, group = self.shape_2d, self.fixed_H, None
@@ -536,16 +281,8 @@ class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
                 raise NotImplementedError(f"fp64 mode (set_precision('fp64')) does not cover {why}")
         marks = [("enter", time.perf_counter())] if os.environ.get("ESPM_FIT_TIMING") else None
         mark = (lambda name: marks.append((name, time.perf_counter()))) if marks is not None else (lambda name: None)
-        big = False
-        try:
-            import torch
-            big = (hasattr(X, "shape") and getattr(X, "ndim", 0) == 2 and int(np.prod(X.shape)) >= _DEVICE_PREP_MIN_SIZE
-                   and getattr(X, "dtype", None) in (np.float32, np.float64) and torch.cuda.is_available() and not self._fp64())
-        except Exception:
-            big = False
-        vkw = dict(dtype=[np.float64, np.float32])
-        if big:
-            vkw["ensure_all_finite"] = False
+        big = ingest.device_prep_applies(X, self._fp64())
+        vkw = dict(dtype=[np.float64, np.float32], ensure_all_finite=not big)
         if self.hspy_comp:
             Xv = validate_data(self, X.T, **vkw)
         else:
@@ -577,18 +314,7 @@ class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
 
     def _fit_ingest(self, f):
         """base.py:261-268, :519-528, :200-201: sign check, zero lines, mean / normalisation, X_, const_KL_ - for a large X on ONE device copy (a sharded fit: on this rank's block, scans combined over the ranks)."""
-        Xv, big, mark = f.Xv, f.big, f.mark
-
-        # Large X: ONE upload; the passes the reference makes over X on the host before the loop (sign check, zero
-        # lines base.py:519-528, mean for normalize, const_KL_ base.py:200-201, the NNDSVD's products) run on that
-        # device copy, which then feeds the engine.  Small X: the host path, like the reference.
-        # A (pixels, channels) array - what hyperspy's decomposition hands over, hspy_comp=True - is uploaded AS IT IS
-        # (pixel-major is also the layout the engine ingests natively: no host transpose, no device transpose); Xd below
-        # is the logical (n, p) view of the device copy either way.
-        Xd = Xd_raw = None
-        x_facts = None   # (large X on the device: what the upload's scans found out about it, for the engine)
-        dev_layout = "cm"
-        lazy = None    # the estimator's own host copy X_ of a large X, made on a worker thread (_HostCopy)
+        Xv, mark = f.Xv, f.mark
         # one fit over several GPUs (shard()): decided BEFORE the upload, so that a large X goes to the device as this rank's block
         # of image rows only - its scans are combined over the ranks, the initialisation's passes run on the blocks
         # (espm_amd/init_device.py), the engine takes the block as it is.  Set-up time and device memory per rank shrink with the
@@ -599,137 +325,47 @@ class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
             import torch
             if torch.distributed.get_world_size(grp) > 1:
                 shard = _Shard(grp, self.shape_2d, int(Xv.shape[1]))
-        x_local = False   # Xd_raw is this rank's block (sharded fit of a large X)
-        # (fp64 mode: the host passes of the reference, in the array's own dtype; the engine takes X_fixed and uploads it)
-        if Xv.size >= _DEVICE_PREP_MIN_SIZE and not self._fp64():
-            import torch
-            if torch.cuda.is_available():
-                if Xv.flags.c_contiguous:
-                    host = Xv
-                elif Xv.T.flags.c_contiguous:
-                    host, dev_layout = Xv.T, "pm"
-                else:
-                    host = np.ascontiguousarray(Xv)
-                lazy = _HostCopy(Xv, dev_layout)
-                try:
-                    mark("host copy thread created")
-                    if shard is not None:
-                        x_local = True
-                        # (pixel-major: the block is a run of rows of the array as it lies; channel-major: a strided copy of 1 / world of it)
-                        host = host[shard.sl] if dev_layout == "pm" else np.ascontiguousarray(host[:, shard.sl])
-                    upload_err = None
-                    try:
-                        Xd_raw, scans = _upload_with_scans(host, torch.device("cuda", torch.cuda.current_device()), self.log_shift)
-                    except Exception as e:   # noqa: BLE001 - (out of memory, a bad block): decided jointly below
-                        upload_err = e
-                    if shard is not None:
-                        # a rank that fails HERE must not leave its peers waiting in the scans' all-reduce: the ranks agree first
-                        shard.agree(upload_err is None, "the upload of this rank's block of X", upload_err)
-                    elif upload_err is not None:
-                        raise upload_err
-                    if shard is not None:
-                        scans = shard.combine_scans(scans, dev_layout)
-                    mark("upload returned")
-                    Xd = Xd_raw if dev_layout == "cm" else Xd_raw.t()
-                    n_bad, n_nan, n_neg = (int(v) for v in scans["bad"].cpu())
-                    if big and n_bad:   # the scan validate_data was told to skip, same message
-                        raise ValueError(f"Input X contains {'NaN' if n_nan else 'infinity'}.")
-                    if n_neg:
-                        raise ValueError("Negative values in data")
-                except BaseException:
-                    lazy.cancel()
-                    raise
-        mark("finite / sign checks read back")
-        if big and Xd is None:   # (no device after all: scikit-learn's own check)
-            from sklearn.utils import assert_all_finite
-            assert_all_finite(Xv, input_name="X")
-        self.const_KL_ = None
-        xscale = 1.0
-        # (channels / pixels without a single count in the image: the engine's sparse store leaves their fill out of its lists)
-        if Xd is None:
-            X_fixed = self.remove_zeros_lines(Xv, self.log_shift)
-            mean_x = None
-            empty_ch, empty_px = Xv.sum(axis=1) == 0, Xv.sum(axis=0) == 0
+        # Large X: ONE upload whose scans stand for the reference's host passes (ingest_device).  Small X, fp64 mode: the host path, like the
+        # reference.  (The validated array is float and 2-D: its size decides; the finiteness scan is owed only where validate_data skipped it.)
+        if ingest.device_prep_applies(Xv, self._fp64()):
+            rec = ingest.ingest_device(Xv, self.log_shift, shard=shard, check_finite=f.big, keep_host_copy=True, mark=mark)
         else:
-            try:
-                # (the line sums of the array as it lies in memory, from the upload's scans: channels are its rows in the "cm" layout)
-                # (sharded: the channel sums are the image's, the pixel sums this rank's block's)
-                zc, zp = ((scans["row_sum"] == 0, scans["col_sum"] == 0) if dev_layout == "cm"
-                          else (scans["col_sum"] == 0, scans["row_sum"] == 0))
-                empty_ch, empty_px = zc, zp
-                n_zero_px = zp.sum().to(torch.float64)
-                if x_local:
-                    torch.distributed.all_reduce(n_zero_px, group=shard.group)
-                n_zero_lines, s1, n_nonint, nnz, x_max = (float(v) for v in torch.cat((torch.stack((n_zero_px + zc.sum(), scans["s1"])),
-                                                                                             scans["facts"])).cpu())
-                numel = float(Xv.size)
-                fill = n_zero_lines > 0
-                if not fill and not x_local:   # what the scans know about X as it goes to the engine (a filled X is another array: the engine looks itself)
-                    x_facts = XFacts(nonneg=True, sum_x=s1, is_int=bool(n_nonint == 0), x_max=x_max, nnz=int(nnz))
-                if fill:
-                    Xd[:, zp] = self.log_shift
-                    Xd[zc, :] = self.log_shift
-                    total = Xd.sum(dtype=torch.float64)
-                    if x_local:
-                        torch.distributed.all_reduce(total, group=shard.group)
-                    mean_x = float(total) / numel
-                else:
-                    mean_x = s1 / numel
-            except BaseException:   # (the worker must not wait for a finish() that will not come)
-                lazy.cancel()
-                raise
-            # X_ is the estimator's own array, like the reference's (remove_zeros_lines copies): the worker thread that is
-            # copying it now fills the empty lines and applies the normalisation
-            X_fixed = lazy
-        mark("empty lines, mean read back")
+            mark("finite / sign checks read back")
+            rec = ingest.ingest_host(Xv, self.log_shift, self.remove_zeros_lines)
+            mark("empty lines, mean read back")
+        self.const_KL_ = None
+        xscale, x_init = 1.0, None   # (x_init: the device image as the initialisation and the loop see it; None on the host path)
         if self.normalize:
-            self.norm_factor_ = (normalization_factor(X_fixed, self.n_components) if mean_x is None
-                                 else self.n_components / (mean_x * X_fixed.shape[0]))
+            self.norm_factor_ = (normalization_factor(rec.X_fixed, self.n_components) if rec.mean_x is None
+                                 else self.n_components / (rec.mean_x * Xv.shape[0]))
             xscale = float(self.norm_factor_)
-        if lazy is not None:
-            zp_all = zp
-            if fill and x_local:   # (the host copy is the whole image: it fills the empty pixels of every rank's block)
-                zp_all = torch.from_numpy(shard.gather_cols(zp.to(torch.uint8)[None, :])[0].astype(bool))
-            lazy.finish(zp_all.cpu().numpy() if fill else None, zc.cpu().numpy() if fill else None, self.log_shift,
+        if rec.lazy is not None:   # the estimator's own host copy X_ of a large X, made on a worker thread (ingest._HostCopy)
+            # X_ is the estimator's own array, like the reference's (remove_zeros_lines copies): the worker thread fills the empty
+            # lines and applies the normalisation
+            zp_all = rec.empty_px
+            if rec.fill and rec.x_local:   # (the host copy is the whole image: it fills the empty pixels of every rank's block)
+                import torch
+                zp_all = torch.from_numpy(shard.gather_cols(zp_all.to(torch.uint8)[None, :])[0].astype(bool))
+            rec.lazy.finish(zp_all.cpu().numpy() if rec.fill else None, rec.empty_ch.cpu().numpy() if rec.fill else None, self.log_shift,
                         self.norm_factor_ if self.normalize else None)
-            self.X_ = lazy
+            self.X_ = rec.lazy
             # the copy runs from here on - behind the upload, next to the initialisation, the engine set-up and the loop (~120 ms
             # for its ~45): joined at the end of the fit it has long finished.  (Rounds 2-3 started it at the loop, because
             # started earlier it "stalled" whatever phase it overlapped: that was the container's CPU quota, _cpu_budget.py.
             # ESPM_HOSTCOPY_START=loop restores that; profiles/r03ac_fit_timing_*.log.)
             if os.environ.get("ESPM_HOSTCOPY_START", "early") == "early":
-                lazy.start()
+                rec.lazy.start()
+            x_init = rec.Xd * xscale if self.normalize else rec.Xd
+            rec = rec._replace(const_kl=ingest.const_kl_device(rec, x_init, self.normalize, self.log_shift, shard))
         else:
-            self.X_ = self.norm_factor_ * X_fixed if self.normalize else X_fixed
-        X_init_dev = None
-        if Xd is not None:
-            X_init_dev = Xd * xscale if self.normalize else Xd
-        if Xd is not None and not fill and not self.normalize:
-            # const_KL_ = sum(X log X - X) (base.py:200-201): both sums came with the upload
-            self._const_KL_dev = float(scans["s2"]) - s1
-        elif Xd is not None:
-            # (lines filled or the image rescaled: the sums belong to another array)  In fp64, in row chunks of 64 M entries: in one
-            # piece its fp64 copy and the three temporaries of the expression were 17 GB next to a 2 GB image
-            rows_of = X_init_dev if X_init_dev.is_contiguous() else X_init_dev.t()   # (the orientation the memory lies in)
-            step = max(1, (64 << 20) // max(1, int(rows_of.shape[1])))
-            total = torch.zeros((), dtype=torch.float64, device=rows_of.device)
-            for a in range(0, int(rows_of.shape[0]), step):
-                xs = rows_of[a:a + step].to(torch.float64)
-                total += (xs * torch.log(xs.clamp_min(self.log_shift))).sum() - xs.sum()
-            if x_local:
-                torch.distributed.all_reduce(total, group=shard.group)
-            self._const_KL_dev = float(total)
-            del xs, rows_of
-
+            self.X_ = self.norm_factor_ * rec.X_fixed if self.normalize else rec.X_fixed
         mark("const_KL read back")
-        f.Xd, f.Xd_raw, f.x_facts, f.dev_layout, f.lazy, f.shard, f.x_local = Xd, Xd_raw, x_facts, dev_layout, lazy, shard, x_local
-        f.xscale, f.X_fixed, f.mean_x, f.empty_ch, f.empty_px, f.X_init_dev = xscale, X_fixed, mean_x, empty_ch, empty_px, X_init_dev
-        f.fill = bool(fill) if Xd is not None else False
+        f.rec, f.shard, f.xscale, f.x_init = rec, shard, xscale, x_init
 
     def _fit_initial_state(self, f, W, H):
         """base.py:269-295 with updates.py:160-223: the physics model's G, W0 / H0 (NNDSVD on the device for a large X), rank 0's arrays on every rank of a sharded fit."""
-        mark, shard, x_local, Xd, xscale, mean_x, X_init_dev = f.mark, f.shard, f.x_local, f.Xd, f.xscale, f.mean_x, f.X_init_dev
-        f.X_init_dev = None
+        mark, shard, rec, X_init_dev = f.mark, f.shard, f.rec, f.x_init
+        f.x_init = None
         if _is_physical_model(self.G):
             self.physics_model_ = self.G
             G = self.physics_model_.NMF_update()
@@ -744,9 +380,9 @@ class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
                                                           init=self.init, random_state=self.random_state,
                                                           simplex_H=self.simplex_H, simplex_W=self.simplex_W,
                                                           physics_model=self.physics_model_, X_device=X_init_dev,
-                                                          shard=shard if x_local else None,   # (X_device is this rank's block of pixels)
+                                                          shard=shard if rec.x_local else None,   # (X_device is this rank's block of pixels)
                                                           # (the mean of what the initialisation sees: known from the upload's scans)
-                                                          X_mean=(mean_x * xscale if (Xd is not None and mean_x is not None) else None))
+                                                          X_mean=None if rec.mean_x is None else rec.mean_x * f.xscale)
         del X_init_dev
         mark("initialize_algorithms")
         # one fit over several GPUs (shard()): this rank's block of image rows; every rank starts from rank 0's W, H, G
@@ -766,21 +402,21 @@ class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
 
     def _fit_engine(self, f):
         """The device engine of the fit with its state loaded (a sharded fit: the record exchange rehearsed), const_KL_."""
-        mark, shard, x_local, Xd, Xd_raw, X_fixed, xscale, fill, Xv = f.mark, f.shard, f.x_local, f.Xd, f.Xd_raw, f.X_fixed, f.xscale, f.fill, f.Xv
-        empty_ch, empty_px, dev_layout, x_facts = f.empty_ch, f.empty_px, f.dev_layout, f.x_facts
-        f.Xd = f.Xd_raw = f.X_fixed = None   # (the context must not keep the device copies of X alive past the engine's build)
-        no_fill = Xd is not None and not fill      # (known from the upload's scans: no read-back to ask again)
-        self._engine = eng = self._make_engine(X_fixed if Xd is None else Xd_raw, xscale, None if self._identity_G else self.G_,
-                                                filled_channels=None if no_fill or not bool(empty_ch.any()) else empty_ch,
-                                                filled_pixels=None if no_fill or not bool(empty_px.any()) else empty_px, layout=dev_layout,
-                                                x_facts=x_facts,
+        mark, shard, rec = f.mark, f.shard, f.rec
+        f.rec = rec.without_x()   # (the context must not keep the device copies of X alive past the engine's build)
+        on_device = rec.Xd_raw is not None
+        # (the masks are passed where the upload's scans - or the host's sums - found lines to fill: no read-back to ask again)
+        self._engine = eng = self._make_engine(rec.Xd_raw if on_device else rec.X_fixed, f.xscale, None if self._identity_G else self.G_,
+                                                filled_channels=rec.empty_ch if rec.fill and bool(rec.empty_ch.any()) else None,
+                                                filled_pixels=rec.empty_px if rec.fill and bool(rec.empty_px.any()) else None, layout=rec.layout,
+                                                x_facts=rec.x_facts,
                                                 # (timing the launch plans costs ~30 ms of device time and gains a few per cent
                                                 #  per iteration: it pays for itself only in very long fits of large images)
-                                                autotune="auto" if Xd is not None else False,   # (MUEngine: from AUTOTUNE_MIN_ITERS iterations on)
-                                                shard=shard, x_local=x_local)
-        self._ingest_layout = dev_layout   # "pm": the (pixels, channels) input went to the device without a transpose
+                                                autotune="auto" if on_device else False,   # (MUEngine: from AUTOTUNE_MIN_ITERS iterations on)
+                                                shard=shard, x_local=rec.x_local)
+        self._ingest_layout = rec.layout   # "pm": the (pixels, channels) input went to the device without a transpose
         mark("engine built")
-        del X_fixed, Xd, Xd_raw
+        del rec
         mark("device copies of X released")
         eng.load_state(self.W_, self.H_ if shard is None else shard.cols(self.H_))
         if shard is not None and getattr(eng, "sharded", False) and eng.exchange.ctx is not None:
@@ -789,17 +425,16 @@ class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
             eng.settle_exchange()
             eng.load_state(self.W_, shard.cols(self.H_))
         self.GWH_numel_ = self.G_.shape[0] * self.H_.shape[1]
-        self.const_KL_ = (getattr(self, "_const_KL_dev", None) if Xv.size >= _DEVICE_PREP_MIN_SIZE else None)
+        self.const_KL_ = f.rec.const_kl   # (computed on the device copy of a large X)
         if self.const_KL_ is None:
             self.const_KL_ = float(np.sum(self.X_ * np.log(np.maximum(self.X_, self.log_shift))) - np.sum(self.X_))
-        self._const_KL_dev = None
 
         mark("state loaded, const_KL")
         return eng
 
     def _fit_loop(self, f, eng):
         """base.py:313-394: the iterations, the bookkeeping of every one of them and the stop rules; a sharded fit that loses a peer restarts once on the collective transport."""
-        mark, shard, lazy, say, out_dtype = f.mark, f.shard, f.lazy, f.say, f.out_dtype
+        mark, shard, lazy, say, out_dtype = f.mark, f.shard, f.rec.lazy, f.say, f.out_dtype
         algo_start = time.time()
         self.n_iter_ = 0
         self._begin_fit()
@@ -862,20 +497,10 @@ class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
                         if self.n_iter_ >= self.max_iter:  # base.py:354-378
                             say("exits because max_iteration was reached")
                             break
-                        if not self.no_stop_criterion:
-                            if max(rel_H, rel_W) < self.tol:
-                                say("exits because of relative change rel_A {} and rel_P {} < tol ".format(rel_H, rel_W))
-                                break
-                            elif abs((eval_before - eval_after) / eval_init) < self.tol:
-                                say("exits because of relative change < tol: {}".format((eval_before - eval_after) / eval_init))
-                                break
-                            elif np.isnan(eval_after):
-                                say("exit because of the presence of NaN")
-                                break
-                            elif (eval_before - eval_after) < 0:
-                                say("exit because of negative decrease {}: {}, {}".format((eval_before - eval_after),
-                                                                                             eval_before, eval_after))
-                                break
+                        why = None if self.no_stop_criterion else stop_message(rel_W, rel_H, eval_before, eval_after, eval_init, self.tol)
+                        if why is not None:
+                            say(why)
+                            break
                         if self.verbose > 0 and np.mod(self.n_iter_, self.eval_print) == 0:
                             say(f"It {self.n_iter_} / {self.max_iter}: loss {eval_after:3e},  "
                                   f"{self.n_iter_ / (time.time() - algo_start + log_shift):0.3f} it/s")
@@ -1030,19 +655,11 @@ class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
 
     def _transform_validate(self, t, X, shape_2d):
         """scikit-learn's validation against the fitted channel count (reset=False), the grid of the new pixels."""
-        big = False
-        try:
-            import torch
-            big = (hasattr(X, "shape") and getattr(X, "ndim", 0) == 2 and int(np.prod(X.shape)) >= _DEVICE_PREP_MIN_SIZE
-                   and getattr(X, "dtype", None) in (np.float32, np.float64) and torch.cuda.is_available())
-        except Exception:
-            big = False
+        big = ingest.device_prep_applies(X, False)   # (fp64 mode was refused before)
         # (scikit-learn counts the PIXELS as features here, base.py:243-247: the new data may have another number of them, so the
         #  array is checked as in the fit but not against n_features_in_)
         from sklearn.utils.validation import check_array
-        vkw = dict(dtype=[np.float64, np.float32])
-        if big:
-            vkw["ensure_all_finite"] = False
+        vkw = dict(dtype=[np.float64, np.float32], ensure_all_finite=not big)
         Xv = check_array(X.T if self.hspy_comp else X, **vkw)
         if Xv.shape[0] != self.G_.shape[0]:
             raise ValueError(f"X has {Xv.shape[0]} channels, the fitted G_ has {self.G_.shape[0]}")
@@ -1058,54 +675,27 @@ class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
     def _transform_ingest(self, t):
         """_fit_ingest for data that is not kept: sign check and empty lines (base.py:519-528) on the host, or for a large X on its ONE
         device copy by the upload's scans; the fit's norm_factor_."""
-        Xv = t.Xv
         t.xscale = float(self.norm_factor_) if self.normalize else 1.0
-        t.Xd_raw, t.x_facts, t.layout = None, None, "cm"
-        if t.big:
-            import torch
-            if Xv.flags.c_contiguous:
-                host = Xv
-            elif Xv.T.flags.c_contiguous:
-                host, t.layout = Xv.T, "pm"
-            else:
-                host = np.ascontiguousarray(Xv)
-            Xd_raw, scans = _upload_with_scans(host, torch.device("cuda", torch.cuda.current_device()), self.log_shift)
-            n_bad, n_nan, n_neg = (int(v) for v in scans["bad"].cpu())
-            if n_bad:
-                raise ValueError(f"Input X contains {'NaN' if n_nan else 'infinity'}.")
-            if n_neg:
-                raise ValueError("Negative values in data")
-            zc, zp = ((scans["row_sum"] == 0, scans["col_sum"] == 0) if t.layout == "cm" else (scans["col_sum"] == 0, scans["row_sum"] == 0))
-            Xd = Xd_raw if t.layout == "cm" else Xd_raw.t()
-            s1, n_nonint, nnz, x_max = (float(v) for v in torch.cat((scans["s1"].view(1), scans["facts"])).cpu())
-            t.empty_ch, t.empty_px = zc, zp
-            if bool(zc.any()) or bool(zp.any()):
-                Xd[:, zp] = self.log_shift
-                Xd[zc, :] = self.log_shift
-            else:
-                t.x_facts = XFacts(nonneg=True, sum_x=s1, is_int=bool(n_nonint == 0), x_max=x_max, nnz=int(nnz))
-            t.Xd_raw, t.X_fixed = Xd_raw, None
-        else:
-            t.X_fixed = self.remove_zeros_lines(Xv, self.log_shift)   # (ValueError on negative values)
-            t.empty_ch, t.empty_px = Xv.sum(axis=1) == 0, Xv.sum(axis=0) == 0
+        t.rec = (ingest.ingest_device(t.Xv, self.log_shift, shard=None, check_finite=True, keep_host_copy=False) if t.big
+                 else ingest.ingest_host(t.Xv, self.log_shift, self.remove_zeros_lines))   # (ValueError on negative values)
 
     def _transform_engine(self, t, H):
         """The engine of the new data - the fit's parameters, the new grid, no fixed_H, W held - with (Wf, H0) loaded.  Not cached."""
         from espm_amd.engine import MUEngine
-        k = self.n_components
+        k, rec = self.n_components, t.rec
+        t.rec = None
         t.out_dtype = t.Xv.dtype
         Wf = np.maximum(np.asarray(self.W_, dtype=np.float64) * t.xscale, self.log_shift)   # (W_ is stored un-normalised, base.py:417-418)
         t.Wf = Wf
         G = None if self._identity_G else self.G_
         if H is None:   # updates.py:213-221
             GW = Wf if G is None else np.asarray(G, dtype=np.float64) @ Wf
-            if t.Xd_raw is not None:
+            if rec.Xd_raw is not None:
                 import torch
-                Xd = t.Xd_raw if t.layout == "cm" else t.Xd_raw.t()
-                gw = torch.from_numpy(GW).to(Xd.device)
-                H0 = (torch.linalg.pinv(gw) @ (Xd.to(torch.float64) * t.xscale)).abs().cpu().numpy()
+                gw = torch.from_numpy(GW).to(rec.Xd_raw.device)
+                H0 = (torch.linalg.pinv(gw) @ (rec.Xd.to(torch.float64) * t.xscale)).abs().cpu().numpy()
             else:
-                H0 = np.abs(np.linalg.lstsq(GW, np.asarray(t.X_fixed, dtype=np.float64) * t.xscale, rcond=None)[0])
+                H0 = np.abs(np.linalg.lstsq(GW, np.asarray(rec.X_fixed, dtype=np.float64) * t.xscale, rcond=None)[0])
             if self.simplex_H:
                 H0 = H0 / H0.sum(axis=0, keepdims=True)
         else:
@@ -1113,16 +703,14 @@ class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
             if H0.shape != (k, t.Xv.shape[1]):
                 raise ValueError(f"H must be {(k, t.Xv.shape[1])}, got {H0.shape}")
         H0 = np.maximum(H0, self.log_shift)
-        any_ch = bool(t.empty_ch.any())
-        any_px = bool(t.empty_px.any())
         kw = dict(self._engine_kwargs())
         kw.pop("frobenius", None)
         kw.pop("pg_gamma_w", None)
-        eng = MUEngine(t.X_fixed if t.Xd_raw is None else t.Xd_raw, k, G=G, shape_2d=t.shape_2d, simplex_H=self.simplex_H,
+        eng = MUEngine(rec.X_fixed if rec.Xd_raw is None else rec.Xd_raw, k, G=G, shape_2d=t.shape_2d, simplex_H=self.simplex_H,
                        simplex_W=False, log_shift=self.log_shift, tol=self.tol, fixed_H=None, fixed_W=None, xscale=t.xscale,
-                       max_iter=self.max_iter, fix_zero_lines=False, filled_channels=t.empty_ch if any_ch or any_px else None,
-                       filled_pixels=t.empty_px if any_ch or any_px else None, layout=t.layout, autotune=False, x_facts=t.x_facts, **kw)
-        t.Xd_raw = t.X_fixed = None
+                       max_iter=self.max_iter, fix_zero_lines=False, filled_channels=rec.empty_ch if rec.fill else None,
+                       filled_pixels=rec.empty_px if rec.fill else None, layout=rec.layout, autotune=False, x_facts=rec.x_facts, **kw)
+        del rec
         eng.load_state(Wf, H0)
         # which store the new data went on and whether its iteration is one launch (include/espm_mu.h: espm_mu_h_chain_applies)
         self.transform_path_ = dict(x_store=eng.x_store, n_heavy=int(eng.n_heavy), h_chain=int(eng.h_chain_applies()))
@@ -1157,24 +745,12 @@ class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
             self.transform_losses_.append(eval_after)
             self.transform_rel_.append(rel_H)
             self.transform_n_iter_ = n
-            stop = False
             if last:
                 say("exits because max_iteration was reached")
                 break
-            if not self.no_stop_criterion:
-                if rel_H < self.tol:   # (max(rel_H, rel_W) with rel_W = 0)
-                    say("exits because of relative change rel_A {} and rel_P {} < tol ".format(rel_H, 0.0))
-                    stop = True
-                elif abs((eval_before - eval_after) / eval_init) < self.tol:
-                    say("exits because of relative change < tol: {}".format((eval_before - eval_after) / eval_init))
-                    stop = True
-                elif np.isnan(eval_after):
-                    say("exit because of the presence of NaN")
-                    stop = True
-                elif (eval_before - eval_after) < 0:
-                    say("exit because of negative decrease {}: {}, {}".format((eval_before - eval_after), eval_before, eval_after))
-                    stop = True
-            if stop:
+            why = None if self.no_stop_criterion else stop_message(0.0, rel_H, eval_before, eval_after, eval_init, self.tol)
+            if why is not None:
+                say(why)
                 eng.retreat_h()   # (state n + 1 was proposed, state n is the result)
                 break
             if self.verbose > 0 and np.mod(n, self.eval_print) == 0:

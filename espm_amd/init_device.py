@@ -195,7 +195,7 @@ def _cholqr_rows_sharded(A, group, passes):
 
 def randomized_svd_sharded(Xd, n_components, random_state, shard, n_oversamples=10):
     """``randomized_svd_device`` for an image whose PIXELS are spread over the ranks: Xd is this rank's (n_samples = channels,
-    block of pixels) matrix, ``shard`` the estimator's _Shard.  The algorithm is the same - Gaussian test matrix from the same
+    block of pixels) matrix, ``shard`` the estimator's sharding.FitShard.  The algorithm is the same - Gaussian test matrix from the same
     ``RandomState`` (replicated: every rank draws it), power iterations, QR, SVD of the small projection, ``svd_flip`` - with the
     contractions over the pixels added over the ranks (n x r and r x r matrices: ~100 KB per all-reduce) and nothing of the
     size of the image ever leaving its rank.  One deviation from scikit-learn: the power iterations normalise the TALL factor
@@ -288,7 +288,7 @@ def initialize_nmf_device(X, n_components, init=None, random_state=None, eps=1e-
 
     X: (n_samples, n_features) numpy array, fp32 or fp64 (kept in its dtype, like scikit-learn); X_device: the same
     matrix already on the GPU (then X is only consulted for its shape and dtype); X_mean: its mean, if the caller has it.
-    shard (the estimator's _Shard): X_device holds this rank's block of pixels only - the randomized SVD runs sharded
+    shard (the estimator's sharding.FitShard): X_device holds this rank's block of pixels only - the randomized SVD runs sharded
     (randomized_svd_sharded), its small factors are replicated and the post-processing below is the same on every rank."""
     from sklearn.utils import check_random_state
 

@@ -22,6 +22,7 @@ import ctypes as C
 import os
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 
 def hs_stride(k: int) -> int:
@@ -300,3 +301,80 @@ def _as_tensor(ptr, nbytes, device):
     m = _Mem()
     m.__cuda_array_interface__ = {"shape": (int(nbytes),), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
     return torch.as_tensor(m, device=device)
+
+
+class FitShard:
+    """Pixel-row sharding of ONE fit over the ranks of a process group (est.shard(group)): every rank
+    runs the same script on the same X; its engine holds a contiguous block of image rows (X and H sharded, W / G replicated)
+    and the results are assembled on every rank."""
+
+    def __init__(self, group, shape_2d, p):
+        dist = torch.distributed
+        self.group, self.world, self.rank = group, dist.get_world_size(group), dist.get_rank(group)
+        self.src = dist.get_global_rank(group, 0)
+        if shape_2d is not None:
+            nx, ny = int(shape_2d[0]), int(shape_2d[1])
+            if nx * ny != p:
+                raise ValueError(f"shape_2d {shape_2d} does not match the {p} pixels of X")
+            blocks = [split_rows(nx, self.world, r) for r in range(self.world)]
+            self.counts = [rows * ny for _, rows in blocks]
+            row0, rows = blocks[self.rank]
+            self.sl, self.shape_2d = slice(row0 * ny, (row0 + rows) * ny), (rows, ny)
+        else:   # no image grid (L = identity, base.py:289-291): any contiguous split of the pixels
+            blocks = [split_rows(p, self.world, r) for r in range(self.world)]
+            self.counts = [rows for _, rows in blocks]
+            row0, rows = blocks[self.rank]
+            self.sl, self.shape_2d = slice(row0, row0 + rows), None
+
+    def combine_scans(self, scans, layout):
+        """The upload's scans of this rank's block (estimators/ingest.py: _upload_with_scans) turned into the image's: counts and sums added
+        over the ranks, the largest entry their maximum, the channel sums added (the rows of the array as it lies in the channel-major
+        layout, its columns in the pixel-major one); the pixel sums stay the block's."""
+        dist = torch.distributed
+        ch = "row_sum" if layout == "cm" else "col_sum"
+        vec = torch.cat((scans["bad"].to(torch.float64), scans["s1"].view(1), scans["s2"].view(1), scans["facts"][:2]))
+        dist.all_reduce(vec, group=self.group)
+        xmax = scans["facts"][2:3].clone()
+        dist.all_reduce(xmax, op=dist.ReduceOp.MAX, group=self.group)
+        chs = scans[ch].clone()
+        dist.all_reduce(chs, group=self.group)
+        out = dict(scans)
+        out["bad"] = vec[:3].round().to(torch.int64)
+        out["s1"], out["s2"] = vec[3], vec[4]
+        out["facts"] = torch.cat((vec[5:7], xmax))
+        out[ch] = chs
+        return out
+
+    def agree(self, ok, what, err=None):
+        """Every rank learns whether every rank succeeded (all-reduce MIN of a flag) before anybody raises: the failing rank re-raises
+        its own exception, the others a RuntimeError naming the step - nobody is left in the next collective waiting for a rank that
+        has gone."""
+        dev = f"cuda:{torch.cuda.current_device()}" if torch.distributed.get_backend(self.group) != "gloo" else "cpu"
+        flag = torch.tensor([1 if ok else 0], dtype=torch.int32, device=dev)
+        torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN, group=self.group)
+        if err is not None:
+            raise err
+        if int(flag.item()) == 0:
+            raise RuntimeError(f"sharded fit: {what} failed on another rank")
+
+    def cols(self, a):
+        """This rank's columns of an (.., p) array (None stays None)."""
+        return None if a is None else a[..., self.sl]
+
+    def broadcast(self, arrays, device):
+        """Rank 0's arrays on every rank (the initial W, H, G: bit-identical starts whatever the ranks' own init gave)."""
+        out = []
+        for a in arrays:
+            t = torch.from_numpy(np.ascontiguousarray(a)).to(device)
+            torch.distributed.broadcast(t, src=self.src, group=self.group)
+            out.append(t.cpu().numpy())
+        return out
+
+    def gather_cols(self, local):
+        """(k, p) numpy array from every rank's (k, p_local) device tensor, in rank order."""
+        width = max(self.counts)
+        mine = torch.zeros((local.shape[0], width), dtype=local.dtype, device=local.device)
+        mine[:, :local.shape[1]] = local
+        parts = [torch.empty_like(mine) for _ in range(self.world)]
+        torch.distributed.all_gather(parts, mine, group=self.group)
+        return np.concatenate([part[:, :c].cpu().numpy() for part, c in zip(parts, self.counts)], axis=1)

@@ -1023,9 +1023,9 @@ def test_device_preparation_of_a_large_x_matches_the_oracle(SmoothNMF, layout, n
     empty channels / pixels (the filled branch takes its own passes), `normalize`, both precisions, and a (pixels, channels)
     array handed over with hspy_comp (uploaded as it lies)."""
     from espm_amd import synth
-    from espm_amd.estimators import base as est_base
+    from espm_amd.estimators import ingest
     n, nx, ny, k = 600, 90, 80, 3
-    assert n * nx * ny >= est_base._DEVICE_PREP_MIN_SIZE
+    assert n * nx * ny >= ingest._DEVICE_PREP_MIN_SIZE
     prob = synth.make_problem(n, nx, ny, k, N=40.0, seed=5)
     X = synth.sample_numpy(prob, seed=5).astype(dtype)
     X[0, X.sum(axis=0) == 0] = 1.0                     # (no accidental holes: the parameter decides)

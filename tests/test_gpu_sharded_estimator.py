@@ -151,8 +151,8 @@ def _large_worker(rank, world, port, out, cfg):
         res = _fit_large(X, k, nx, ny, dist.group.WORLD, hspy)
         # the sharded randomized SVD against the one-GPU routine on the whole image (same random stream)
         from espm_amd import init_device
-        from espm_amd.estimators.base import _Shard
-        sh = _Shard(dist.group.WORLD, (nx, ny), nx * ny)
+        from espm_amd.sharding import FitShard
+        sh = FitShard(dist.group.WORLD, (nx, ny), nx * ny)
         Xd = torch.from_numpy(X).cuda()
         U1, s1, V1 = init_device.randomized_svd_device(Xd, k, 0)
         U2, s2, V2 = init_device.randomized_svd_sharded(Xd[:, sh.sl].contiguous(), k, 0, sh)

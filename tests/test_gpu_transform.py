@@ -118,14 +118,14 @@ def build_case(name):
     return est_kw, X_fit, fit_grid, X_new, new_grid, regs
 
 
-def oracle_transform(est, X_new, new_grid, H0, regs, tol, algo, max_iter=MAX_ITER):
+def oracle_transform(est, X_new, new_grid, H0, regs, tol, algo, max_iter=MAX_ITER, **kw):
     scale = float(est.norm_factor_) if est.normalize else 1.0
     Wf = np.maximum(np.asarray(est.W_, dtype=np.float64) * scale, oc.LOG_SHIFT)   # (W_ may be float32: its entries on the floor read back a rounding below it)
     lam = regs.get("lambda_L", 0.0)
     return oc.fit(np.asarray(X_new, dtype=np.float64) * scale, est.n_components, G=None if est.G is None else np.asarray(est.G_, dtype=np.float64),
                   W=Wf.copy(), fixed_W=Wf.copy(), H=None if H0 is None else H0.copy(), lambda_L=lam, mu=regs.get("mu", 0),
                   simplex_H=regs["simplex_H"], simplex_W=regs["simplex_W"], shape_2d=new_grid if lam else None, tol=tol, max_iter=max_iter,
-                  algo=algo)
+                  algo=algo, **kw)
 
 
 def assert_stop_not_marginal(ref, tol):
@@ -267,6 +267,98 @@ def test_transform_is_the_pixel_rows_method(SmoothNMF):
     assert not hasattr(est, "transform") and hasattr(est, "unmix") and hasattr(est, "fit_transform")
     with pytest.raises(AttributeError):
         est.transform(X_new)
+
+
+# ---- an X above the device-preparation threshold: ONE upload, the sign check and the empty lines from its scans ---------------------
+BIG = (600, 90, 80, 3)      # 4.32 M entries, just above estimators/ingest.py's 4 M (the size test_gpu_estimator.py's large fit uses)
+BIG_REGS = dict(simplex_H=True, simplex_W=False, lambda_L=1.0)
+_big_cache = {}
+
+
+def _big_draws(holes):
+    """(X of the fit, X_new), both (n, p) fp32 counts; ``holes``: the same empty channels and pixels in both."""
+    if ("draws", holes) not in _big_cache:
+        from espm_amd import synth
+        n, nx, ny, k = BIG
+        prob = synth.make_problem(n, nx, ny, k, N=40.0, seed=5)
+        draws = []
+        for seed in (5, 6):
+            X = synth.sample_numpy(prob, seed=seed).astype(np.float32)
+            X[0, X.sum(axis=0) == 0] = 1.0                     # (no accidental holes: the parameter decides)
+            X[X.sum(axis=1) == 0, 0] = 1.0
+            if holes:
+                X[:5] = 0
+                X[300:303] = 0
+                X[:, 1000:1040] = 0
+                X[:, -7:] = 0
+            draws.append(X)
+        _big_cache["draws", holes] = draws
+    return _big_cache["draws", holes]
+
+
+def _big_fitted(SmoothNMF, layout, holes):
+    """The estimator fitted 6 iterations on the first draw (once per layout and holes), set up for a 6-iteration unmix."""
+    if ("est", layout, holes) not in _big_cache:
+        from espm_amd import synth
+        n, nx, ny, k = BIG
+        X_fit = _big_draws(holes)[0]
+        W0, H0 = synth.random_init(n, k, nx * ny, seed=5, scale=0.07)
+        est = SmoothNMF(n_components=k, shape_2d=(nx, ny), max_iter=6, tol=0, no_stop_criterion=True, verbose=0, hspy_comp=(layout == "pm"), **BIG_REGS)
+        quiet(est.fit, np.ascontiguousarray(X_fit.T) if layout == "pm" else X_fit, W=W0.copy(), H=H0.copy())
+        _big_cache["est", layout, holes] = est
+    return _big_cache["est", layout, holes]
+
+
+@pytest.mark.parametrize("layout,holes,supplied", [("cm", False, True), ("cm", True, True), ("pm", False, True), ("pm", True, True), ("cm", False, False)],
+                         ids=["cm", "cm-holes", "pm", "pm-holes", "cm-H_none"])
+def test_unmix_of_a_large_x_on_the_device_and_on_the_host_matches_the_oracle(SmoothNMF, monkeypatch, layout, holes, supplied):
+    """unmix of an X above the device-preparation threshold - uploaded once, as it lies (a (pixels, channels) array with hspy_comp: pixel-major),
+    sign check, empty lines and the store's facts from the upload's scans, H = None: the pseudo-inverse on the device copy - against the
+    oracle, and the same call with the threshold above the array's size (the host passes): the same store, the same tolerances."""
+    from espm_amd.estimators import ingest
+    n, nx, ny, k = BIG
+    assert n * nx * ny >= ingest._DEVICE_PREP_MIN_SIZE
+    est = _big_fitted(SmoothNMF, layout, holes)
+    X_new = _big_draws(holes)[1]
+    H0 = None
+    if supplied:
+        H0 = np.random.default_rng(99).random((k, nx * ny)) + 0.2
+        H0 /= H0.sum(axis=0, keepdims=True)
+    ref = oracle_transform(est, X_new, (nx, ny), H0, BIG_REGS, 0, "log_surrogate", 6, no_stop_criterion=True)
+    assert ref["n_iter"] == 6
+    arg_X = np.ascontiguousarray(X_new.T) if layout == "pm" else X_new
+    arg_H = None if H0 is None else (H0.T if layout == "pm" else H0)
+    stores = {}
+    for path in ("device", "host"):
+        if path == "host":
+            monkeypatch.setattr(ingest, "_DEVICE_PREP_MIN_SIZE", X_new.size + 1)
+        uploads = []
+        upload = ingest._upload_with_scans
+        monkeypatch.setattr(ingest, "_upload_with_scans", lambda *a, **kw: uploads.append(1) or upload(*a, **kw))
+        Hn = quiet(est.unmix, arg_X, H=arg_H)
+        monkeypatch.setattr(ingest, "_upload_with_scans", upload)
+        assert len(uploads) == (1 if path == "device" else 0)          # (the path that was meant)
+        if layout == "pm":
+            assert Hn.shape == (nx * ny, k)
+            Hn = Hn.T
+        stores[path] = est.transform_path_["x_store"]
+        print(f"{layout} holes={holes} H supplied={supplied}, {path} path: n_iter {est.transform_n_iter_}, store {stores[path]}, max|dH| {np.abs(Hn - ref['H']).max():.2e}, "
+              f"max rel loss {np.abs(np.array(est.transform_losses_) / ref['losses'] - 1).max():.2e}")
+        assert est.transform_n_iter_ == 6
+        np.testing.assert_allclose(est.transform_losses_, ref["losses"], rtol=LOSS_RTOL)
+        np.testing.assert_allclose(Hn, ref["H"], rtol=0, atol=H_ATOL)
+    assert stores["device"] == stores["host"]
+
+
+def test_unmix_of_a_large_x_refuses_nan_and_negative_values(SmoothNMF):
+    est = _big_fitted(SmoothNMF, "cm", False)
+    bad = _big_draws(False)[1].copy()
+    bad[3, 17] = np.nan
+    with pytest.raises(ValueError, match="NaN"):
+        quiet(est.unmix, bad)
+    bad[3, 17] = -1.0
+    with pytest.raises(ValueError, match="Negative values in data"):
+        quiet(est.unmix, bad)
 
 
 # ---- 3: the three ways through the H-only iteration give the same bits ----------------------------------------------------------

@@ -255,10 +255,10 @@ def test_lu_normaliser_of_the_device_init_equals_scipy():
 @pytest.mark.parametrize("fill_lines", [False, True])
 @pytest.mark.parametrize("scale", [None, 0.37])
 def test_host_copy_of_a_large_fit_equals_the_reference_passes(layout, fill_lines, scale):
-    """estimators/base.py::_HostCopy (the estimator's own X_ of a large fit, made on worker threads) against the passes it
+    """estimators/ingest.py::_HostCopy (the estimator's own X_ of a large fit, made on worker threads) against the passes it
     replaces: remove_zeros_lines' copy with its filled lines (espm/estimators/base.py:519-528), then the normalisation
     (base.py:264-267) - values, dtype and memory order, in both ingest layouts."""
-    from espm_amd.estimators.base import _HostCopy
+    from espm_amd.estimators.ingest import _HostCopy
 
     rs = np.random.RandomState(5)
     n, p = 37, 1000

@@ -171,17 +171,17 @@ def _shard_worker(rank, world, port, out):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        from espm_amd.estimators.base import _Shard
+        from espm_amd.sharding import FitShard
         rng = np.random.default_rng(5)            # the same arrays on every rank, rank 0's made distinguishable below
         H = rng.random((K, NX * NY))
         W = rng.random((N, K)) + rank             # what a rank's own initialisation would give
-        sh = _Shard(dist.group.WORLD, (NX, NY), NX * NY)
+        sh = FitShard(dist.group.WORLD, (NX, NY), NX * NY)
         row0, rows = sharding.split_rows(NX, world, rank)
         assert (sh.sl.start, sh.sl.stop) == (row0 * NY, (row0 + rows) * NY) and sh.shape_2d == (rows, NY) and sum(sh.counts) == NX * NY
         Wb, Hb = sh.broadcast([W, H], "cpu")                     # rank 0's arrays everywhere
         mine = torch.from_numpy(sh.cols(H)).contiguous()         # this rank's columns ...
         full = sh.gather_cols(mine)                              # ... assembled on every rank
-        flat = _Shard(dist.group.WORLD, None, NX * NY)           # no image grid: a contiguous split of the pixels
+        flat = FitShard(dist.group.WORLD, None, NX * NY)           # no image grid: a contiguous split of the pixels
         out[rank] = (Wb, Hb, full, sh.cols(None) is None, (flat.sl.start, flat.sl.stop), flat.shape_2d, flat.counts)
     finally:
         dist.destroy_process_group()
@@ -189,7 +189,7 @@ def _shard_worker(rank, world, port, out):
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_estimator_shard_helper_under_gloo(world):
-    """The host side of ``est.shard(group)`` (espm_amd/estimators/base.py::_Shard) without a GPU: every rank's block of image
+    """The host side of ``est.shard(group)`` (espm_amd/sharding.py::FitShard) without a GPU: every rank's block of image
     rows, rank 0's initial arrays on every rank, the ranks' blocks of H assembled in rank order."""
     with mp.Manager() as mgr:
         out = mgr.dict()
@@ -215,19 +215,17 @@ def _ingest_worker(rank, world, port, out):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
         from espm_amd import init_device
-        from espm_amd.estimators.base import _Shard
+        from espm_amd.sharding import FitShard
         n, nx, ny, k = 48, 12, 16, 3
         rng = np.random.default_rng(5)
         Wt, Ht = rng.random((n, k)) + 0.05, rng.random((k, nx * ny)) + 0.05
         X = rng.poisson(Wt @ Ht * 3).astype(np.float32)
         X[7, :] = 0                                     # an empty channel: only the all-reduced channel sums can know
-        sh = _Shard(dist.group.WORLD, (nx, ny), nx * ny)
+        sh = FitShard(dist.group.WORLD, (nx, ny), nx * ny)
         Xl = torch.from_numpy(np.ascontiguousarray(X[:, sh.sl]))
-        # the upload's scans of this rank's block (espm_amd/estimators/base.py: _upload_with_scans), formed here on the host tensor
-        xd = Xl.double()
-        scans = dict(row_sum=xd.sum(dim=1), col_sum=xd.sum(dim=0), bad=torch.zeros(3, dtype=torch.int64), s1=xd.sum(),
-                     s2=(xd * torch.log(xd.clamp_min(1e-14))).sum(),
-                     facts=torch.stack(((Xl != Xl.round()).sum().double(), (Xl != 0).sum().double(), Xl.max().double())))
+        # the upload's scans of this rank's block: what _upload_with_scans runs on every chunk, here on the host tensor
+        from espm_amd.estimators.ingest import scan_chunk
+        scans = scan_chunk(Xl, 1e-14)
         comb = sh.combine_scans(scans, "cm")
         Xd = torch.from_numpy(X).double()
         res = dict(ch_sum_ok=bool(torch.allclose(comb["row_sum"], Xd.sum(dim=1))), s1=float(comb["s1"]), s1_ref=float(Xd.sum()),
@@ -270,8 +268,8 @@ def _agree_worker(rank, world, port, out):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        from espm_amd.estimators.base import _Shard
-        sh = _Shard(dist.group.WORLD, (NX, NY), NX * NY)
+        from espm_amd.sharding import FitShard
+        sh = FitShard(dist.group.WORLD, (NX, NY), NX * NY)
         sh.agree(True, "a step everybody passes")
         try:
             sh.agree(rank != 1, "the upload", MemoryError("rank 1 ran out of memory") if rank == 1 else None)

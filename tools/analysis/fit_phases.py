@@ -6,7 +6,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import numpy as np
 import torch
 from espm_amd import synth
-from espm_amd.estimators import SmoothNMF, base
+from espm_amd.estimators import SmoothNMF, base, ingest
 from espm_amd.engine import MUEngine
 
 marks = []
@@ -30,10 +30,10 @@ MUEngine.iterate = timed("iterate", MUEngine.iterate)
 MUEngine.history = timed("history read-back", MUEngine.history)
 MUEngine.get_W = timed("get_W", MUEngine.get_W)
 if os.environ.get("NOCOPY") == "1":   # experiment: the fit without the estimator's host copy X_ (is the copy what unsettles the phases?)
-    base._HostCopy.start = lambda self: None
-    base._HostCopy.result = lambda self: None
+    ingest._HostCopy.start = lambda self: None
+    ingest._HostCopy.result = lambda self: None
 else:
-    base._HostCopy.result = timed("join of the host copy X_", base._HostCopy.result)
+    ingest._HostCopy.result = timed("join of the host copy X_", ingest._HostCopy.result)
 _to = torch.Tensor.to
 
 

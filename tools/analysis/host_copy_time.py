@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""How long the estimator's own host copy X_ of a headline-size image takes on this host (base.py's _HostCopy worker): one
+"""How long the estimator's own host copy X_ of a headline-size image takes on this host (estimators/ingest.py's _HostCopy worker): one
 thread against a few threads over row blocks (numpy releases the GIL inside copies and ufunc loops)."""
 import time
 import threading
