@@ -806,6 +806,61 @@ class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
             out = dict(out, H_std=out["H_std"].T)
         return out
 
+    def spectral_diagnostics(self, X=None):
+        """Per-channel deviance and error bars of ``W_`` (``espm_amd.measures.spectral_diagnostics`` on ``G_``, ``W_`` and ``H_``): the
+        spectral half of ``pixel_diagnostics``.
+
+        Sets ``channel_deviance_`` (n,): the Poisson deviance 2 sum_p (x ln(x / y) - x + y) of every energy channel - the residual
+        spectrum, in which a missing line or element shows as a narrow band; ``sum_spectrum_`` and ``model_spectrum_`` (n,): the
+        measured and the modelled sum spectrum; ``W_std_``, of ``W_``'s shape: the Cramer-Rao bound of every entry of ``W_`` given
+        the fitted abundances (with a physics model or a dictionary G: the error bars of the concentrations); ``D_std_`` (n, k): the
+        bound on the spectra ``G_ @ W_``.  With ``simplex_W`` the bound is the one under the constraint the fit imposed: the rows
+        ``physics_model_.NMF_simplex()`` of W sum to one per component with a physics model, all rows otherwise.  Channels (or, with
+        G, the whole matrix) whose Fisher information is numerically singular hold NaN and are counted in ``n_singular``.  The bound
+        ignores the uncertainty of ``H_``, the regularisers (``mu``, ``lambda_L``) and entries held at the ``log_shift`` floor: it
+        is the error bar given the abundances.  Returns dict(channel_deviance, sum_spectrum, model_spectrum, M, W_std, D_std,
+        n_singular); all of it is indexed by channel or by W's rows, so ``hspy_comp`` changes only how ``X`` is read.
+
+        ``X``: as for ``pixel_diagnostics`` - the fitted image in counts, (channels, pixels), or (pixels, channels) with
+        ``hspy_comp``; ValueError when its channels do not match ``G_`` or its pixels ``H_``.  ``X=None`` takes the fit's ``X_``
+        un-scaled, with the same cost as there: under ``normalize`` that is a host array in ``X_``'s dtype, 4 or 8 bytes per entry on
+        the host and again on the device against 1 or 2 for the original counts, and lines without a count carry the ``log_shift``
+        fill - at large sizes pass the X that was fitted.  Computed in fp64 whatever the estimator's precision, on the current device
+        (a ``shard()``ed estimator: every rank holds the whole ``W_`` and ``H_`` and computes everything on its own device).  More
+        than 8 components raise NotImplementedError before anything is uploaded, and so does an estimator with imposed ``fixed_W``
+        entries: taking imposed entries out of the information matrix is a later step."""
+        from espm_amd import measures
+        check_is_fitted(self, "W_")
+        k = int(self.H_.shape[0])
+        if k > 8:
+            raise NotImplementedError(f"spectral_diagnostics: {k} components (the kernel is built for 1..8)")
+        if self.fixed_W is not None and (np.asarray(self.fixed_W) >= 0).any():
+            raise NotImplementedError("spectral_diagnostics: the bound with imposed fixed_W entries is not implemented")
+        layout = "cm"
+        if X is None:
+            check_is_fitted(self, "X_")
+            X = np.asarray(self._X_fixed())
+        else:
+            if not hasattr(X, "shape") or getattr(X, "ndim", 0) != 2:
+                X = np.asarray(X)
+            if X.ndim != 2:
+                raise ValueError("X must be 2-D")
+            layout = "pm" if self.hspy_comp else "cm"
+            n, p = (X.shape[1], X.shape[0]) if self.hspy_comp else (X.shape[0], X.shape[1])
+            if n != self.G_.shape[0]:
+                raise ValueError(f"X has {n} channels, the fitted G_ has {self.G_.shape[0]}")
+            if p != self.H_.shape[1]:
+                raise ValueError(f"X has {p} pixels, the fitted H_ has {self.H_.shape[1]}")
+        rows = None
+        if self.simplex_W and getattr(self, "algo", None) != "bmd" and not self.l2:   # (the W step that had a simplex: _make_engine)
+            rows = self.physics_model_.NMF_simplex() if self.physics_model_ is not None else True
+        out = measures.spectral_diagnostics(X, np.asarray(self.W_, dtype=np.float64), np.asarray(self.H_, dtype=np.float64),
+                                            G=None if self._identity_G else np.asarray(self.G_, dtype=np.float64), simplex_rows=rows,
+                                            log_shift=self.log_shift, layout=layout)
+        self.channel_deviance_, self.sum_spectrum_, self.model_spectrum_ = out["channel_deviance"], out["sum_spectrum"], out["model_spectrum"]
+        self.W_std_, self.D_std_ = out["W_std"], out["D_std"]
+        return out
+
     def inverse_transform(self, W):
         """G W H_ (espm/estimators/base.py:461-477)."""
         check_is_fitted(self)

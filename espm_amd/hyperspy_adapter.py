@@ -98,6 +98,11 @@ class SpectrumImage:
         """(deviance (ny, nx), H_std (k, ny, nx)) of the kept estimator, after its ``pixel_diagnostics()``."""
         return diagnostic_maps(self.learning_results.decomposition_algorithm, self.shape_2d)
 
+    def get_decomposition_diagnostic_spectra(self):
+        """(channel_deviance (n,), sum_spectrum (n,), model_spectrum (n,), D_std (k, n)) of the kept estimator, after its
+        ``spectral_diagnostics()``."""
+        return diagnostic_spectra(self.learning_results.decomposition_algorithm)
+
 
 def diagnostic_maps(est, shape_2d=None):
     """``est.deviance_`` and ``est.H_std_`` (set by ``est.pixel_diagnostics()``) in the navigation shape, like the loadings:
@@ -106,6 +111,16 @@ def diagnostic_maps(est, shape_2d=None):
         raise AttributeError("call est.pixel_diagnostics() first: it sets deviance_ and H_std_")
     ny, nx = (int(v) for v in (shape_2d if shape_2d is not None else est.shape_2d))
     return np.asarray(est.deviance_).reshape((ny, nx)), np.asarray(est.H_std_).reshape((-1, ny, nx))
+
+
+def diagnostic_spectra(est):
+    """``est.channel_deviance_``, ``est.sum_spectrum_``, ``est.model_spectrum_`` (n,) and ``est.D_std_`` as (k, n) (set by
+    ``est.spectral_diagnostics()``) on the signal axis, like the factors: the residual spectrum next to the measured and the
+    modelled sum spectrum, and the error band of every component's spectrum."""
+    if not hasattr(est, "channel_deviance_"):
+        raise AttributeError("call est.spectral_diagnostics() first: it sets channel_deviance_, sum_spectrum_, model_spectrum_ and D_std_")
+    return (np.asarray(est.channel_deviance_), np.asarray(est.sum_spectrum_), np.asarray(est.model_spectrum_),
+            np.asarray(est.D_std_).T)
 
 
 def register():
@@ -149,5 +164,10 @@ try:  # the real signal class, where hyperspy is installed (hyperspy_extension.y
         def X(self):
             shape = self.axes_manager[1].size, self.axes_manager[0].size, self.axes_manager[2].size
             return self.data.reshape((shape[0] * shape[1], shape[2])).T
+
+        def get_decomposition_diagnostic_spectra(self):
+            """(channel_deviance, sum_spectrum, model_spectrum (n,), D_std (k, n)) of the kept estimator, after its
+            ``spectral_diagnostics()``."""
+            return diagnostic_spectra(self.learning_results.decomposition_algorithm)
 except Exception:  # pragma: no cover - hyperspy is absent in the build image
     EDSespmAMD = None

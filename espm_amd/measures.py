@@ -353,3 +353,193 @@ def pixel_diagnostics(X, D, H, *, simplex_H=False, log_shift=log_shift, layout="
                                                    n, p, _ptr(Dd), _ptr(Hd), k, float(log_shift), int(bool(simplex_H)), _ptr(dv), _ptr(hs),
                                                    _ptr(ns), _stream()))
         return dict(deviance=dv.cpu().numpy(), H_std=hs.cpu().numpy(), n_singular=int(ns.item()))
+
+
+# ---- per-channel diagnostics of a fitted model (csrc/mu_diag_chan.hip) -------------------------------------------------------------
+_SPECTRAL_MAX_F = 2048   # rows of the dense information matrix of a dictionary fit (m k): above it, it is no small matrix any more
+
+
+def _spd_inverse(A):
+    """(A^-1, bad) of symmetric matrices (..., N, N) by LAPACK's Cholesky A = L L^T, whose squared diagonal holds the pivots of the
+    root-free form the pixel kernel uses, with that kernel's rule: a pivot that is not above N eps max diag(A) marks the matrix
+    singular.  A^-1 = L^-T L^-1.  Singular matrices (``bad``) come back as NaN."""
+    A = np.array(A, dtype=np.float64, copy=True)
+    N = A.shape[-1]
+    eye = np.eye(N)
+    thr = N * np.finfo(np.float64).eps * np.max(np.diagonal(A, axis1=-2, axis2=-1), axis=-1)
+    bad = ~np.isfinite(A).all(axis=(-2, -1))
+    A[bad] = eye
+    try:
+        L = np.linalg.cholesky(A)
+    except np.linalg.LinAlgError:   # a pivot <= 0 somewhere in the stack: find which matrices, one by one
+        flat, fbad = A.reshape(-1, N, N), bad.reshape(-1).copy()
+        for c in range(flat.shape[0]):
+            try:
+                np.linalg.cholesky(flat[c])
+            except np.linalg.LinAlgError:
+                fbad[c] = True
+        bad = fbad.reshape(bad.shape)
+        A[bad] = eye
+        L = np.linalg.cholesky(A)
+    bad = bad | ~(np.diagonal(L, axis1=-2, axis2=-1) ** 2 > thr[..., None]).all(axis=-1)
+    L[bad] = eye
+    Z = np.linalg.inv(L)
+    S = np.swapaxes(Z, -1, -2) @ Z
+    S[bad] = np.nan
+    return S, bad
+
+
+def _simplex_rows(simplex_rows, rows):
+    """None (no constraint), True (all ``rows`` rows of W) or an index array -> None or a sorted array of distinct row indices."""
+    if simplex_rows is None or simplex_rows is False:
+        return None
+    if simplex_rows is True:
+        return np.arange(rows)
+    idx = np.unique(np.asarray(simplex_rows).astype(np.int64).ravel())
+    if idx.size == 0:
+        return None
+    if idx[0] < 0 or idx[-1] >= rows:
+        raise ValueError(f"simplex_rows must index the {rows} rows of W")
+    return idx
+
+
+def _sqrt_var(v):
+    with np.errstate(invalid="ignore"):
+        return np.sqrt(np.where(v < 0, 0.0, v))   # (a rounding-negative variance is 0; a NaN stays)
+
+
+def _constrained(free, sub, N):
+    """free - sub, the variance left by a constraint; a difference at the rounding level of ``free`` (an entry the constraint
+    leaves no freedom, such as the only row of its set) is 0."""
+    with np.errstate(invalid="ignore"):
+        return np.where(free - sub <= 8 * N * np.finfo(np.float64).eps * free, 0.0, free - sub)
+
+
+def spectral_bounds(M, G=None, simplex_rows=None):
+    """The host half of ``spectral_diagnostics``: from the per-channel information M (n, k, k) to the Cramer-Rao bounds
+    dict(W_std, D_std (n, k), n_singular), in fp64 numpy - nothing here depends on the pixels.
+
+    ``G=None``: W is D, the information is block diagonal, S_c = M_c^-1 by Cholesky (``_spd_inverse``); a channel whose M_c fails the
+    pivot rule (a pivot not above k eps max diag(M_c)) is NaN.  Under the simplex sum_{c in rows} W[c, a] = 1 the rows of the set
+    get diag(S_c - S_c T^-1 S_c) with T the sum of S_c over the regular rows of the set (NaN rows are left out of T: they are
+    treated as held, not as free); rows outside the set keep S_c.
+    ``G`` (n, m): F[(i, a), (j, b)] = sum_c G[c, i] G[c, j] M_c[a, b], dense (m k)^2, C = F^-1 (the pivot rule with m k in place of
+    k; a singular F makes every entry NaN), under the simplex C - C A (A^T C A)^-1 A^T C with A[(i, a), b] = delta_ab for i in
+    ``simplex_rows``; W_std[i, a] = sqrt(C[(i, a), (i, a)]), D_std[c, a] = sqrt(g_c^T C_aa g_c)."""
+    M = np.asarray(M, dtype=np.float64)
+    n, k = M.shape[0], M.shape[1]
+    if G is None:
+        rows = _simplex_rows(simplex_rows, n)
+        S, bad = _spd_inverse(M)
+        var = np.einsum("cii->ci", S).copy()
+        if rows is not None:
+            reg = rows[~bad[rows]]
+            if reg.size:
+                Tinv, tbad = _spd_inverse(S[reg].sum(axis=0))
+                if tbad:
+                    var[reg] = np.nan
+                else:
+                    var[reg] = _constrained(var[reg], np.einsum("cij,jl,cli->ci", S[reg], Tinv, S[reg]), k)
+        W_std = _sqrt_var(var)
+        return dict(W_std=W_std, D_std=W_std.copy(), n_singular=int(np.isnan(W_std).any(axis=1).sum()))
+    G = np.asarray(G, dtype=np.float64)
+    m = G.shape[1]
+    rows = _simplex_rows(simplex_rows, m)
+    F = np.empty((m, k, m, k), dtype=np.float64)
+    for a in range(k):
+        for b in range(a + 1):
+            P = G.T @ (M[:, a, b][:, None] * G)
+            P = 0.5 * (P + P.T)
+            F[:, a, :, b] = P
+            F[:, b, :, a] = P
+    C, bad = _spd_inverse(F.reshape(m * k, m * k))
+
+    def variances(C):   # diag(C) as (m, k) and g_c^T C_aa g_c as (n, k)
+        C4 = C.reshape(m, k, m, k)
+        return (np.einsum("iaia->ia", C4).copy(),
+                np.stack([((G @ np.ascontiguousarray(C4[:, a, :, a])) * G).sum(axis=1) for a in range(k)], axis=1))
+
+    var_W, var_D = variances(C)
+    if not bad and rows is not None:
+        A = np.zeros((m, k, k), dtype=np.float64)
+        A[rows] = np.eye(k)
+        A = A.reshape(m * k, k)
+        CA = C @ A
+        Tinv, tbad = _spd_inverse(A.T @ CA)
+        if tbad:
+            var_W[:], var_D[:] = np.nan, np.nan
+        else:
+            sub_W, sub_D = variances(CA @ Tinv @ CA.T)
+            var_W, var_D = _constrained(var_W, sub_W, m * k), _constrained(var_D, sub_D, m * k)
+    W_std, D_std = _sqrt_var(var_W), _sqrt_var(var_D)
+    return dict(W_std=W_std, D_std=D_std, n_singular=int(np.isnan(W_std).any(axis=1).sum()))
+
+
+def spectral_diagnostics(X, D_or_W, H, *, G=None, simplex_rows=None, log_shift=log_shift, layout="cm", device=None):
+    """In which energy channels the model fails and how well every spectrum is known - the transpose side of ``pixel_diagnostics``.
+    Per channel c, with Y = max(D H, log_shift) and D = ``D_or_W`` (or ``G @ D_or_W`` with a dictionary ``G`` (n, m) and W (m, k)):
+
+    * ``channel_deviance`` (n,): 2 sum_p (x ln(x / y) - x + y), the residual spectrum - a missing line shows as a narrow band of
+      channels the model does not fit;
+    * ``sum_spectrum``, ``model_spectrum`` (n,): sum_p x and sum_p y, to plot it next to;
+    * ``M`` (n, k, k): M_c = sum_p h_p h_p^T / y_cp, the expected Fisher information of row c of D with the abundances held;
+    * ``W_std``, of W's shape: the Cramer-Rao bound of every entry of W given H, and ``D_std`` (n, k): the bound on the spectra
+      D = G W (``spectral_bounds`` holds the algebra; without G both are sqrt(diag(M_c^-1)));
+    * ``n_singular``: the rows of ``W_std`` that are NaN - channels whose M_c has a Cholesky pivot that is not above
+      k eps max diag(M_c), or all m rows when the dictionary's information matrix fails the same rule.
+
+    ``simplex_rows``: None for no constraint, True for sum_c W[c, a] = 1 over all rows of W, or the indices of the rows that sum
+    to one (a physics model's ``NMF_simplex()``).  Singular rows are left out of the constraint's sum: they stay NaN and the
+    regular rows are bounded as if the singular ones were held.
+
+    What the bound leaves out: the uncertainty of H itself, the regularisers of the fit (mu, lambda_L) and entries of W held at the
+    ``log_shift`` floor.  It is the error bar "given the abundances", as ``pixel_diagnostics`` gives the one "given the spectra".
+
+    X, ``layout``, ``device`` and the dtype rules are those of ``pixel_diagnostics``; 1..8 components; a dictionary with m k above
+    2048 raises NotImplementedError.  The pass over X is one fp64 HIP kernel that reduces over the pixels without atomics (two
+    calls give the same bits; so do the two layouts); there is no CPU path.  The step from M to the bounds does not depend on the
+    pixels and is fp64 numpy on the host.  Returns a dict of float64 numpy arrays and the int ``n_singular``."""
+    from espm_amd import _lib
+    W = np.asarray(D_or_W, dtype=np.float64)
+    if W.ndim == 2 and W.shape[1] > _lib.DIAG_MAX_K:
+        raise NotImplementedError(f"spectral_diagnostics: {W.shape[1]} components (the kernel is built for 1..{_lib.DIAG_MAX_K})")
+    if G is not None:
+        G = np.asarray(G, dtype=np.float64)
+        if G.ndim != 2 or W.ndim != 2 or G.shape[1] != W.shape[0]:
+            raise ValueError(f"G must be (channels, m) and W (m, k): got {G.shape} and {W.shape}")
+        if G.shape[1] * W.shape[1] > _SPECTRAL_MAX_F:
+            raise NotImplementedError(f"spectral_diagnostics: a dictionary of {G.shape[1]} entries x {W.shape[1]} components gives an "
+                                      f"information matrix of {G.shape[1] * W.shape[1]} rows (at most {_SPECTRAL_MAX_F})")
+        D = G @ W
+    else:
+        D = W
+    n, p, k, D, H = _diag_check(X, D, H, layout, log_shift)
+    _simplex_rows(simplex_rows, W.shape[0])   # (an index out of range: before the upload)
+    import torch
+
+    from espm_amd.engine import _ptr, _stream, require_gpu
+
+    is_dev = isinstance(X, torch.Tensor) and X.is_cuda
+    dev = require_gpu(device if device is not None else (X.device if is_dev else None))
+    nt = k * (k + 1) // 2
+    with torch.cuda.device(dev):
+        Xd = _diag_upload(X, dev)
+        code = {torch.uint8: _lib.DIAG_X_U8, torch.uint16: _lib.DIAG_X_U16, torch.float32: _lib.DIAG_X_F32,
+                torch.float64: _lib.DIAG_X_F64}[Xd.dtype]
+        Dd, Hd = torch.from_numpy(D).to(dev), torch.from_numpy(H).to(dev)
+        out = torch.empty((3 + nt) * n, dtype=torch.float64, device=dev)   # dev, xsum, ysum, then m_tri (n, nt)
+        nbytes = int(_lib.lib.espm_channel_diagnostics_scratch(n, p, k))
+        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        _lib.check(_lib.lib.espm_channel_diagnostics(_ptr(Xd), code, _lib.LAYOUT_CM if layout == "cm" else _lib.LAYOUT_PM,
+                                                     int(Xd.stride(0)), n, p, _ptr(Dd), _ptr(Hd), k, float(log_shift), _ptr(out[:n]),
+                                                     _ptr(out[n:2 * n]), _ptr(out[2 * n:3 * n]), _ptr(out[3 * n:]), _ptr(scratch),
+                                                     nbytes, _stream()))
+        host = out.cpu().numpy()
+    tri = host[3 * n:].reshape(n, nt)
+    M = np.empty((n, k, k), dtype=np.float64)
+    il, jl = np.tril_indices(k)   # row by row: (0,0), (1,0), (1,1), (2,0), ...
+    M[:, il, jl] = tri
+    M[:, jl, il] = tri
+    res = dict(channel_deviance=host[:n].copy(), sum_spectrum=host[n:2 * n].copy(), model_spectrum=host[2 * n:3 * n].copy(), M=M)
+    res.update(spectral_bounds(M, G=G, simplex_rows=simplex_rows))
+    return res

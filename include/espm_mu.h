@@ -43,6 +43,7 @@
  *   espm_surrogate_terms  <- espm/estimators/surrogates.py:6-149 (module-level surrogates)
  *   espm_pixel_diagnostics<- (new) per-pixel Poisson deviance and Cramer-Rao bound of H given the spectra; no reference analogue
  *                            (hyperspy's model fitting reports them as red_chisq and the parameters' std)
+ *   espm_channel_diagnostics <- (new) per-channel deviance, sum spectra and Fisher information of the spectra given the abundances
  *   espm_lu_pl            <- espm/estimators/updates.py:179 -> scikit-learn's _initialize_nmf -> _randomized_range_finder: the LU
  *                            normaliser of its power iterations (scipy.linalg.lu(A, permute_l=True)[0]) on tall device matrices
  *
@@ -714,6 +715,29 @@ int espm_f64_sparse_w_accum(const uint32_t* w_elem, const int64_t* w_off, const 
 #define ESPM_DIAG_X_F64 3
 int espm_pixel_diagnostics(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, const double* d, const double* h, int k,
                            double log_shift, int simplex, double* dev, double* h_std, int32_t* n_singular, espm_stream_t stream);
+
+/* ---- channel diagnostics (csrc/mu_diag_chan.hip; espm_amd.measures.spectral_diagnostics, NMFEstimator.spectral_diagnostics) ----
+ * The transpose side of the pixel diagnostics: in which energy channels a fitted model fails and how well every spectrum is known,
+ * in one fp64 pass over X that reduces over the pixels.  x, x_dtype (ESPM_DIAG_X_*), x_layout, ld, d (n, k), h (k, p) and log_shift
+ * are exactly as for espm_pixel_diagnostics.  With Y = max(d h, log_shift), per channel c (all outputs fp64):
+ *   dev[c]       = 2 sum_p (x ln(x / y) - x + y), the first term 0 where x == 0: the residual spectrum
+ *   xsum[c]      = sum_p x, the measured sum spectrum (exact for counts: the sums stay below 2^53)
+ *   ysum[c]      = sum_p y, the modelled sum spectrum
+ *   m_tri[c, t]  (n, k (k + 1) / 2): the lower triangle, row by row ((0,0), (1,0), (1,1), (2,0), ...), of
+ *                  M_c = sum_p h_p h_p^T / y_cp, the expected Fisher information of row c of d with the abundances held.  The
+ *                  information of W in d = G W follows without another pass: F = sum_c (g_c g_c^T) (x) M_c.
+ * A workgroup takes ESPM_CDIAG_BLOCK channels (one per thread) and ESPM_CDIAG_PCHUNK pixels and writes its partial sums to
+ * `scratch` (device memory, espm_channel_diagnostics_scratch(n, p, k) bytes: chunks x (3 + k (k + 1) / 2) x n doubles); a second
+ * launch on `stream` adds the chunks in ascending order.  Nothing is accumulated atomically: two calls give the same bits, and so
+ * do the two layouts of one image.  k = 1..ESPM_DIAG_MAX_K.  ESPM_EINVAL for a null pointer, a layout or dtype that does not
+ * exist, ld below the row length, n or p below 1, or scratch_bytes below what the query returns (the message names both sizes).
+ * Only the narrow build has the kernels; the wide builds return ESPM_EUNSUPPORTED, and their query returns 0. */
+#define ESPM_CDIAG_BLOCK 256     /* channels (threads) per workgroup                                                          */
+#define ESPM_CDIAG_PCHUNK 2048   /* pixels per workgroup: 2048 channels x 512^2 pixels are 8 x 128 workgroups                  */
+int espm_channel_diagnostics(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, const double* d, const double* h, int k,
+                             double log_shift, double* dev, double* xsum, double* ysum, double* m_tri, void* scratch,
+                             size_t scratch_bytes, espm_stream_t stream);
+size_t espm_channel_diagnostics_scratch(int n, int p, int k);
 
 #ifdef __cplusplus
 }

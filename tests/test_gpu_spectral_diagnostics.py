@@ -1,0 +1,236 @@
+"""spectral_diagnostics on the GPU (csrc/mu_diag_chan.hip) against the numpy fp64 reference of tests/spectral_reference.py, whose
+docstring derives the bounds used here (deviance 8 p eps sum |t|; sums of counts exact; model_spectrum and M 4 (p + k) eps relative;
+W_std and D_std 8 k (p + k) eps cond relative).
+
+The parity shapes are the smallest that cross every boundary of the kernel: three pixel chunks with a ragged tail
+(2 ESPM_CDIAG_PCHUNK + 155), 64 pixels (less than a chunk and than a workgroup), 70 and 256 + 52 channels (one and two channel
+blocks, neither a multiple of it), one to eight components, both layouts, the four dtypes, a row stride above the row length.
+Every image holds a pixel without counts, an all-zero channel and a row of D that is 0."""
+import numpy as np
+import pytest
+
+import diag_reference as dr
+import spectral_reference as sr
+from test_gpu_pixel_diagnostics import ESTIMATORS, GRID, K, N, _fit_image, quiet
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def measures():
+    from espm_amd import measures
+    return measures
+
+
+def _p(p):
+    from espm_amd import _lib
+    return 2 * _lib.CDIAG_PCHUNK + 155 if p is None else p
+
+
+def _as_input(X, layout, padded):
+    """X (n, p) in the layout asked for; ``padded``: a device tensor whose rows are 12 elements longer than they say, filled with 999
+    (255 in 8 bits): counts that must not be read."""
+    import torch
+    Xin = X if layout == "cm" else np.ascontiguousarray(X.T)
+    if padded:
+        wide = np.full((Xin.shape[0], Xin.shape[1] + 12), 255 if Xin.dtype == np.uint8 else 999, dtype=Xin.dtype)
+        wide[:, :Xin.shape[1]] = Xin
+        Xin = torch.from_numpy(wide).to("cuda")[:, :Xin.shape[1]]
+        assert Xin.stride(0) == wide.shape[1]
+    return Xin
+
+
+# (n, p or None for "two pixel chunks + 155", k, layout, dtype, padded row stride)
+PARITY = [
+    (70, None, 3, "cm", "float32", False),
+    (70, None, 8, "pm", "uint8", False),
+    (308, 300, 5, "pm", "uint16", True),
+    (70, 64, 1, "cm", "float64", False),
+    (308, 667, 5, "cm", "uint8", True),
+    (70, 64, 8, "pm", "float64", False),
+]
+
+
+@pytest.mark.parametrize("n,p,k,layout,dtype,padded", PARITY, ids=[f"n{c[0]}_k{c[2]}_{c[3]}_{c[4]}" for c in PARITY])
+def test_parity_with_numpy(measures, n, p, k, layout, dtype, padded):
+    p = _p(p)
+    X, D, H, facts = dr.image(n, p, k, dtype, False)
+    Xin = _as_input(X, layout, padded)
+    integer = dtype != "float64"
+    for rows in (None, True):
+        ref = sr.reference(X, D, H, simplex_rows=rows)
+        assert ref["cond_max"] < 1e8, "the parity images must stay away from the NaN rule"
+        out = measures.spectral_diagnostics(Xin, D, H, simplex_rows=rows, layout=layout)
+        for name, shape in (("channel_deviance", (n,)), ("sum_spectrum", (n,)), ("model_spectrum", (n,)), ("M", (n, k, k)),
+                            ("W_std", (n, k)), ("D_std", (n, k))):
+            assert out[name].dtype == np.float64 and out[name].shape == shape, name
+        assert out["n_singular"] == 0 and np.array_equal(out["M"], out["M"].transpose(0, 2, 1))
+        sr.check(out, ref, p, k, f"n={n} p={p} k={k} {layout} {dtype} rows={rows}", integer=integer)
+    # the floor is active in the row of D that is 0: M_c = H H^T / log_shift, and the one count there adds x ln(x / log_shift)
+    fc = facts["floor_channel"]
+    assert out["channel_deviance"][fc] > 2 * (3 * np.log(3 / dr.LOG_SHIFT) - 3) - 1e-6
+    assert out["sum_spectrum"][fc] == 3 and out["sum_spectrum"][facts["zero_channel"]] == 0
+    np.testing.assert_allclose(out["model_spectrum"][fc], p * dr.LOG_SHIFT, rtol=1e-12)
+    # the other layout of the same image: the same accumulation in the same order
+    other = measures.spectral_diagnostics(np.ascontiguousarray(X.T) if layout == "cm" else X, D, H, simplex_rows=True,
+                                          layout="pm" if layout == "cm" else "cm")
+    assert all(np.array_equal(other[a], out[a]) for a in ("channel_deviance", "sum_spectrum", "model_spectrum", "M", "W_std"))
+
+
+DICT = [(70, None, 3, "pm", "float32"), (308, 300, 5, "cm", "uint16")]
+
+
+@pytest.mark.parametrize("n,p,k,layout,dtype", DICT, ids=[f"n{c[0]}_k{c[2]}_{c[3]}_{c[4]}" for c in DICT])
+def test_dictionary_parity(measures, n, p, k, layout, dtype):
+    p = _p(p)
+    X, G, W, H, _ = sr.dict_image(n, p, k, dtype)
+    Xin = _as_input(X, layout, False)
+    for rows in (None, True, np.array([0, 2, 5])):
+        ref = sr.reference(X, W, H, G=G, simplex_rows=rows)
+        assert ref["cond_max"] < 1e8
+        out = measures.spectral_diagnostics(Xin, W, H, G=G, simplex_rows=rows, layout=layout)
+        assert out["W_std"].shape == (sr.M_DICT, k) and out["D_std"].shape == (n, k) and out["n_singular"] == 0
+        sr.check(out, ref, p, k, f"dictionary n={n} p={p} k={k} {layout} {dtype} rows={rows}")
+
+
+def test_other_dtypes_a_device_tensor_and_a_second_call(measures):
+    """int32, float16 and int64 images are converted to a dtype that holds them exactly; a device tensor gives what the host array
+    gives; two calls give the same bits (no atomics on doubles)."""
+    import torch
+    p = _p(None)
+    X, D, H, _ = dr.image(70, p, 3, "float32", False)
+    Xi = np.minimum(X.astype(np.float64), 2000.0)
+    want = measures.spectral_diagnostics(Xi, D, H, simplex_rows=True)
+    names = ("channel_deviance", "sum_spectrum", "model_spectrum", "M", "W_std", "D_std")
+    for other in (Xi.astype(np.int32), Xi.astype(np.float16), Xi.astype(np.int64), torch.from_numpy(Xi).to("cuda"),
+                  torch.from_numpy(Xi.astype(np.int64)).to("cuda"), Xi):
+        got = measures.spectral_diagnostics(other, D, H, simplex_rows=True)
+        assert all(np.array_equal(got[a], want[a]) for a in names)
+
+
+# ---- singular cases -------------------------------------------------------------------------------------------------------------
+def test_identical_abundances_make_every_channel_singular(measures):
+    n, p = 70, 300
+    X, D, H, _ = dr.image(n, p, 2, "float32", False)
+    H = np.array(H)
+    H[1] = H[0]
+    ref = sr.reference(X, D, H)
+    for rows in (None, True):
+        out = measures.spectral_diagnostics(X, D, H, simplex_rows=rows)
+        assert np.isnan(out["W_std"]).all() and np.isnan(out["D_std"]).all() and out["n_singular"] == n
+        sr.check(out, ref, p, 2, f"singular rows={rows}", stds=False)
+
+
+def test_identical_dictionary_columns_make_F_singular(measures):
+    n, p, k = 70, 300, 2
+    X, G, W, H, _ = sr.dict_image(n, p, k, "float32")
+    G = np.array(G)
+    G[:, 4] = G[:, 1]
+    ref = sr.reference(X, W, H, G=G)
+    for rows in (None, True):
+        out = measures.spectral_diagnostics(X, W, H, G=G, simplex_rows=rows)
+        assert np.isnan(out["W_std"]).all() and np.isnan(out["D_std"]).all() and out["n_singular"] == sr.M_DICT
+        sr.check(out, ref, p, k, f"singular F rows={rows}", stds=False)
+
+
+# ---- the estimator --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(ESTIMATORS))
+def test_estimator_method(measures, name):
+    from espm_amd import hyperspy_adapter as ha
+    from espm_amd.estimators import SmoothNMF
+    cfg = dict(ESTIMATORS[name])
+    X, G = _fit_image(cfg.pop("with_G"))
+    fp64 = cfg.pop("fp64", False)
+    p = X.shape[1]
+    simplex_W = not cfg["simplex_H"]
+    est = SmoothNMF(n_components=K, G=G, shape_2d=GRID, max_iter=30, tol=0.0, verbose=0, random_state=0, simplex_W=simplex_W, **cfg)
+    if fp64:
+        est.set_precision("fp64")
+    Xin = np.ascontiguousarray(X.T) if cfg["hspy_comp"] else X
+    quiet(est.fit, Xin)
+    with pytest.raises(AttributeError, match="spectral_diagnostics"):
+        ha.diagnostic_spectra(est)
+    kept = {a: np.array(getattr(est, a), copy=True) for a in ("W_", "H_", "G_", "components_")}
+    kept["X_"], losses = np.array(np.asarray(est.X_), copy=True), list(est.losses_)
+
+    out = est.spectral_diagnostics(Xin)   # (pixels, channels) with hspy_comp: read as such
+    W, H = np.asarray(est.W_, dtype=np.float64), np.asarray(est.H_, dtype=np.float64)
+    Gd = None if G is None else np.asarray(est.G_, dtype=np.float64)
+    rows = True if simplex_W else None
+    want = measures.spectral_diagnostics(X, W, H, G=Gd, simplex_rows=rows, log_shift=est.log_shift)
+    attrs = dict(channel_deviance_="channel_deviance", sum_spectrum_="sum_spectrum", model_spectrum_="model_spectrum", W_std_="W_std",
+                 D_std_="D_std")
+    for attr, key in attrs.items():
+        assert np.array_equal(getattr(est, attr), want[key]) and np.array_equal(out[key], want[key]), attr
+    assert est.W_std_.shape == est.W_.shape and est.D_std_.shape == (N, K) and est.channel_deviance_.shape == (N,)
+    assert out["n_singular"] == want["n_singular"] == 0
+    ref = sr.reference(X, W, H, G=Gd, simplex_rows=rows, log_shift=est.log_shift)
+    assert ref["cond_max"] < 1e8
+    sr.check(want, ref, p, K, f"{name}: X passed")
+
+    none = est.spectral_diagnostics()   # the fit's X_ un-scaled: the same image to rounding (it has no empty lines)
+    sr.check(none, ref, p, K, f"{name}: X=None", integer=not cfg["normalize"])
+
+    for a, v in kept.items():
+        assert np.array_equal(np.asarray(getattr(est, a)), v), f"{a} changed"
+    assert list(est.losses_) == losses
+
+    dev, xs, ys, band = ha.diagnostic_spectra(est)
+    assert dev.shape == xs.shape == ys.shape == (N,) and band.shape == (K, N) and band[1, 7] == est.D_std_[7, 1]
+
+    with pytest.raises(ValueError, match="channels"):
+        est.spectral_diagnostics(Xin[:-1] if not cfg["hspy_comp"] else Xin[:, :-1])
+    with pytest.raises(ValueError, match="pixels"):
+        est.spectral_diagnostics(Xin[:, :-1] if not cfg["hspy_comp"] else Xin[:-1])
+
+
+def test_estimator_refusals(measures, monkeypatch):
+    from sklearn.exceptions import NotFittedError
+
+    from espm_amd.estimators import SmoothNMF
+    X, _ = _fit_image(False)
+    with pytest.raises(NotFittedError):
+        SmoothNMF(n_components=K).spectral_diagnostics(X)
+    nine = SmoothNMF(n_components=9, max_iter=3, tol=0.0, verbose=0, random_state=0)
+    quiet(nine.fit, X)
+    fixed = -np.ones((N, K))
+    fixed[5, 1] = 0.7
+    held = SmoothNMF(n_components=K, max_iter=3, tol=0.0, verbose=0, random_state=0, fixed_W=fixed, simplex_W=False, simplex_H=True)
+    quiet(held.fit, X)
+    monkeypatch.setattr(measures, "_diag_upload", lambda *a, **k: pytest.fail("the upload was reached"))
+    for est, what in ((nine, "9 components"), (held, "fixed_W")):
+        with pytest.raises(NotImplementedError, match=what):
+            est.spectral_diagnostics(X)
+        with pytest.raises(NotImplementedError, match=what):
+            est.spectral_diagnostics()
+        assert not hasattr(est, "channel_deviance_")
+
+
+# ---- what the number means ------------------------------------------------------------------------------------------------------
+def test_w_std_is_the_spread_of_the_estimates(measures):
+    """4000 channels that share one true row d0 (k = 3), 300 pixels with a fixed seeded H, X ~ Poisson(d0 H) drawn per channel: given
+    H the rows of W are independent, so the channels of one image are the Monte Carlo.  W alone is fitted by 300 multiplicative
+    iterations from the truth (every entry of H held by ``fixed_H``; no simplex, no regulariser, no normalisation): the empirical
+    standard deviation over the channels of each column of the estimates lies within 10 % of the mean W_std of that column.  The
+    sampling error of a standard deviation over 4000 draws is 1.1 % and the bound is asymptotic at this dose (~3500 counts per
+    channel); 10 % catches a wrong formula (a factor of 2, a missing square root, M inverted the wrong way round), it is not a
+    measurement.  The dose keeps every estimate far above the log_shift floor, which is asserted."""
+    from espm_amd.engine import MUEngine
+    n, k, p = 4000, 3, 300
+    rng = np.random.default_rng(42)
+    d0 = np.array([20.0, 12.0, 8.0])
+    H = rng.random((k, p)) + 0.1
+    X = rng.poisson(np.tile((d0 @ H)[None, :], (n, 1))).astype(np.float64)
+    W0 = np.tile(d0[None, :], (n, 1))
+    eng = MUEngine(X, k, simplex_H=False, simplex_W=False, fixed_H=H, tol=0.0, max_iter=300, fix_zero_lines=False, device="cuda:0")
+    eng.load_state(W0, H)
+    eng.iterate(300)
+    W_est = np.asarray(eng.get_W(), dtype=np.float64)
+    np.testing.assert_allclose(np.asarray(eng.get_H(), dtype=np.float64), H, rtol=1e-6)   # (held: W alone was fitted)
+    assert W_est.shape == (n, k) and W_est.min() > 0.5, "an estimate at the floor: the bound does not apply"
+    spread = W_est.std(axis=0, ddof=1)
+    out = measures.spectral_diagnostics(X, W_est, H)
+    bar = out["W_std"].mean(axis=0)
+    print(f"mean estimate {W_est.mean(axis=0)}, empirical std {spread}, mean W_std {bar}, ratio {spread / bar}")
+    assert out["n_singular"] == 0
+    assert (np.abs(spread / bar - 1) < 0.10).all()
