@@ -29,6 +29,7 @@ F64S_MAX_COUNT, F64S_MAX_N, F64S_WBLOCK = _D["ESPM_F64S_MAX_COUNT"], _D["ESPM_F6
 DIAG_X_U8, DIAG_X_U16, DIAG_X_F32, DIAG_X_F64 = (_D["ESPM_DIAG_X_" + n] for n in ("U8", "U16", "F32", "F64"))
 DIAG_MAX_K, DIAG_BLOCK, DIAG_CHUNK = _D["ESPM_DIAG_MAX_K"], _D["ESPM_DIAG_BLOCK"], _D["ESPM_DIAG_CHUNK"]
 CDIAG_BLOCK, CDIAG_PCHUNK = _D["ESPM_CDIAG_BLOCK"], _D["ESPM_CDIAG_PCHUNK"]
+BIN_BLOCK, BIN_PARTS = _D["ESPM_BIN_BLOCK"], _D["ESPM_BIN_PARTS"]
 SRC_F32, SRC_F64 = 0, 1
 LAYOUT_CM, LAYOUT_PM = 0, 1
 ABI_VERSION = _D["ESPM_MU_ABI_VERSION"]
@@ -153,6 +154,10 @@ SYMBOLS = {
     "espm_channel_diagnostics": (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp,
                                            _vp, C.c_size_t, _vp]),
     "espm_channel_diagnostics_scratch": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    # pixel binning (csrc/mu_binning.hip): narrow build only, plain device pointers (the candidate bins: a host array of int32 pairs)
+    "espm_rebin_pixels": (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _i64, _vp]),
+    "espm_binning_sums": (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp]),
+    "espm_binning_sums_scratch": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
 }
 
 

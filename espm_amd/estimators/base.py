@@ -261,6 +261,8 @@ class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
         they stand for): validation, ingest (for a large X: ONE upload whose scans replace the reference's host passes), the initial W / H / G, the
         engine, the iteration loop with the stop rules, the results."""
         import types
+        for name in ("bin_", "binned_shape_2d_", "W_binned_", "H_binned_"):   # (fit_binned sets them again after its coarse fit)
+            self.__dict__.pop(name, None)
         f = types.SimpleNamespace()
         self._fit_validate(f, X)
         self._fit_ingest(f)
@@ -757,6 +759,78 @@ class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
                 say(f"It {n} / {self.max_iter}: loss {eval_after:3e}")
             eval_before = eval_after
 
+    # ---- fit on the binned image, abundances at full resolution ------------------------------------------------------------------
+    def fit_binned(self, X, bin, y=None, W=None):
+        """Fit the spectra on the image binned by ``bin = (by, bx)`` and return H at full resolution (H.T with ``hspy_comp``): the
+        workflow the reference leaves to the user around ``estimate_best_binning`` (eds_spim.py:746-798) - decompose the binned
+        map, read the abundances back on the pixels - with the scaling between the two carried here.
+
+        1. ``espm_amd.binning.rebin`` sums X over the bins on the device; ``fit_transform`` runs on the binned image with
+           ``shape_2d`` set to the binned grid (``lambda_L`` acts on that grid with the value given; ``W``: its initial W).  Kept:
+           ``bin_``, ``binned_shape_2d_``, ``W_binned_``, ``H_binned_`` (a later plain fit removes them); ``n_iter_``, ``losses_``
+           and ``X_`` stay the coarse fit's: ``X_`` is the binned image, so ``pixel_diagnostics`` / ``spectral_diagnostics`` ask
+           for the full-resolution X instead of taking ``X_`` (ValueError with ``X=None``).
+        2. A pixel's model is its bin's model over B = by bx.  Under ``normalize``: ``norm_factor_`` times B - the value
+           ``normalization_factor`` gives for X itself - and ``W_ = W_binned_ / B``, so that ``W_ * norm_factor_`` is the normalised
+           W the coarse fit ended with.  Without: ``W_ = W_binned_ / B``, except under ``simplex_W``, where W keeps its simplex and H
+           carries the 1 / B.
+        3. ``H_ = unmix(X, H=H0)``: the H-only fit of X against ``W_``, started from every pixel's bin column of the coarse H
+           (over B where W kept its simplex; renormalised under ``simplex_H``).  ``transform_n_iter_``, ``transform_losses_``,
+           ``transform_rel_`` and ``transform_path_`` hold the record of this stage; ``shape_2d`` is the full grid again.
+
+        X: a host array, (channels, pixels), or (pixels, channels) with ``hspy_comp``; the binned image comes back to the host for
+        the coarse fit (it is B times smaller).  Sharded and fp64 fits are out of scope.  Refused before anything is uploaded: whatever ``unmix`` refuses (linesearch,
+        algo='projected_gradient', l2=True, shard(), fp64 mode) and ``fixed_H``, which belongs to full-resolution pixels
+        (NotImplementedError); ``shape_2d`` unset, or factors that do not divide the image (ValueError: the message names the crop
+        that would)."""
+        from espm_amd import binning
+        why = self._transform_refusal()
+        if why is not None:
+            raise NotImplementedError(f"fit_binned does not cover {why}")
+        if self.fixed_H is not None:
+            raise NotImplementedError("fit_binned does not cover fixed_H: its entries belong to full-resolution pixels")
+        if self.shape_2d is None:
+            raise ValueError("fit_binned needs the grid of the pixels: build the estimator with shape_2d=(rows, columns)")
+        by, bx = binning._check_bin(bin)
+        full = (int(self.shape_2d[0]), int(self.shape_2d[1]))
+        ny, nx = full
+        if ny % by or nx % bx:
+            raise ValueError(f"bin {(by, bx)} does not divide the image {full}: crop it to {(ny - ny % by, nx - nx % bx)}")
+        layout = "pm" if self.hspy_comp else "cm"
+        Xb = binning.rebin(X, full, (by, bx), layout=layout)   # (ValueError when shape_2d does not match X)
+        coarse = (ny // by, nx // bx)
+        given_shape = self.shape_2d
+        self.shape_2d = coarse
+        try:
+            self.fit_transform(Xb, W=W)
+        finally:
+            self.shape_2d = given_shape
+        B = by * bx
+        self.bin_, self.binned_shape_2d_ = (by, bx), coarse
+        self.W_binned_, self.H_binned_ = self.W_, self.H_
+        k = self.H_binned_.shape[0]
+        H0 = np.asarray(self.H_binned_, dtype=np.float64).reshape(k, coarse[0], coarse[1]).repeat(by, axis=1).repeat(bx, axis=2).reshape(k, ny * nx)
+        if self.normalize:
+            self.norm_factor_ = self.norm_factor_ * B
+            self.W_ = self.W_binned_ / B
+        elif self.simplex_W:
+            H0 = H0 / B
+        else:
+            self.W_ = self.W_binned_ / B
+        if self.simplex_H:
+            H0 = H0 / H0.sum(axis=0, keepdims=True)
+        self._L_cache, self._L_pixels = None, ny * nx
+        Hn = self.unmix(X, H=H0.T if self.hspy_comp else H0)
+        self.H_ = Hn.T if self.hspy_comp else Hn
+        self.components_ = (self.G_ @ self.W_).T if self.hspy_comp else self.H_
+        return Hn
+
+    def _refuse_binned_X(self, who):
+        """After fit_binned, X_ is the BINNED image while W_, H_ and norm_factor_ belong to full-resolution pixels."""
+        if getattr(self, "bin_", None) is not None:
+            raise ValueError(f"{who}: this estimator was fitted by fit_binned with bin {self.bin_}: X_ holds the binned image, "
+                             "H_ the full-resolution pixels - pass the full-resolution X")
+
     # ---- diagnostics of the fit: where it fails, and an error bar on every abundance ---------------------------------------------
     def pixel_diagnostics(self, X=None):
         """Per-pixel deviance and error bars of ``H_`` (``espm_amd.measures.pixel_diagnostics`` on ``G_ @ W_`` and ``H_``; the reference
@@ -786,6 +860,7 @@ class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
         layout = "cm"
         if X is None:
             check_is_fitted(self, "X_")
+            self._refuse_binned_X("pixel_diagnostics")
             X = np.asarray(self._X_fixed())
         else:
             if not hasattr(X, "shape") or getattr(X, "ndim", 0) != 2:
@@ -839,6 +914,7 @@ class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
         layout = "cm"
         if X is None:
             check_is_fitted(self, "X_")
+            self._refuse_binned_X("spectral_diagnostics")
             X = np.asarray(self._X_fixed())
         else:
             if not hasattr(X, "shape") or getattr(X, "ndim", 0) != 2:

@@ -20,6 +20,9 @@ What is here:
 * ``decompose(signal, est)`` - ``signal.decomposition(algorithm=est)`` on a real hyperspy signal (or a ``SpectrumImage``)
   with the checks the reference leaves to the user: ``hspy_comp`` must be on, ``shape_2d`` is taken from the signal when the
   estimator has none (the Laplacian needs the image grid, base.py:286-291).
+* ``SpectrumImage.rebin`` / ``.estimate_best_binning`` (eds_spim.py:746-798 on integer factors, ``espm_amd.binning``) and
+  ``decompose(signal, est, bin=(by, bx))``: the spectra fitted on the binned map, loadings at full resolution
+  (``NMFEstimator.fit_binned``).
 * ``hyperspy_extension.yaml`` (next to this file) and the ``hyperspy.extensions`` entry point in ``pyproject.toml`` declare
   the signal type ``EDS_espm_amd`` -> ``EDSespmAMD`` below, defined only when hyperspy imports.
 """
@@ -69,14 +72,28 @@ class SpectrumImage:
         ny, nx, n = self.data.shape
         return self.data.reshape((ny * nx, n))
 
-    def decomposition(self, algorithm, output_dimension=None, return_info=False, **kwargs):
+    def rebin(self, bin):
+        """A new ``SpectrumImage`` of the sums over (by, bx) blocks of pixels (``espm_amd.binning.rebin`` on the device; the last
+        bin row and column are smaller when the factors do not divide the image)."""
+        from espm_amd import binning
+        gny, gnx = binning.binned_shape(self.shape_2d, bin)
+        return SpectrumImage(binning.rebin(self.unfolded(), self.shape_2d, bin, layout="pm").reshape((gny, gnx, self.data.shape[2])))
+
+    def estimate_best_binning(self, bins=None, inspect=False):
+        """The (by, bx) of least estimated risk among ``bins`` (by default the square bins up to half the image), or with
+        ``inspect=True`` (risk of every candidate, best): eds_spim.py:746-798 on integer factors (``espm_amd.binning``)."""
+        from espm_amd import binning
+        return binning.estimate_best_binning(self.unfolded(), self.shape_2d, bins=bins, inspect=inspect, layout="pm")
+
+    def decomposition(self, algorithm, output_dimension=None, return_info=False, bin=None, **kwargs):
         """hyperspy's ``decomposition(algorithm=<object>)`` for a custom estimator: ``fit_transform(data (p, n))`` ->
-        loadings (p, k), ``components_`` (k, n) -> factors (n, k); the estimator stays in ``learning_results``."""
+        loadings (p, k), ``components_`` (k, n) -> factors (n, k); the estimator stays in ``learning_results``.  ``bin=(by, bx)``:
+        ``algorithm.fit_binned`` instead - the spectra fitted on the binned image, the loadings at full resolution."""
         if not hasattr(algorithm, "fit_transform"):
             raise ValueError("algorithm must implement fit_transform() (scikit-learn style)")
         if kwargs:
             raise TypeError(f"unsupported decomposition arguments for a custom algorithm: {sorted(kwargs)}")
-        loadings = algorithm.fit_transform(self.unfolded())
+        loadings = algorithm.fit_transform(self.unfolded()) if bin is None else algorithm.fit_binned(self.unfolded(), bin)
         factors = np.asarray(algorithm.components_).T
         lr = self.learning_results
         lr.decomposition_algorithm = algorithm
@@ -136,15 +153,29 @@ def register():
     return True
 
 
-def decompose(signal, est, **kwargs):
-    """``signal.decomposition(algorithm=est)`` with the estimator set up for hyperspy's calling convention."""
+def decompose(signal, est, bin=None, **kwargs):
+    """``signal.decomposition(algorithm=est)`` with the estimator set up for hyperspy's calling convention.  ``bin=(by, bx)``
+    routes to ``est.fit_binned``: the spectra are fitted on the binned image and ``learning_results`` holds full-resolution
+    loadings (a ``SpectrumImage``, or any signal with ``shape_2d`` and a (pixels, channels) view of its data)."""
     if not getattr(est, "hspy_comp", False):
         raise ValueError("hyperspy hands (pixels, channels) to the estimator: build it with hspy_comp=True "
                          "(espm/estimators/base.py:249-259 only warns)")
     if getattr(est, "shape_2d", None) is None and hasattr(signal, "shape_2d"):
         est.shape_2d = tuple(int(v) for v in signal.shape_2d)
     register()
-    signal.decomposition(algorithm=est, **kwargs)
+    if bin is None:
+        signal.decomposition(algorithm=est, **kwargs)
+    elif isinstance(signal, SpectrumImage):
+        signal.decomposition(algorithm=est, bin=bin, **kwargs)
+    else:   # (hyperspy's own decomposition knows no bin: its results are filled as it fills them for a custom algorithm)
+        if kwargs:
+            raise TypeError(f"unsupported decomposition arguments with bin: {sorted(kwargs)}")
+        data = np.asarray(signal.data)
+        loadings = est.fit_binned(data.reshape((-1, data.shape[-1])), bin)
+        lr = signal.learning_results
+        lr.decomposition_algorithm = est
+        lr.loadings, lr.factors = np.asarray(loadings), np.asarray(est.components_).T
+        lr.output_dimension = lr.factors.shape[1]
     return signal.learning_results
 
 

@@ -44,6 +44,8 @@
  *   espm_pixel_diagnostics<- (new) per-pixel Poisson deviance and Cramer-Rao bound of H given the spectra; no reference analogue
  *                            (hyperspy's model fitting reports them as red_chisq and the parameters' std)
  *   espm_channel_diagnostics <- (new) per-channel deviance, sum spectra and Fisher information of the spectra given the abundances
+ *   espm_rebin_pixels, espm_binning_sums <- espm/datasets/eds_spim.py:746-798 (estimate_best_binning) on integer factors: the bin sums and
+ *                            the four sums its risk estimate reduces to, from X on the device instead of a rebin and an upsample per candidate
  *   espm_lu_pl            <- espm/estimators/updates.py:179 -> scikit-learn's _initialize_nmf -> _randomized_range_finder: the LU
  *                            normaliser of its power iterations (scipy.linalg.lu(A, permute_l=True)[0]) on tall device matrices
  *
@@ -738,6 +740,35 @@ int espm_channel_diagnostics(const void* x, int x_dtype, int x_layout, int64_t l
                              double log_shift, double* dev, double* xsum, double* ysum, double* m_tri, void* scratch,
                              size_t scratch_bytes, espm_stream_t stream);
 size_t espm_channel_diagnostics_scratch(int n, int p, int k);
+
+/* ---- pixel binning (csrc/mu_binning.hip; espm_amd.binning, NMFEstimator.fit_binned) ----
+ * The image is ny x nx pixels, row-major (pixel y * nx + x), n channels: x, x_dtype (ESPM_DIAG_X_*), x_layout and ld as for the
+ * diagnostics, with p = ny * nx.  A bin (by, bx), both >= 1, puts pixel (y, x) into bin (y / by, x / bx) of a grid of
+ * ceil(ny / by) x ceil(nx / bx) bins; the factors need not divide the image (the last bin row and column hold fewer pixels, n_g of
+ * them) and a factor above the axis is the whole axis.  S_gc is the sum of x over the pixels of bin g in channel c.
+ *   espm_rebin_pixels   out[c, g] = S_gc in the input's layout on the binned grid - (n, bins) with rows out_ld apart for
+ *                       ESPM_LAYOUT_CM, (bins, n) for ESPM_LAYOUT_PM - as out_dtype ESPM_DIAG_X_F32 or ESPM_DIAG_X_F64.  Integer input is
+ *                       summed exactly in integers, floating-point input in fp64; rounded once on the store.  One launch.
+ *   espm_binning_sums   bins: a HOST array of n_bins (by, bx) pairs.  out (device, 2 + 2 n_bins doubles): T1 = sum x and T2 = sum x^2
+ *                       over the cube, then per candidate A = sum_gc S_gc^2 / n_g and C = sum_gc S_gc / n_g - what the risk estimate
+ *                       of eds_spim.py:787-793 is made of: with K = p, L = n, var = C / (K L), bias = (T2 - T1 - A + C) / (K L),
+ *                       risk = var K / L + bias.  One pass over X per candidate and one for the totals, each by ESPM_BIN_PARTS
+ *                       workgroups that write their partial sums to `scratch` (device, espm_binning_sums_scratch(n, ny, nx, n_bins)
+ *                       bytes: (2 + 2 n_bins) x ESPM_BIN_PARTS doubles, and 128 x ESPM_BIN_PARTS more
+ *                       through which a pixel-major candidate with few, large bins goes in slabs of image rows that a second launch
+ *                       joins); a last launch adds the partial sums in ascending order.
+ * Nothing is accumulated atomically and every order of additions follows from the shapes alone: two calls give the same bits.
+ * ESPM_EINVAL, before the device is touched, for a null pointer, a layout or dtype that does not exist, ld or out_ld below the row
+ * length, n, ny or nx below 1, 2^31 pixels or more, a factor below 1, n_bins below 1, or scratch_bytes below what the query returns
+ * (the message names both sizes).  Only the narrow build has the kernels; the wide builds return ESPM_EUNSUPPORTED, and their query
+ * returns 0. */
+#define ESPM_BIN_BLOCK 256     /* threads per workgroup: columns of a strip (channel-major), 64 channels x 4 (pixel-major)       */
+#define ESPM_BIN_PARTS 2048    /* workgroups, and partial sums per slot of the scratch, of every launch of espm_binning_sums  */
+int espm_rebin_pixels(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int ny, int nx, int by, int bx, void* out,
+                      int out_dtype, int64_t out_ld, espm_stream_t stream);
+int espm_binning_sums(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int ny, int nx, const int32_t* bins, int n_bins,
+                      double* out, void* scratch, size_t scratch_bytes, espm_stream_t stream);
+size_t espm_binning_sums_scratch(int n, int ny, int nx, int n_bins);
 
 #ifdef __cplusplus
 }
