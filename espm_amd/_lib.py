@@ -30,6 +30,7 @@ DIAG_X_U8, DIAG_X_U16, DIAG_X_F32, DIAG_X_F64 = (_D["ESPM_DIAG_X_" + n] for n in
 DIAG_MAX_K, DIAG_BLOCK, DIAG_CHUNK = _D["ESPM_DIAG_MAX_K"], _D["ESPM_DIAG_BLOCK"], _D["ESPM_DIAG_CHUNK"]
 CDIAG_BLOCK, CDIAG_PCHUNK = _D["ESPM_CDIAG_BLOCK"], _D["ESPM_CDIAG_PCHUNK"]
 BIN_BLOCK, BIN_PARTS = _D["ESPM_BIN_BLOCK"], _D["ESPM_BIN_PARTS"]
+SPLIT_BLOCK, SPLIT_HEAVY, SPLIT_MAX_K = _D["ESPM_SPLIT_BLOCK"], _D["ESPM_SPLIT_HEAVY"], _D["ESPM_SPLIT_MAX_K"]
 SRC_F32, SRC_F64 = 0, 1
 LAYOUT_CM, LAYOUT_PM = 0, 1
 ABI_VERSION = _D["ESPM_MU_ABI_VERSION"]
@@ -158,6 +159,10 @@ SYMBOLS = {
     "espm_rebin_pixels": (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _i64, _vp]),
     "espm_binning_sums": (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp]),
     "espm_binning_sums_scratch": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    # count splitting (csrc/mu_split.hip): narrow build only, plain device pointers
+    "espm_thin_counts": (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int, _i64, _i64, _i64, C.c_uint64, _vp, _vp, _i64, _vp]),
+    "espm_split_deviance": (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int, _i64, _i64, _i64, C.c_uint64, _vp, _vp, C.c_int, C.c_double,
+                                      _vp, _vp, _vp, _vp]),
 }
 
 

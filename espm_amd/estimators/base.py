@@ -263,6 +263,8 @@ class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
         import types
         for name in ("bin_", "binned_shape_2d_", "W_binned_", "H_binned_"):   # (fit_binned sets them again after its coarse fit)
             self.__dict__.pop(name, None)
+        for name in self._SPLIT_ATTRIBUTES:   # (and fit_split its own, after the fit of the training part)
+            self.__dict__.pop(name, None)
         f = types.SimpleNamespace()
         self._fit_validate(f, X)
         self._fit_ingest(f)
@@ -824,6 +826,53 @@ class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
         self.H_ = Hn.T if self.hspy_comp else Hn
         self.components_ = (self.G_ @ self.W_).T if self.hspy_comp else self.H_
         return Hn
+
+    # ---- fit on a thinned image, scored on the counts held out ----------------------------------------------------------------------
+    _SPLIT_ATTRIBUTES = ("split_q_", "split_seed_", "heldout_deviance_", "train_deviance_", "heldout_deviance_map_", "train_deviance_map_",
+                         "heldout_counts_")
+
+    def _split_refusal(self):
+        if getattr(self, "_shard_group", None) is not None:
+            raise NotImplementedError("fit_split does not cover shard(): the split and its score run on one GPU")
+
+    def fit_split(self, X, q=0.8, seed=0, y=None, W=None, H=None):
+        """Fit on a Poisson-thinned part of the count image X and score the fit on the counts it has not seen (``espm_amd.splitting``;
+        no reference analogue): the honest score for ``n_components``, ``mu``, ``lambda_L`` or a bin that the in-sample deviance
+        cannot be.
+
+        1. ``splitting.thin(X, q, seed)`` on the device: X_a holds a fraction q_eff = round(q 2^32) / 2^32 of every entry's counts,
+           X_b = X - X_a the rest, independent of it for Poisson X.  X_a comes to the host and ``fit_transform(X_a, W=W, H=H)`` runs on
+           it as on any image.
+        2. ``splitting.split_deviance`` regenerates the split from (X, seed) and evaluates the fitted model ``G_ @ W_``, ``H_`` on
+           both parts, the held-out one against the model scaled by (1 - q_eff) / q_eff.
+
+        EVERY fitted attribute (``W_``, ``H_``, ``X_``, ``norm_factor_``, ``losses_``, ...) is that of the TRAINING image, at the dose
+        q_eff of X: the model is not rescaled to the full dose.  Set in addition: ``split_q_`` (q_eff), ``split_seed_``,
+        ``heldout_deviance_`` and ``train_deviance_`` (totals), ``heldout_deviance_map_`` and ``train_deviance_map_`` (p,),
+        ``heldout_counts_`` (p,) int64; a later plain fit removes them.  Returns what ``fit_transform`` returns.
+
+        X: integer counts 0 .. 65535 - a host array or a device tensor, (channels, pixels), or (pixels, channels) with ``hspy_comp``;
+        TypeError for floating-point X, ValueError for values out of range, before anything is uploaded.  Every solver, G kind and
+        precision mode, 1 .. 32 components; ``shard()``ed estimators raise NotImplementedError before anything is uploaded."""
+        from espm_amd import splitting
+        self._split_refusal()
+        layout = "pm" if self.hspy_comp else "cm"
+        Xd = splitting._resident(X, q, seed, layout)   # (one upload for the split and the score: 1 or 2 bytes per entry stay on the device)
+        Xa = splitting._to_host(splitting._thin(Xd, q, seed, layout, False)[0])
+        return self._fit_split_stages(Xd, Xa, q, seed, layout, W=W, H=H)
+
+    def _fit_split_stages(self, X, Xa, q, seed, layout, W=None, H=None):
+        """The fit of the training image Xa = thin(X, q, seed)[0] (a host array) and its score on both parts of X (the device copy);
+        fit_split, and splitting.scan, which shares both among its estimators."""
+        from espm_amd import splitting
+        # (counts up to 65535 are exact in float32; handed over as integers, scikit-learn's validation would make them float64)
+        out = self.fit_transform(Xa.astype(np.float64 if self._fp64() else np.float32), W=W, H=H)
+        D = np.asarray(self.W_ if self._identity_G else self.G_ @ self.W_, dtype=np.float64)
+        s = splitting.split_deviance(X, D, np.asarray(self.H_, dtype=np.float64), q=q, seed=seed, log_shift=self.log_shift, layout=layout)
+        self.split_q_, self.split_seed_ = s["q_eff"], int(seed)
+        self.heldout_deviance_, self.train_deviance_ = s["heldout"], s["train"]
+        self.heldout_deviance_map_, self.train_deviance_map_, self.heldout_counts_ = s["heldout_map"], s["train_map"], s["heldout_counts"]
+        return out
 
     def _refuse_binned_X(self, who):
         """After fit_binned, X_ is the BINNED image while W_, H_ and norm_factor_ belong to full-resolution pixels."""

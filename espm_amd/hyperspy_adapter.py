@@ -23,6 +23,9 @@ What is here:
 * ``SpectrumImage.rebin`` / ``.estimate_best_binning`` (eds_spim.py:746-798 on integer factors, ``espm_amd.binning``) and
   ``decompose(signal, est, bin=(by, bx))``: the spectra fitted on the binned map, loadings at full resolution
   (``NMFEstimator.fit_binned``).
+* ``SpectrumImage.thin(q, seed)`` (``espm_amd.splitting``: two independent count images from one) and
+  ``decompose(signal, est, split=(q, seed))``: the fit of the thinned image, scored on the held-out counts
+  (``NMFEstimator.fit_split``).
 * ``hyperspy_extension.yaml`` (next to this file) and the ``hyperspy.extensions`` entry point in ``pyproject.toml`` declare
   the signal type ``EDS_espm_amd`` -> ``EDSespmAMD`` below, defined only when hyperspy imports.
 """
@@ -85,15 +88,27 @@ class SpectrumImage:
         from espm_amd import binning
         return binning.estimate_best_binning(self.unfolded(), self.shape_2d, bins=bins, inspect=inspect, layout="pm")
 
-    def decomposition(self, algorithm, output_dimension=None, return_info=False, bin=None, **kwargs):
+    def thin(self, q=0.5, seed=0):
+        """Two ``SpectrumImage``s of this one's shape and dtype: a Poisson-thinned part holding a fraction q of the counts and the rest,
+        independent of each other for Poisson counts (``espm_amd.splitting.thin`` on the device; integer counts 0 .. 65535)."""
+        from espm_amd import splitting
+        Xa, Xb = splitting.thin(self.unfolded(), q=q, seed=seed, layout="pm")
+        return SpectrumImage(Xa.reshape(self.data.shape)), SpectrumImage(Xb.reshape(self.data.shape))
+
+    def decomposition(self, algorithm, output_dimension=None, return_info=False, bin=None, split=None, **kwargs):
         """hyperspy's ``decomposition(algorithm=<object>)`` for a custom estimator: ``fit_transform(data (p, n))`` ->
         loadings (p, k), ``components_`` (k, n) -> factors (n, k); the estimator stays in ``learning_results``.  ``bin=(by, bx)``:
-        ``algorithm.fit_binned`` instead - the spectra fitted on the binned image, the loadings at full resolution."""
+        ``algorithm.fit_binned`` instead - the spectra fitted on the binned image, the loadings at full resolution.
+        ``split=(q, seed)``: ``algorithm.fit_split`` - the fit of the thinned image, with its held-out deviance on the estimator."""
         if not hasattr(algorithm, "fit_transform"):
             raise ValueError("algorithm must implement fit_transform() (scikit-learn style)")
         if kwargs:
             raise TypeError(f"unsupported decomposition arguments for a custom algorithm: {sorted(kwargs)}")
-        loadings = algorithm.fit_transform(self.unfolded()) if bin is None else algorithm.fit_binned(self.unfolded(), bin)
+        if split is not None:
+            q, seed = _check_split(split, bin)
+            loadings = algorithm.fit_split(self.unfolded(), q=q, seed=seed)
+        else:
+            loadings = algorithm.fit_transform(self.unfolded()) if bin is None else algorithm.fit_binned(self.unfolded(), bin)
         factors = np.asarray(algorithm.components_).T
         lr = self.learning_results
         lr.decomposition_algorithm = algorithm
@@ -153,25 +168,41 @@ def register():
     return True
 
 
-def decompose(signal, est, bin=None, **kwargs):
+def _check_split(split, bin):
+    """(q, seed) of ``split``; ValueError when ``bin`` is given too (a binned fit of a thinned image is two calls, in that order)."""
+    if bin is not None:
+        raise ValueError("split and bin exclude each other: thin the image (SpectrumImage.thin) and decompose a part with bin")
+    try:
+        q, seed = split
+    except (TypeError, ValueError):
+        raise ValueError(f"split is a pair (q, seed), not {split!r}") from None
+    return q, seed
+
+
+def decompose(signal, est, bin=None, split=None, **kwargs):
     """``signal.decomposition(algorithm=est)`` with the estimator set up for hyperspy's calling convention.  ``bin=(by, bx)``
     routes to ``est.fit_binned``: the spectra are fitted on the binned image and ``learning_results`` holds full-resolution
-    loadings (a ``SpectrumImage``, or any signal with ``shape_2d`` and a (pixels, channels) view of its data)."""
+    loadings (a ``SpectrumImage``, or any signal with ``shape_2d`` and a (pixels, channels) view of its data).
+    ``split=(q, seed)`` routes to ``est.fit_split``: the fit of the thinned image, ``est.heldout_deviance_`` its score on the counts
+    held out; together with ``bin``: ValueError."""
+    if split is not None:
+        _check_split(split, bin)
     if not getattr(est, "hspy_comp", False):
         raise ValueError("hyperspy hands (pixels, channels) to the estimator: build it with hspy_comp=True "
                          "(espm/estimators/base.py:249-259 only warns)")
     if getattr(est, "shape_2d", None) is None and hasattr(signal, "shape_2d"):
         est.shape_2d = tuple(int(v) for v in signal.shape_2d)
     register()
-    if bin is None:
+    if bin is None and split is None:
         signal.decomposition(algorithm=est, **kwargs)
     elif isinstance(signal, SpectrumImage):
-        signal.decomposition(algorithm=est, bin=bin, **kwargs)
-    else:   # (hyperspy's own decomposition knows no bin: its results are filled as it fills them for a custom algorithm)
+        signal.decomposition(algorithm=est, bin=bin, split=split, **kwargs)
+    else:   # (hyperspy's own decomposition knows no bin and no split: its results are filled as it fills them for a custom algorithm)
         if kwargs:
-            raise TypeError(f"unsupported decomposition arguments with bin: {sorted(kwargs)}")
+            raise TypeError(f"unsupported decomposition arguments with {'bin' if split is None else 'split'}: {sorted(kwargs)}")
         data = np.asarray(signal.data)
-        loadings = est.fit_binned(data.reshape((-1, data.shape[-1])), bin)
+        flat = data.reshape((-1, data.shape[-1]))
+        loadings = est.fit_binned(flat, bin) if split is None else est.fit_split(flat, q=split[0], seed=split[1])
         lr = signal.learning_results
         lr.decomposition_algorithm = est
         lr.loadings, lr.factors = np.asarray(loadings), np.asarray(est.components_).T

@@ -1,0 +1,196 @@
+"""Poisson count splitting (data thinning) on the device (csrc/mu_split.hip): a training image and an independent held-out image of the
+same specimen from ONE measured count map, and the held-out deviance of a fit of the first - an honest score for the number of
+components, ``mu`` / ``lambda_L`` or a bin, which the in-sample ``deviance_`` cannot be (it falls with every added component).  The
+reference has no analogue.
+
+If x ~ Poisson(l) and x_a ~ Binomial(x, q), then x_a ~ Poisson(q l) and x_b = x - x_a ~ Poisson((1 - q) l), and the two are independent.
+A model Y fitted to X_a therefore predicts r Y for X_b with r = (1 - q) / q, and 2 sum (x_b ln(x_b / (r Y)) - x_b + r Y) is the deviance
+of data the fit has not seen.
+
+The split is defined by a rule, not by the kernel (include/espm_mu.h, "count splitting"): element (c, j) of the image, seen as
+(channels, pixels), has the index e = c p + j; draw d = 0 .. x - 1 of it is word (d mod 4) of Philox4x32-10 with the counter
+(e low, e high, d div 4, 0) and the key (seed low, seed high), and count d goes to X_a iff its word < thr = round(q 2^32).  So the split
+depends on (X, seed, q) alone - not on the layout X comes in, the device, or how the work was cut - and every function here reports
+the fraction the split really has, ``q_eff = thr / 2^32``.
+
+There is no CPU path: every function needs the GPU (X goes up as 8- or 16-bit counts, or stays where it is when it is a device
+tensor)."""
+from __future__ import annotations
+
+import numpy as np
+
+MAX_COUNT = 65535
+
+
+def threshold(q):
+    """(thr, q_eff): the integer threshold round(q 2^32) (ties to even; held inside 1 .. 2^32 - 1) and the fraction thr / 2^32 of the
+    counts that part A really gets.  ValueError unless 0 < q < 1."""
+    try:
+        q = float(q)
+    except (TypeError, ValueError):
+        raise ValueError(f"q must be a number with 0 < q < 1, not {q!r}") from None
+    if not 0.0 < q < 1.0:
+        raise ValueError(f"q must lie strictly between 0 and 1, not {q!r}")
+    thr = min(max(int(round(q * 2.0 ** 32)), 1), 2 ** 32 - 1)
+    return thr, thr / 2.0 ** 32
+
+
+def _check_seed(seed):
+    if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"seed must be an integer in 0 .. 2^64 - 1, not {seed!r}")
+    return int(seed)
+
+
+def _counts(X, layout):
+    """X as the kernels read it - a host array or a device tensor of uint8 / uint16 - and (n, p): TypeError for an X that is no image of
+    counts, ValueError for values outside 0 .. 65535.  Nothing is uploaded here."""
+    import torch
+    if layout not in ("cm", "pm"):
+        raise ValueError(f"layout must be 'cm' ((channels, pixels)) or 'pm' ((pixels, channels)), not {layout!r}")
+    is_t = isinstance(X, torch.Tensor)
+    if not is_t:
+        X = np.asarray(X)
+    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError("X must be a non-empty 2-D array or tensor")
+    integer = (not (X.dtype.is_floating_point or X.dtype.is_complex)) if is_t else X.dtype.kind in "iub"
+    if not integer:
+        raise TypeError(f"thinning is defined for counts: X has dtype {X.dtype} (an integer dtype with values 0 .. {MAX_COUNT})")
+    n, p = (int(X.shape[0]), int(X.shape[1])) if layout == "cm" else (int(X.shape[1]), int(X.shape[0]))
+    if X.dtype in ((torch.uint8, torch.uint16) if is_t else (np.uint8, np.uint16)):
+        return X, n, p
+    if is_t:
+        wide = X.to(torch.int64) if X.dtype != torch.bool else X.to(torch.uint8)
+        lo, hi = int(wide.min().item()), int(wide.max().item())
+    else:
+        lo, hi = int(X.min()), int(X.max())
+    if lo < 0 or hi > MAX_COUNT:
+        raise ValueError(f"X holds values from {lo} to {hi}: counts are 0 .. {MAX_COUNT}")
+    if is_t:
+        return X.to(torch.uint8 if hi <= 255 else torch.uint16), n, p
+    return X.astype(np.uint8 if hi <= 255 else np.uint16), n, p
+
+
+def _on_device(X):
+    """(Xd, dtype code, device): the 8- or 16-bit X on the GPU."""
+    from espm_amd import binning
+    return binning._on_device(X)
+
+
+def _resident(X, q, seed, layout):
+    """X on the device as the kernels read it, after every check of (X, q, seed, layout): for callers that split and score the same
+    image (one upload for both; a device tensor of 8- or 16-bit counts is returned as it is)."""
+    threshold(q)
+    _check_seed(seed)
+    return _on_device(_counts(X, layout)[0])[0]
+
+
+def _thin(X, q, seed, layout, want_b):
+    thr, q_eff = threshold(q)
+    seed = _check_seed(seed)
+    X, n, p = _counts(X, layout)
+    import torch
+
+    from espm_amd import _lib
+    from espm_amd.engine import _ptr, _stream
+    Xd, code, dev = _on_device(X)
+    with torch.cuda.device(dev):
+        Xa = torch.empty(Xd.shape, dtype=Xd.dtype, device=dev)
+        Xb = torch.empty(Xd.shape, dtype=Xd.dtype, device=dev) if want_b else None
+        _lib.check(_lib.lib.espm_thin_counts(_ptr(Xd), code, _lib.LAYOUT_CM if layout == "cm" else _lib.LAYOUT_PM, int(Xd.stride(0)), n, p, p, 0,
+                                             thr, seed, _ptr(Xa), _ptr(Xb) if want_b else None, int(Xa.stride(0)), _stream()))
+    return Xa, Xb, q_eff
+
+
+def _to_host(T):
+    return T.cpu().numpy()
+
+
+def thin(X, q=0.5, seed=0, layout="cm", device=False):
+    """(X_a, X_b): the thinning of the count image X by the module's rule - X_a holds a fraction ``threshold(q)[1]`` of every entry's
+    counts in expectation, X_b = X - X_a the rest, and for Poisson X the two are independent Poisson images.  Both have X's shape and
+    layout and the dtype X was uploaded in, as host arrays, or with ``device=True`` as device tensors.
+
+    X: a host array or a device tensor of an integer dtype with values 0 .. 65535, (channels, pixels) for ``layout="cm"`` or
+    (pixels, channels) for "pm"; uint8 and uint16 are read as they are, other integer dtypes are narrowed to the smaller of the two
+    that holds them after a range check.  Floating-point X raises TypeError (thinning is defined for counts), negative values or
+    values above 65535 ValueError, a q outside (0, 1) or a seed outside 0 .. 2^64 - 1 ValueError - all before anything is uploaded.
+    One HIP kernel, no atomics: the result is a function of (X, q, seed) alone, bit for bit, in both layouts."""
+    Xa, Xb, _ = _thin(X, q, seed, layout, True)
+    return (Xa, Xb) if device else (_to_host(Xa), _to_host(Xb))
+
+
+def split_deviance(X, D, H, q=0.5, seed=0, log_shift=1e-14, layout="cm"):
+    """The in-sample and the held-out Poisson deviance of a model of the training part of X: D (n, k) and H (k, p) are ``G_ @ W_`` and
+    ``H_`` of a fit of ``thin(X, q, seed)[0]``.  The kernel regenerates X_a from (X, seed) by the rule, so X_b is never stored or read
+    back.  With Y = max(D H, log_shift) and r = (1 - q_eff) / q_eff, returns dict(
+
+    * ``train_map`` (p,): 2 sum_c (x_a ln(x_a / Y) - x_a + Y) per pixel,
+    * ``heldout_map`` (p,): 2 sum_c (x_b ln(x_b / (r Y)) - x_b + r Y) per pixel,
+    * ``train``, ``heldout``: their totals, summed on the host in index order,
+    * ``heldout_counts`` (p,) int64: sum_c x_b per pixel, exact,
+    * ``q_eff``).
+
+    X as for ``thin``; 1 .. 32 components; everything in fp64, sums in channel order: two calls, and both layouts, give the same
+    bits."""
+    thr, q_eff = threshold(q)
+    seed = _check_seed(seed)
+    X, n, p = _counts(X, layout)
+    D, H = np.ascontiguousarray(D, dtype=np.float64), np.ascontiguousarray(H, dtype=np.float64)
+    if D.ndim != 2 or H.ndim != 2 or D.shape[1] != H.shape[0]:
+        raise ValueError("D must be (channels, components) and H (components, pixels)")
+    k = int(D.shape[1])
+    if D.shape[0] != n:
+        raise ValueError(f"X has {n} channels, D has {D.shape[0]}")
+    if H.shape[1] != p:
+        raise ValueError(f"X has {p} pixels, H has {H.shape[1]}")
+    if not log_shift > 0:
+        raise ValueError("log_shift must be positive")
+    from espm_amd import _lib
+    if not 1 <= k <= _lib.SPLIT_MAX_K:
+        raise NotImplementedError(f"split_deviance: {k} components (the kernel is built for 1..{_lib.SPLIT_MAX_K})")
+    import torch
+
+    from espm_amd.engine import _ptr, _stream
+    Xd, code, dev = _on_device(X)
+    with torch.cuda.device(dev):
+        Dd, Hd = torch.from_numpy(D).to(dev), torch.from_numpy(H).to(dev)
+        da = torch.empty(p, dtype=torch.float64, device=dev)
+        db = torch.empty(p, dtype=torch.float64, device=dev)
+        cb = torch.empty(p, dtype=torch.int64, device=dev)
+        _lib.check(_lib.lib.espm_split_deviance(_ptr(Xd), code, _lib.LAYOUT_CM if layout == "cm" else _lib.LAYOUT_PM, int(Xd.stride(0)), n, p, p, 0,
+                                                thr, seed, _ptr(Dd), _ptr(Hd), k, float(log_shift), _ptr(da), _ptr(db), _ptr(cb), _stream()))
+        train_map, heldout_map, counts = da.cpu().numpy(), db.cpu().numpy(), cb.cpu().numpy()
+    return dict(train_map=train_map, heldout_map=heldout_map, train=_ordered_sum(train_map), heldout=_ordered_sum(heldout_map),
+                heldout_counts=counts, q_eff=q_eff)
+
+
+def _ordered_sum(v):
+    """The sum of v in index order (numpy's pairwise ``sum`` is another order; ``cumsum`` adds one element after the other)."""
+    return float(np.cumsum(v)[-1])
+
+
+def scan(X, estimators, q=0.8, seeds=(0,)):
+    """Score a list of candidate estimators (numbers of components, ``mu``, ``lambda_L``, ...) on one image by count splitting: X goes
+    to the device once, for every seed it is thinned once (X_a comes to the host once and is shared), every estimator runs
+    ``fit_transform`` on X_a and is scored with ``split_deviance`` - the stages of ``NMFEstimator.fit_split``, whose attributes every
+    estimator carries afterwards, from the last seed.  Returns dict(``heldout`` and ``train`` (len(estimators), len(seeds)), ``best``:
+    the index of the estimator with the least mean held-out deviance, ``q_eff``)."""
+    estimators, seeds = list(estimators), [_check_seed(s) for s in seeds]
+    if not estimators or not seeds:
+        raise ValueError("scan needs at least one estimator and one seed")
+    thr, q_eff = threshold(q)
+    for est in estimators:
+        est._split_refusal()
+    held, train = np.empty((len(estimators), len(seeds))), np.empty((len(estimators), len(seeds)))
+    resident = {}   # X on the device, per layout the estimators read it in
+    for s, seed in enumerate(seeds):
+        parts = {}
+        for i, est in enumerate(estimators):
+            layout = "pm" if est.hspy_comp else "cm"
+            if layout not in resident:
+                resident[layout] = _resident(X, q, seed, layout)
+            if layout not in parts:
+                parts[layout] = _to_host(_thin(resident[layout], q, seed, layout, False)[0])
+            est._fit_split_stages(resident[layout], parts[layout], q, seed, layout)
+            held[i, s], train[i, s] = est.heldout_deviance_, est.train_deviance_
+    return dict(heldout=held, train=train, best=int(np.argmin(held.mean(axis=1))), q_eff=q_eff)

@@ -46,6 +46,8 @@
  *   espm_channel_diagnostics <- (new) per-channel deviance, sum spectra and Fisher information of the spectra given the abundances
  *   espm_rebin_pixels, espm_binning_sums <- espm/datasets/eds_spim.py:746-798 (estimate_best_binning) on integer factors: the bin sums and
  *                            the four sums its risk estimate reduces to, from X on the device instead of a rebin and an upsample per candidate
+ *   espm_thin_counts, espm_split_deviance <- (new) Poisson count splitting: a training and an independent held-out image from one measured
+ *                            map, and the held-out deviance of a fit of the first; no reference analogue
  *   espm_lu_pl            <- espm/estimators/updates.py:179 -> scikit-learn's _initialize_nmf -> _randomized_range_finder: the LU
  *                            normaliser of its power iterations (scipy.linalg.lu(A, permute_l=True)[0]) on tall device matrices
  *
@@ -769,6 +771,40 @@ int espm_rebin_pixels(const void* x, int x_dtype, int x_layout, int64_t ld, int 
 int espm_binning_sums(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int ny, int nx, const int32_t* bins, int n_bins,
                       double* out, void* scratch, size_t scratch_bytes, espm_stream_t stream);
 size_t espm_binning_sums_scratch(int n, int ny, int nx, int n_bins);
+
+/* ---- count splitting (csrc/mu_split.hip; espm_amd.splitting, NMFEstimator.fit_split) ----
+ * If x ~ Poisson(l) and x_a ~ Binomial(x, q), then x_a ~ Poisson(q l) and x_b = x - x_a ~ Poisson((1 - q) l), independent: one count
+ * image gives a training image and a held-out image of the same specimen.  Plain device pointers, no espm_mu_state.  x, x_layout and ld
+ * as for the diagnostics, x_dtype ESPM_DIAG_X_U8 or ESPM_DIAG_X_U16; x holds the pixels j0 .. j0 + p - 1 of an image of p_total pixels
+ * (the whole image: j0 = 0, p_total = p).
+ * THE RULE (the split is defined by it, not by the kernels).  The image is logically (n, p_total), channel-major: element (c, j) has the
+ * 64-bit index e = c * p_total + j - in either layout, in any slab.  Draw d = 0 .. x - 1 of element e is word (d mod 4) of
+ * Philox4x32-10 (Salmon et al. 2011) with the counter (e low 32, e high 32, d div 4, 0) and the key (seed low 32, seed high 32); count
+ * d goes to part A iff its word < q_threshold, 1 <= q_threshold <= 2^32 - 1: the fraction is q_threshold / 2^32 exactly.  x_a is the
+ * number of such d, x_b = x - x_a.
+ *   espm_thin_counts     xa, xb (xb may be NULL): the two parts in x's dtype and layout, rows out_ld apart.  One launch.  A zero entry
+ *                        costs its read, another one ceil(x / 4) Philox calls; an entry of ESPM_SPLIT_HEAVY or more is drawn by its
+ *                        whole wave, each lane taking blocks of four draws.
+ *   espm_split_deviance  d (n, k) row-major and h (k, p): the model of the TRAINING part (G W and H of a fit of x_a).  x_a is regenerated
+ *                        from (x, seed) by the rule - x_b is never stored.  With Y = max(d h, log_shift) and r = (2^32 - q_threshold) /
+ *                        q_threshold, per pixel j (terms x ln(x / .) are 0 where x == 0):
+ *                          dev_a[j] = 2 sum_c (x_a ln(x_a / Y) - x_a + Y)          the in-sample deviance
+ *                          dev_b[j] = 2 sum_c (x_b ln(x_b / (r Y)) - x_b + r Y)    the held-out deviance
+ *                          cnt_b[j] = sum_c x_b                                    (int64: exact)
+ *                        All arithmetic in fp64, a pixel per thread, the sums in channel order; k = 1..ESPM_SPLIT_MAX_K.  One launch.
+ * Nothing is accumulated atomically: two calls give the same bits, and so do the two layouts of one image.  ESPM_EINVAL, before the
+ * device is touched and with the offending values in the message, for a null pointer, a layout that does not exist, a dtype other than
+ * u8 / u16, ld or out_ld below the row length, n or p below 1, a slab outside 0 .. p_total, q_threshold outside 1 .. 2^32 - 1, k
+ * outside 1..ESPM_SPLIT_MAX_K, log_shift not positive.  Only the narrow build has the kernels; the wide builds return
+ * ESPM_EUNSUPPORTED. */
+#define ESPM_SPLIT_BLOCK 256   /* threads per workgroup: entries of a row (thinning), pixels (deviance)                          */
+#define ESPM_SPLIT_HEAVY 256   /* counts from which the wave shares an entry's draws (16-bit images only)                       */
+#define ESPM_SPLIT_MAX_K 32
+int espm_thin_counts(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, int64_t p_total, int64_t j0, int64_t q_threshold,
+                     uint64_t seed, void* xa, void* xb, int64_t out_ld, espm_stream_t stream);
+int espm_split_deviance(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, int64_t p_total, int64_t j0, int64_t q_threshold,
+                        uint64_t seed, const double* d, const double* h, int k, double log_shift, double* dev_a, double* dev_b,
+                        int64_t* cnt_b, espm_stream_t stream);
 
 #ifdef __cplusplus
 }
