@@ -76,6 +76,7 @@ SYMBOLS = {
     "espm_mu_w_update_tail": (C.c_int, [_SP, C.c_int, C.c_int, _vp]),
     "espm_mu_pack_x": (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "espm_mu_ell_count": (C.c_int, [_SP, _vp, _vp, _vp, _vp, _vp]),
+    "espm_mu_ell_block_counts": (C.c_int, [_SP, _vp, _vp, _vp]),
     "espm_mu_ell_count_hist": (C.c_int, [_SP, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "espm_mu_ell_fill_hist": (C.c_int, [_SP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "espm_mu_ell_plan": (C.c_int, [_SP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -36,7 +36,7 @@ static int roundup(int v, int m) { return (v + m - 1) / m * m; }
   F(ell_h_off) F(ell_klc) F(ell_w) F(ell_w_off) F(chan_perm) F(ell_cbits) F(n_cg) F(pix_perm) F(g_t) F(breg_sr_px) \
   F(breg_sr_ch) F(h_rule) F(pg_gamma_w) F(pg_q) F(ell_fill_px) F(ell_fill_num) F(ell_fill_n) F(tail_mode) F(no_fused) \
   F(ell_pb) F(ell_stream) F(ell_hv_n) F(ell_hv_npx) F(ell_hv_ngrp) F(ell_hv_px) F(ell_hv_px_off) F(ell_hv_pm) F(ell_hv_klc) F(ell_hv_kl) \
-  F(ell_hv_grp) F(ell_hv_grp_off) F(ell_hv_wm) F(hpart_alt)
+  F(ell_hv_grp) F(ell_hv_grp_off) F(ell_hv_wm) F(hpart_alt) F(ell_blk_cnt)
 
 // the caller's view of the state must be this library's (include/espm_mu.h, ESPM_MU_ABI_VERSION): checked before any field is read
 static int check_abi(const espm_mu_state* st) {

@@ -677,6 +677,7 @@ struct HStepArgs {
   const int32_t* ell_off;
   const float* ell_klc;
   const int32_t* ell_pix;
+  const float* ell_blk_cnt;   // (nblk_w, n_pad) the lists' counts per (W block, channel): the fused kernel's loss at ESPM_ELL_IMPLICIT_K components (mu_h_kernel.hpp), else unused
   int ell_bits, n_pad;
   int ell_tp;        // pixels per workgroup of the sparse H-step (= tile_px: 64, 128, 256 or 512)
   const float* l2_m; // Frobenius branch: (KP, KP) GW^T GW, else null
@@ -914,6 +915,7 @@ inline HStepArgs make_h_args(const espm_mu_state* st, int src, int write_h) {
   a.ell_off = st->ell_h_off;
   a.ell_klc = st->ell_klc;
   a.ell_pix = st->pix_perm;
+  a.ell_blk_cnt = st->ell_blk_cnt;
   a.ell_bits = st->ell_cbits;
   a.ell_tp = st->tile_px;
   a.l2_m = nullptr;

@@ -500,6 +500,18 @@ int launch_ell_count(const uint8_t* x_pm, int n, int n_pad, int p, int p_pad, in
   return rc ? rc : rc2;
 }
 
+// espm_mu_state.ell_blk_cnt: lane = channel, the counts of one W block summed in pixel order (integers below 2^24: exact in any order)
+__global__ __launch_bounds__(256) void ell_block_counts_kernel(const uint8_t* __restrict__ x_pm, int n, int n_pad, int p, int pb, float* __restrict__ out) {
+  const int b = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
+  if (c >= n_pad) return;
+  int sum = 0;
+  if (c < n) {
+    const int q0 = b * pb, q1 = min(p, q0 + pb);
+    for (int q = q0; q < q1; ++q) sum += x_pm[(size_t)q * n_pad + c];
+  }
+  out[(size_t)b * n_pad + c] = (float)sum;
+}
+
 int launch_ell_plan(const int32_t* cnt_px, const int32_t* cnt_bc, int n, int n_cg, int nblk, int p_pad, int win,
                     int32_t* chan_perm, int32_t* pix_perm, int32_t* h_off, int32_t* w_off, long long* rows, hipStream_t stream) {
   const size_t lds = (size_t)(n > win ? n : win) * sizeof(int32_t);
@@ -532,3 +544,18 @@ int launch_ell_fill(const uint8_t* x_pm, int n, int n_pad, int p, int p_pad, int
 }
 
 }  // namespace espm
+
+// (an entry point of its own, next to its kernel: espm_mu_ell_count's launcher keeps its arguments)
+extern "C" int espm_mu_ell_block_counts(const espm_mu_state* st, const void* x_pm_u8, float* blk_cnt, espm_stream_t stream) {
+  using namespace espm;
+  ESPM_REQUIRE(st != nullptr, "state is NULL");
+  ESPM_REQUIRE(st->struct_size == (uint32_t)sizeof(espm_mu_state) && st->abi_version == (uint32_t)ESPM_MU_ABI_VERSION,
+               "espm_mu_state of %u bytes, ABI %u handed to a library built for %zu bytes, ABI %d", st->struct_size, st->abi_version,
+               sizeof(espm_mu_state), ESPM_MU_ABI_VERSION);
+  ESPM_REQUIRE(st->x_dtype == ESPM_X_ELL && st->n >= 1 && st->p >= 1 && st->n_pad >= st->n && st->ell_pb >= 128 && st->nblk_w == (st->p + st->ell_pb - 1) / st->ell_pb,
+               "ell_block_counts: set x_dtype = ESPM_X_ELL and call espm_mu_query first");
+  ESPM_REQUIRE(x_pm_u8 && blk_cnt, "ell_block_counts: NULL pointer");
+  hipLaunchKernelGGL(ell_block_counts_kernel, dim3(st->nblk_w, (st->n_pad + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const uint8_t*>(x_pm_u8), st->n, st->n_pad, st->p, st->ell_pb, blk_cnt);
+  return check_hip(hipGetLastError(), "ell_block_counts launch");
+}

@@ -161,6 +161,41 @@ __device__ __forceinline__ void ell_axpy(float (&acc)[K], const float (&g)[K], f
   if constexpr (K & 1) acc[K - 1] = fmaf(g[K - 1], r, acc[K - 1]);
 }
 
+// IMPL (mu_h_kernel.hpp: FixTab, the implicit last component): g holds components 0 .. K - 2 of a normalised row, h the lane's differences
+// v_k - v_{K-1} and, in its last place, v_{K-1}; the last accumulator collects the ratios themselves.
+template <int K, bool IMPL>
+__device__ __forceinline__ float ell_dot_i(const float (&g)[K], const float (&h)[K]) {
+  if constexpr (!IMPL) {
+    return ell_dot<K>(g, h);
+  } else {
+    float y = h[K - 1];
+#pragma unroll
+    for (int i = 0; i < K - 1; ++i) y = fmaf(g[i], h[i], y);
+    return y;
+  }
+}
+template <int K, bool IMPL>
+__device__ __forceinline__ void ell_axpy_i(float (&acc)[K], const float (&g)[K], float r) {
+  if constexpr (!IMPL) {
+    ell_axpy<K>(acc, g, r);
+  } else {
+#pragma unroll
+    for (int q = 0; q < (K - 1) / 2; ++q) {
+      const f2 t = f2{g[2 * q], g[2 * q + 1]} * r + f2{acc[2 * q], acc[2 * q + 1]};
+      acc[2 * q] = t.x;
+      acc[2 * q + 1] = t.y;
+    }
+    if constexpr ((K - 1) & 1) acc[K - 2] = fmaf(g[K - 2], r, acc[K - 2]);
+    acc[K - 1] += r;
+  }
+}
+// the lane's vector in that form
+template <int K>
+__device__ __forceinline__ void ell_implicit_lane(float (&v)[K]) {
+#pragma unroll
+  for (int i = 0; i < K - 1; ++i) v[i] -= v[K - 1];
+}
+
 // Walks the `len` dwords (two 16-bit entries each) of this lane's list; `row` points at the lane's first
 // dword, consecutive dwords are 64 apart.  UNR dwords are requested one batch ahead of their use and the
 // 2 UNR table gathers of a batch are issued together.  get(dword, half, g) gathers the table row of entry
@@ -357,8 +392,10 @@ struct EllGetUnit {
 };
 
 // The fused kernel's tables (mu_h_kernel.hpp: FixTab): one address register per entry, the second part of a row at a constant offset.
-template <int K>
+// IMPL: the table holds components 0 .. 3 of the normalised rows and nothing else (K = 5): the K <= 4 path, the last place of g stays unset.
+template <int K, bool IMPL = false>
 struct EllGetUnitFix {
+  static_assert(!IMPL || K == 5, "the implicit last component: one float4 per row");
   static constexpr bool FIXED = FixTab<K>::TWO && FixTab<K>::FIXED;
   uint32_t lds_q;   // (only without the fixed layout: the float4 part's run-time base)
   __device__ __forceinline__ EllGetUnitFix(int rows = 0) : lds_q((uint32_t)(EllTab<K>::WB * rows) * 4u) {}
@@ -366,6 +403,7 @@ struct EllGetUnitFix {
     const lds_v4f lo = *(ESPM_LDS(lds_v4f))(uintptr_t)off;
 #pragma unroll
     for (int i = 0; i < (K < 4 ? K : 4); ++i) g[i] = lo[i];
+    if constexpr (IMPL) return;
     if constexpr (K == 5) g[4] = *(ESPM_LDS(float))(uintptr_t)(off + ESPM_TAB2_BASE);
     if constexpr (K == 6) {
       const lds_v2f v = *(ESPM_LDS(lds_v2f))(uintptr_t)(off + ESPM_TAB2_BASE);
@@ -380,12 +418,12 @@ struct EllGetUnitFix {
     }
   }
   __device__ __forceinline__ float operator()(uint32_t e, int half, float (&g)[K]) const {
-    if constexpr (FIXED || K <= 4) row(half ? e >> 16 : e & 0xffffu, g);
+    if constexpr (FIXED || K <= 4 || IMPL) row(half ? e >> 16 : e & 0xffffu, g);
     else EllTab<K>::get_unit(lds_q, half ? e >> 16 : e & 0xffffu, g);
     return 1.f;
   }
 };
-template <int K>
+template <int K, bool IMPL = false>
 struct EllGetFix {
   const float* tab;
   int rows, idx_bits;
@@ -393,20 +431,20 @@ struct EllGetFix {
   __device__ __forceinline__ EllGetFix(const float* t, int r, int bits) : tab(t), rows(r), idx_bits(bits), mask((1u << bits) - 1u) {}
   __device__ __forceinline__ float operator()(uint32_t e, int half, float (&g)[K]) const {
     const uint32_t v = half ? e >> 16 : e & 0xffffu;
-    if constexpr (EllGetUnitFix<K>::FIXED || K <= 4) EllGetUnitFix<K>::row((v & mask) << 4, g);
+    if constexpr (EllGetUnitFix<K>::FIXED || K <= 4 || IMPL) EllGetUnitFix<K, IMPL>::row((v & mask) << 4, g);
     else EllTab<K>::get(tab, rows, v & mask, g);
     return (float)(v >> idx_bits);
   }
 };
-template <int K, bool FIX>
+template <int K, bool FIX, bool IMPL = false>
 struct EllGetters {
   typedef EllGetUnit<K> Unit;
   typedef EllGet<K> General;
 };
-template <int K>
-struct EllGetters<K, true> {
-  typedef EllGetUnitFix<K> Unit;
-  typedef EllGetFix<K> General;
+template <int K, bool IMPL>
+struct EllGetters<K, true, IMPL> {
+  typedef EllGetUnitFix<K, IMPL> Unit;
+  typedef EllGetFix<K, IMPL> General;
 };
 
 // The H walk over rows [x0, x1) of a list group whose first `mid` rows are unit rows: num += GW^T (X / (GW H)) of the lane's
@@ -422,42 +460,44 @@ struct EllGetters<K, true> {
 #ifndef ESPM_ELL_KLPROD
 #define ESPM_ELL_KLPROD 1
 #endif
-template <int K, bool LOSS, int UNR, int PF, int PRIO = 0, bool STREAM = false, bool FIX = false, bool PP = false>   // FIX: the fused kernel's table layout; PP: ell_walk_pre
+// IMPL: the table's rows are normalised and lack their last component, hk is the pixel's column as ell_implicit_lane leaves it, acc[K - 1] collects
+// the sum of the ratios and kl the loss terms of y' = y / sigma_c (ell_dot_i; the caller owes sum cnt[c] log2 sigma_c).
+template <int K, bool LOSS, int UNR, int PF, int PRIO = 0, bool STREAM = false, bool FIX = false, bool PP = false, bool IMPL = false>   // FIX: the fused kernel's table layout; PP: ell_walk_pre
 __device__ __forceinline__ void ell_h_rows(const uint32_t* lrow, int x0, int x1, int mid, const float* tab, int n_pad, int ell_bits,
                                            const float (&hk)[K], float (&acc)[K], float& kl) {
   if (x0 < mid) {
     if constexpr (LOSS && ESPM_ELL_KLPROD) {
       float prod = 1.f;
-      ell_walk<K, UNR, PF, PRIO, STREAM, PP>(lrow + (size_t)x0 * 64, min(x1, mid) - x0, typename EllGetters<K, FIX>::Unit(n_pad),
+      ell_walk<K, UNR, PF, PRIO, STREAM, PP>(lrow + (size_t)x0 * 64, min(x1, mid) - x0, typename EllGetters<K, FIX, IMPL>::Unit(n_pad),
         [&](float, const float (&g)[K]) {
-          const float r = __builtin_amdgcn_rcpf(ell_dot<K>(g, hk));
-          ell_axpy<K>(acc, g, r);
+          const float r = __builtin_amdgcn_rcpf(ell_dot_i<K, IMPL>(g, hk));
+          ell_axpy_i<K, IMPL>(acc, g, r);
           prod *= r;
         },
         [&](auto redo) {
           const bool ok = __builtin_amdgcn_classf(prod, 0x100);   // a positive normal number
           if (__builtin_expect(__builtin_amdgcn_ballot_w64(!ok) != 0, 0)) {
-            redo([&](float, const float (&g)[K]) { kl += __builtin_amdgcn_logf(__builtin_amdgcn_rcpf(ell_dot<K>(g, hk))); });
+            redo([&](float, const float (&g)[K]) { kl += __builtin_amdgcn_logf(__builtin_amdgcn_rcpf(ell_dot_i<K, IMPL>(g, hk))); });
           } else {
             kl += __builtin_amdgcn_logf(prod);
           }
           prod = 1.f;
         });
     } else {
-      ell_walk<K, UNR, PF, PRIO, STREAM, PP>(lrow + (size_t)x0 * 64, min(x1, mid) - x0, typename EllGetters<K, FIX>::Unit(n_pad), [&](float, const float (&g)[K]) {
-        const float r = __builtin_amdgcn_rcpf(ell_dot<K>(g, hk));
-        ell_axpy<K>(acc, g, r);
+      ell_walk<K, UNR, PF, PRIO, STREAM, PP>(lrow + (size_t)x0 * 64, min(x1, mid) - x0, typename EllGetters<K, FIX, IMPL>::Unit(n_pad), [&](float, const float (&g)[K]) {
+        const float r = __builtin_amdgcn_rcpf(ell_dot_i<K, IMPL>(g, hk));
+        ell_axpy_i<K, IMPL>(acc, g, r);
         if constexpr (LOSS) kl += __builtin_amdgcn_logf(r);
       });
     }
   }
   if (x1 > mid) {
     const int g0 = max(x0, mid);
-    ell_walk<K, UNR, PF, PRIO, STREAM, PP>(lrow + (size_t)g0 * 64, x1 - g0, typename EllGetters<K, FIX>::General(tab, n_pad, ell_bits), [&](float x, const float (&g)[K]) {
-      const float y = ell_dot<K>(g, hk);
+    ell_walk<K, UNR, PF, PRIO, STREAM, PP>(lrow + (size_t)g0 * 64, x1 - g0, typename EllGetters<K, FIX, IMPL>::General(tab, n_pad, ell_bits), [&](float x, const float (&g)[K]) {
+      const float y = ell_dot_i<K, IMPL>(g, hk);
       // (+1e-37: a padding entry has x = 0 and must give 0 * log2(tiny), not 0 * -inf; same guard as the dense kernels)
       const float r = LOSS ? fmaf(x, __builtin_amdgcn_rcpf(y), 1e-37f) : x * __builtin_amdgcn_rcpf(y);
-      ell_axpy<K>(acc, g, r);
+      ell_axpy_i<K, IMPL>(acc, g, r);
       if constexpr (LOSS) kl = fmaf(x, __builtin_amdgcn_logf(r), kl);
     });
   }

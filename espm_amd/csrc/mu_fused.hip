@@ -168,6 +168,8 @@ static int launch_fused_k(const FusedArgs& args_in, int nblk, hipStream_t stream
                        args.h.simplex_h && args.h.lambda_l != 0.f && args.h.grid_mode && args.h.have_prev && args.h.write_h && args.h.h_rule == 0 &&
                        args.h.tail_on != 1 && !args.static_units && args.slab_lds && !args.w_split && args.red_lds_off >= 0 && staged_ok &&
                        (args.perm_lds != 0) == (pb != ESPM_ELL_PB) && ESPM_FUSED_SMALL_THREADS == ESPM_ELL_WTHREADS;
+    if (plain) ESPM_REQUIRE(!(EllImplicit<K>::ON && args.h.compute_loss) || args.h.ell_blk_cnt,
+                            "fused half-steps at %d components with the loss: espm_mu_state.ell_blk_cnt is missing (espm_mu_ell_block_counts)", K);
     // (the lists too large for the last-level cache, the caller says: the instance that loads them without allocating there)
     if (plain && args.stream_lists && pb == ESPM_ELL_PB) return launch_fused_plain_stream(args, K, args.h.compute_loss != 0, true, nblk, bytes, stream);
     if (plain) return launch_fused_plain(args, K, args.h.compute_loss != 0, pb == ESPM_ELL_PB, nblk, bytes, stream);
@@ -194,7 +196,7 @@ size_t fused_ell_lds_bytes(int n_pad, int k, int pb) {
   const int tab_rows = n_pad > pb ? n_pad : pb;
   const bool fixed = k > 4 && k >= ESPM_FIXTAB_MIN_K;   // (FixTab, mu_h_kernel.hpp)
   if (fixed && tab_rows > ESPM_TAB2_BASE / 16) return (size_t)-1;   // (those tables hold at most 2048 rows)
-  const int wb = k <= 4 ? 0 : (k == 5 ? 1 : (k == 6 ? 2 : 4));
+  const int wb = k <= 4 ? 0 : (k == 5 ? 1 : (k == 6 ? 2 : 4));   // (k = ESPM_ELL_IMPLICIT_K: the implicit form uses 16 of a row's 20 bytes; the region keeps the explicit form's size)
   const size_t tab_bytes = fixed ? (size_t)ESPM_TAB2_BASE + (size_t)16 * tab_rows : (size_t)(4 + wb) * 4 * tab_rows;
   const int seg = pb == ESPM_ELL_PB ? (k <= 4 ? 4 : (k <= 6 ? 3 : 2)) : ESPM_ELL_PB / pb;   // FusedGeom<K>::S | 1024 / pb
   const int n_cg = (n_pad + 63) / 64;   // (>= the channel groups of any n with this n_pad)

@@ -24,6 +24,9 @@
 //   4. W walk, dynamic too: the block's channel groups (in order of decreasing length) through a second counter; a group
 //      is walked by one wave, so its rows of the slab have one writer whoever that is.
 //
+// k = ESPM_ELL_IMPLICIT_K (5), PLAIN instances: both tables hold their rows NORMALISED and without the last component (mu_h_kernel.hpp, FixTab): one 16-byte gather per
+// entry; the prologue owes the loss sum_c cnt[c] log2 sigma_c (HStepArgs::ell_blk_cnt), every thread for the rows it stages.
+//
 // Against the two launches this saves a kernel boundary, the table prologue of the W accumulation (1024 rows of h_t
 // from memory, a barrier), and 2 x 4 KP p bytes of h_t traffic.  The block's record goes to the hpart slot of its first
 // tile, zeros to the slot of the second (HStepArgs::rec_nb), so the readers of the records do not change.
@@ -205,6 +208,7 @@ __global__ __launch_bounds__(NT) void mu_fused_ell_kernel(const FusedArgs fa) {
   const int TP = PB / 2;                           // pixels per H tile
   const int GPT_SHIFT = PBITS - 7;                 // log2(list groups per tile)
   constexpr int PROWS = FusedGeom<K>::PROWS;
+  constexpr bool IMPL = EllImplicit<K>::ON && PLAIN;   // (mu_h_kernel.hpp: normalised tables without their last component - the lean instances)
   // segments per list group of the H walk: below the full geometry 1024 / PB, i.e. always 16 (group, segment) units
   constexpr bool S_RT = FULL && FusedGeom<K>::S_MAX > FusedGeom<K>::S;   // (k >= 5 at the full geometry: as many segments as fit, the launcher's choice)
   const int S = (FULL && !S_RT) ? FusedGeom<K>::S : fa.h_segs;   // (below the full geometry: 1024 / PB, or more where the numerators' region - grown for the slab - holds them)
@@ -254,18 +258,22 @@ __global__ __launch_bounds__(NT) void mu_fused_ell_kernel(const FusedArgs fa) {
   constexpr bool PREF_W = PLAIN && !FULL && K <= 6 && ESPM_FUSED_FIRST_PREFETCH != 0;   // (k = 7, 8: the request's registers are spilled ones, configuration 5's shard 100.5 -> 101.1 us)
   const int wave_id = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   bool staged = false;
+  float kl_corr = 0.f;   // IMPL: this thread's part of sum_c cnt[c] log2 sigma_c over the table rows it stages (a fixed assignment of rows to threads)
+  const float* blk_cnt = (IMPL && LOSS) ? a.ell_blk_cnt + (size_t)blockIdx.x * a.n_pad : nullptr;
   if constexpr (ESPM_FUSED_PROLOGUE_BATCH) {
     constexpr int TR = 4, PC = 4;   // table rows / permutation entries a thread stages
     const int n_perm = perm_lds ? PB + 64 * fa.w.n_cg : 0, n_woff = 2 * fa.w.n_cg + 1;
     staged = PLAIN || (a.n_pad <= TR * NT && n_perm <= PC * NT && n_woff <= NT && a.cs_nbk <= 64 && 2 * K <= NT / 64);   // (uniform; fused_prologue_staged on the host)
     if (staged) {
       float4 tlo[TR], thi[TR];
+      float tcnt[TR];
 #pragma unroll
       for (int i = 0; i < TR; ++i) {
         const int r = threadIdx.x + i * NT;
         const float* src = a.gw_s + (size_t)min(r, a.n_pad - 1) * KP;
         tlo[i] = *reinterpret_cast<const float4*>(src);
         thi[i] = K > 4 ? *reinterpret_cast<const float4*>(src + 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (IMPL && LOSS) tcnt[i] = blk_cnt[min(r, a.n_pad - 1)];
       }
       int pv[PC];
 #pragma unroll
@@ -298,7 +306,10 @@ __global__ __launch_bounds__(NT) void mu_fused_ell_kernel(const FusedArgs fa) {
 #pragma unroll
       for (int i = 0; i < TR; ++i) {
         const int r = threadIdx.x + i * NT;
-        if (r < a.n_pad) FixTab<K>::put(tab, a.n_pad, r, tlo[i], thi[i]);
+        if (r < a.n_pad) {
+          const float lg = FixTab<K>::template put<IMPL>(tab, a.n_pad, r, tlo[i], thi[i]);
+          if constexpr (IMPL && LOSS) kl_corr = fmaf(tcnt[i], lg, kl_corr);
+        }
       }
 #pragma unroll
       for (int i = 0; i < PC; ++i) {
@@ -400,8 +411,9 @@ __global__ __launch_bounds__(NT) void mu_fused_ell_kernel(const FusedArgs fa) {
         float hk[K];
 #pragma unroll
         for (int kk = 0; kk < K; ++kk) hk[kk] = a.h_in[(size_t)kk * a.p_pad + px];
+        if constexpr (IMPL) ell_implicit_lane<K>(hk);
         const uint32_t* lrow = a.ell + (size_t)beg * 64 + lane;
-        ell_h_rows<K, LOSS, UNR_H, PF, PRIO, STREAM, true, WALK_PP>(lrow, x0, x1, mid, tab, a.n_pad, a.ell_bits, hk, acc, kl);
+        ell_h_rows<K, LOSS, UNR_H, PF, PRIO, STREAM, true, WALK_PP, IMPL>(lrow, x0, x1, mid, tab, a.n_pad, a.ell_bits, hk, acc, kl);
         if constexpr (PRIO > 0) __builtin_amdgcn_s_setprio(0);
       }
     }
@@ -440,8 +452,8 @@ __global__ __launch_bounds__(NT) void mu_fused_ell_kernel(const FusedArgs fa) {
       }
     }
   };
-  h_epilogue<K, true, 0, ESPM_FUSED_SUM_BATCHED ? (FULL ? FusedGeom<K>::S_MAX : ESPM_FUSED_MAX_SEGS) : 0, PLAIN>(
-      a, part, S, PB, blk0, 0.f, cs_lds, tab, PB, false,
+  h_epilogue<K, true, 0, ESPM_FUSED_SUM_BATCHED ? (FULL ? FusedGeom<K>::S_MAX : ESPM_FUSED_MAX_SEGS) : 0, PLAIN, decltype(request_w), false, IMPL>(
+      a, part, S, PB, blk0, -kl_corr, cs_lds, tab, PB, false,
       (PLAIN || fa.red_lds_off >= 0) ? reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(smem) + fa.red_lds_off) : nullptr, relw, request_w,
       ukl, NGRP * S);
 
@@ -469,6 +481,7 @@ __global__ __launch_bounds__(NT) void mu_fused_ell_kernel(const FusedArgs fa) {
 #pragma unroll
       for (int kk = 0; kk < K; ++kk) gw[kk] = gsrc[kk];
     }
+    if constexpr (IMPL) ell_implicit_lane<K>(gw);
 #pragma unroll
     for (int kk = 0; kk < K; ++kk) acc[kk] = 0.f;
     const int wkind = (PREF_W && first_w) ? fw_kind : 0;
@@ -486,14 +499,20 @@ __global__ __launch_bounds__(NT) void mu_fused_ell_kernel(const FusedArgs fa) {
       }
     }
     const uint32_t* lrow = w.ell + (size_t)beg * 64 + lane;
-    ell_walk_pre<K, UNR_W, PF, PRIO, STREAM, WALK_PP>(lrow + (size_t)(u0 - beg) * 64, u1 - u0, EllGetUnitFix<K>(PB), [&](float, const float (&h)[K]) {
-      ell_axpy<K>(acc, h, __builtin_amdgcn_rcpf(ell_dot<K>(h, gw)));
+    ell_walk_pre<K, UNR_W, PF, PRIO, STREAM, WALK_PP>(lrow + (size_t)(u0 - beg) * 64, u1 - u0, EllGetUnitFix<K, IMPL>(PB), [&](float, const float (&h)[K]) {
+      ell_axpy_i<K, IMPL>(acc, h, __builtin_amdgcn_rcpf(ell_dot_i<K, IMPL>(h, gw)));
     }, EllNoFlush(), wkind == 1, fw_rows);
-    ell_walk_pre<K, UNR_W, PF, PRIO, STREAM, WALK_PP>(lrow + (size_t)(g0 - beg) * 64, g1 - g0, EllGetFix<K>(tab, PB, PBITS), [&](float x, const float (&h)[K]) {
-      const float r = x * __builtin_amdgcn_rcpf(ell_dot<K>(h, gw));
-      ell_axpy<K>(acc, h, r);
+    ell_walk_pre<K, UNR_W, PF, PRIO, STREAM, WALK_PP>(lrow + (size_t)(g0 - beg) * 64, g1 - g0, EllGetFix<K, IMPL>(tab, PB, PBITS), [&](float x, const float (&h)[K]) {
+      const float r = x * __builtin_amdgcn_rcpf(ell_dot_i<K, IMPL>(h, gw));
+      ell_axpy_i<K, IMPL>(acc, h, r);
     }, EllNoFlush(), wkind == 2, fw_rows);
     if constexpr (PRIO > 0) __builtin_amdgcn_s_setprio(0);
+    if constexpr (IMPL) {   // the last sum, once per unit: S - (the others), in a fixed order (its true value is >= 0)
+      float low = acc[0];
+#pragma unroll
+      for (int kk = 1; kk < K - 1; ++kk) low += acc[kk];
+      acc[K - 1] = fmaxf(acc[K - 1] - low, 0.f);
+    }
     if (c >= 0) {
       if (slab_lds) {
         float* copy = part + (size_t)whalf * K * w.n_pad;

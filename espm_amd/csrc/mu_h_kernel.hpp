@@ -64,23 +64,58 @@ __device__ __forceinline__ void lds_table_put(float* tab, int rows, int r, const
 #ifndef ESPM_FIXTAB_MIN_K   // component counts from which the fused kernel's tables take this layout (A/B: 9 keeps the layout above for all)
 #define ESPM_FIXTAB_MIN_K 6
 #endif
+// ---- k = 5: the fifth component IMPLICIT ----------------------------------------------------------------------------------------------------
+// Both walks of the fused kernel use a gathered row t only through  x t / (t . v)  (v: the lane's H column or row of G W), which does not change
+// when t is scaled.  The tables therefore hold t' = t / sum_k t_k, components 0..3 only - ONE float4 per row at LDS address 16 r, like k <= 4 -
+// and t'_4 = 1 - (t'_0 + .. + t'_3) is never formed:  t' . v = v_4 + sum_{k<4} t'_k (v_k - v_4)  (four FMAs from v_4, the differences held by the
+// lane),  r' = x / (t' . v),  acc_k += r' t'_k  for k < 4, and the fifth accumulator collects S = sum r' = sum_k acc_k, from which the fifth
+// sum is restored ONCE (per pixel after all partials are added; per channel at the end of its unit): acc_4 = S - (acc_0 + .. + acc_3).
+// Per entry: one gather instead of two (the two-pass 4-byte read is gone), one decode instruction instead of two, four dot-product FMAs instead
+// of five.  The loss sees y' = y / sigma_c (sigma_c: the sum of row c of G W): sum x log2(x / y) = sum x log2(x / y') - sum_c cnt[c] log2 sigma_c
+// with cnt[c] the block's counts of channel c (espm_mu_state.ell_blk_cnt), which the prologue subtracts row by row while it stages the table.
+// ESPM_ELL_IMPLICIT_K: the component count that takes this form in the fused kernel's PLAIN instances (5; 0: none - the explicit tables
+// everywhere, A/B).  The generic instances (fill and heavy numerators, fixed H, no previous H ...) keep the explicit tables: y' = v_4 + sum t'_k (v_k - v_4)
+// carries an absolute error of ~6e-8 max(v), i.e. a relative one that grows where y' << max(v) - a row of G W concentrated on one component met by a pixel
+// concentrated on another.  On a W spanning seven decades (tests/test_gpu_ell_heavy.py, fused against two launches) that moved entries 1e-7 of their row's
+// largest by 1e-4 relative after 8 iterations: inside the tolerance on W (2e-4), outside that comparison's 2e-5.
+#ifndef ESPM_ELL_IMPLICIT_K
+#define ESPM_ELL_IMPLICIT_K 5
+#endif
+static_assert(ESPM_ELL_IMPLICIT_K == 0 || ESPM_ELL_IMPLICIT_K == 5, "the implicit last component: built and measured for k = 5");
+template <int K>
+struct EllImplicit {
+  static constexpr bool ON = K == ESPM_ELL_IMPLICIT_K;
+};
 template <int K>
 struct FixTab {
   static constexpr bool TWO = K > 4;
   static constexpr bool FIXED = K >= ESPM_FIXTAB_MIN_K;   // (K <= 4: one part either way)
   static constexpr int MAX_ROWS = (TWO && FIXED) ? ESPM_TAB2_BASE / 16 : (1 << 30);
   __host__ __device__ static constexpr size_t bytes(int rows) {
+    // (the implicit form uses 16 bytes per row of this region: the layout of the workgroup's LDS stays that of the explicit form, which the
+    //  generic instances keep)
     return (TWO && FIXED) ? (size_t)ESPM_TAB2_BASE + 16u * (size_t)rows : (size_t)(4 + LdsTabGeom<K>::WB) * 4u * (size_t)rows;
   }
-  static __device__ __forceinline__ void put(float* tab, int rows, int r, const float4 lo, const float4 hi) {
-    if constexpr (!(TWO && FIXED)) {
+  // returns log2 of the row's sum where the row is stored normalised (IMPL), else 0
+  template <bool IMPL = false>
+  static __device__ __forceinline__ float put(float* tab, int rows, int r, const float4 lo, const float4 hi) {
+    if constexpr (IMPL) {
+      static_assert(EllImplicit<K>::ON, "the implicit last component: ESPM_ELL_IMPLICIT_K components");
+      const float s = (((lo.x + lo.y) + lo.z) + lo.w) + hi.x;   // (a fixed order; true divisions below: once per row)
+      const bool ok = s > 0.f && s <= 3.0e38f;                  // (rows of padding channels are zeros: never referenced with a count)
+      const float d = ok ? s : 1.f;
+      reinterpret_cast<float4*>(tab)[r] = ok ? make_float4(lo.x / d, lo.y / d, lo.z / d, lo.w / d) : make_float4(0.2f, 0.2f, 0.2f, 0.2f);
+      return ok ? log2f(s) : 0.f;
+    } else if constexpr (!(TWO && FIXED)) {
       lds_table_put<K>(tab, rows, r, lo, hi);
+      return 0.f;
     } else {
       reinterpret_cast<float4*>(tab)[r] = lo;
       float* p2 = tab + ESPM_TAB2_BASE / 4 + 4 * (size_t)r;
       if constexpr (K == 5) p2[0] = hi.x;
       else if constexpr (K == 6) *reinterpret_cast<float2*>(p2) = make_float2(hi.x, hi.y);
       else *reinterpret_cast<float4*>(p2) = hi;
+      return 0.f;
     }
   }
   static __device__ __forceinline__ void put_row(float* tab, int rows, int r, const float* src) {   // src: a KP-strided row of gw_s
@@ -170,7 +205,9 @@ struct HEpiNoHook {
 // CHAIN (mu_h_chain.hpp): where a.chain_prev is set, the statistics of h_in come from the previous launch's records instead of
 // a.hstat_in: as `chain`, reduced at the start of the kernel (the dense kernels), or - chain_scr - combined here behind the barrier
 // from the wave stage the kernel left in LDS (the sparse kernel, whose walk has no scalar register to spare for them).
-template <int K, bool EARLY = true, int RULE = 0, int MAXP = 0, bool PLAIN = false, typename Hook = HEpiNoHook, bool CHAIN = false>
+// IMPL (the fused kernel at ESPM_ELL_IMPLICIT_K components): row K - 1 of the partials holds S = the sum of all K numerators (FixTab's comment); the
+// last numerator is restored here, once per pixel, behind the slot-ordered sums and ahead of everything that is added to the numerators.
+template <int K, bool EARLY = true, int RULE = 0, int MAXP = 0, bool PLAIN = false, typename Hook = HEpiNoHook, bool CHAIN = false, bool IMPL = false>
 __device__ __forceinline__ void h_epilogue(const HStepArgs& a, float* smem, int nparts, int TP, int tile0, float kl_lane,
                                            const double* colsum = nullptr,   // the workgroup's own copy of colsum(GW) (LDS), else a.colsum_gw
                                            float* lds_tab = nullptr, int lds_rows = 0, bool kl_rows = false,
@@ -247,7 +284,7 @@ __device__ __forceinline__ void h_epilogue(const HStepArgs& a, float* smem, int 
     if (lds_tab) {
       float4 hi = make_float4(0.f, 0.f, 0.f, 0.f);
       if constexpr (KP > 4 && K > 4) hi = make_float4(ht[4], ht[5], ht[6], ht[7]);
-      FixTab<K>::put(lds_tab, lds_rows, jj, make_float4(ht[0], ht[1], ht[2], ht[3]), hi);   // (a table handed to the epilogue is the fused kernel's)
+      FixTab<K>::template put<IMPL>(lds_tab, lds_rows, jj, make_float4(ht[0], ht[1], ht[2], ht[3]), hi);   // (a table handed to the epilogue is the fused kernel's)
     } else {
       store_row_kp(a.h_t + (size_t)q * KP, ht);
     }
@@ -256,7 +293,7 @@ __device__ __forceinline__ void h_epilogue(const HStepArgs& a, float* smem, int 
   for (int jj = threadIdx.x; jj < TP; jj += (int)blockDim.x) {
     const int q = tile0 + jj;
     if (q >= a.p) {
-      if (lds_tab) FixTab<K>::put(lds_tab, lds_rows, jj, make_float4(1.f, 1.f, 1.f, 1.f), make_float4(1.f, 1.f, 1.f, 1.f));
+      if (lds_tab) FixTab<K>::template put<IMPL>(lds_tab, lds_rows, jj, make_float4(1.f, 1.f, 1.f, 1.f), make_float4(1.f, 1.f, 1.f, 1.f));
       continue;
     }
     if (!loaded) h_epilogue_load<K, PLAIN>(a, q, stencil, in);  // tiles wider than the workgroup: later pixels of a thread
@@ -317,6 +354,12 @@ __device__ __forceinline__ void h_epilogue(const HStepArgs& a, float* smem, int 
         nv[kk] = s * a.xscale;
         dv[kk] = (float)(colsum ? colsum[kk] : a.colsum_gw[kk]);
       }
+    }
+    if constexpr (IMPL) {   // (true value >= 0: what the subtraction leaves below it is rounding)
+      float low = nv[0];
+#pragma unroll
+      for (int kk = 1; kk < K - 1; ++kk) low += nv[kk];
+      nv[K - 1] = fmaxf(nv[K - 1] - low, 0.f);
     }
     ESPM_PHASE_STAMP(40);   // (instrumented build) partial numerators summed
     if (f_fill) {  // (uniform) sparse store: a pixel without counts takes the numerator of its log_shift fill (include/espm_mu.h)

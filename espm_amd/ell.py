@@ -256,6 +256,19 @@ def build(Xpm, p_pad, cbits, tile_px=512, chunk=16384):
     return out
 
 
+def block_counts(Xpm, n_pad, tile_px=512):
+    """espm_mu_state.ell_blk_cnt of the image `build` was given: (nblk_w, n_pad) float32, the counts the LISTS hold of every channel in
+    every W block of 2 tile_px pixels - the heavy elements are not in the lists and not in these sums."""
+    p, n = Xpm.shape
+    PB = 2 * tile_px
+    light, _ = split_heavy(Xpm, PB)
+    nblk_w = (p + PB - 1) // PB
+    out = torch.zeros((nblk_w, n_pad), dtype=torch.float32, device=Xpm.device)
+    for b in range(nblk_w):
+        out[b, :n] = light[b * PB:(b + 1) * PB].to(torch.float64).sum(dim=0).to(torch.float32)
+    return out
+
+
 def lds_bytes_h(n_pad, k):
     """LDS the sparse H-step needs: the GW table plus the partial numerators of a 512-pixel tile (two sets for k <= 6,
     where the list groups of a window are walked in pairs)."""

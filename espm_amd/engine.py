@@ -346,6 +346,7 @@ class MUEngine:
             self.x_cm = self.x_pm = None
             if torch_builder:
                 self.ell = _ell.build(Xd if layout == "pm" else Xd.t(), st.p_pad, st.ell_cbits, st.tile_px)
+                self.ell["blk_cnt"] = _ell.block_counts(Xd if layout == "pm" else Xd.t(), st.n_pad, st.tile_px)
             else:
                 self.ell = self._build_ell(src, n_heavy, nnz)
                 self._tick("sparse store build")
@@ -475,6 +476,7 @@ class MUEngine:
                 st.ell_hv_klc, st.ell_hv_kl = self.hv_klc.data_ptr(), self.hv_kl.data_ptr()
             st.ell_w, st.ell_w_off, st.chan_perm = (self.ell[key].data_ptr() for key in ("ell_w", "ell_w_off", "chan_perm"))
             st.pix_perm = self.ell["pix_perm"].data_ptr()
+            st.ell_blk_cnt = self.ell["blk_cnt"].data_ptr()
         st.g = self.g.data_ptr() if self.g is not None else None
         st.g_t = self.g_t.data_ptr() if self.g_t is not None else None
         st.colsum_g = self.colsum_g.data_ptr() if self.colsum_g is not None else None
@@ -564,6 +566,9 @@ class MUEngine:
         bkt_bc = torch.empty((st.nblk_w, st.n_cg * 64, _lib.ELL_BUCKETS), dtype=torch.uint8, device=dev) if hist else None
         self._check(self.lib.espm_mu_ell_count_hist(C.byref(st), _ptr(x8), _ptr(cnt_px), _ptr(cnt_bc), _ptr(klc),
                                                     _ptr(bkt_px) if hist else None, _ptr(bkt_bc) if hist else None, _stream()))
+        # the lists' counts per (W block, channel): what the one-launch iteration's loss owes at 5 components (include/espm_mu.h, ell_blk_cnt)
+        blk_cnt = torch.empty((st.nblk_w, st.n_pad), dtype=torch.float32, device=dev)
+        self._check(self.lib.espm_mu_ell_block_counts(C.byref(st), _ptr(x8), _ptr(blk_cnt), _stream()))
         chan_perm = torch.empty((st.nblk_w, st.n_cg * 64), **i32)
         pix_perm = torch.empty(st.p_pad, **i32)
         h_off = torch.empty(2 * (st.p_pad // 64) + 1, **i32)          # per group: first unit row, first general row
@@ -583,7 +588,7 @@ class MUEngine:
         finally:
             st.x_cm = None
         torch.cuda.current_stream().synchronize()
-        out = dict(ell_h=ell_h, ell_h_off=h_off, klc=klc, pix_perm=pix_perm, ell_w=ell_w, ell_w_off=w_off, chan_perm=chan_perm, n_cg=st.n_cg,
+        out = dict(ell_h=ell_h, ell_h_off=h_off, klc=klc, pix_perm=pix_perm, ell_w=ell_w, ell_w_off=w_off, chan_perm=chan_perm, blk_cnt=blk_cnt, n_cg=st.n_cg,
                    nblk_w=st.nblk_w, nnz=nnz, entries_h=int(cnt_px[0].sum()), entries_w=int(cnt_bc[0].sum()), rows_h=rows_h,
                    rows_w=rows_w, unit_rows_h=int((h_off[1::2] - h_off[0:-1:2]).sum()),
                    unit_rows_w=int((w_off[1::2] - w_off[0:-1:2]).sum()))

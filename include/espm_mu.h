@@ -165,7 +165,7 @@ enum { ESPM_LAYOUT_CM = 0 /* (n, p) channel-major */, ESPM_LAYOUT_PM = 1 /* (p, 
  * point that takes a state checks st->struct_size == sizeof(espm_mu_state) and st->abi_version == ESPM_MU_ABI_VERSION
  * first and fails with ESPM_EINVAL otherwise: a binding whose copy of the layout has drifted is refused instead of
  * having its pointers misread.  A binding can also compare its layout field by field with espm_mu_state_layout(). */
-#define ESPM_MU_ABI_VERSION 6
+#define ESPM_MU_ABI_VERSION 7
 
 typedef struct espm_mu_state {
   uint32_t struct_size;   /* sizeof(espm_mu_state) as the CALLER sees it                  */
@@ -336,6 +336,12 @@ typedef struct espm_mu_state {
    * hpart and hpart_alt in turn, and each reduces what it needs of its predecessor's records itself: one launch per iteration
    * (espm_mu_h_chain_applies).  NULL: espm_mu_iterate_h runs espm_mu_step_h + espm_mu_h_finalize per iteration.  Nothing else reads it. */
   double* hpart_alt;
+  /* Sparse store: (nblk_w, n_pad) floats - the sum of the counts that the LISTS hold of channel c in W block b (ell_pb pixels) at
+   * [b * n_pad + c]; heavy elements are not in the lists and not in these sums, channels n .. n_pad - 1 hold 0.  Fixed when the store
+   * is built (espm_mu_ell_block_counts; 2 MB at 2048 channels x 512^2 pixels).  The lean instances of the one-launch iteration at 5 components gather rows
+   * of G W divided by their sums sigma_c (one 16-byte read per list entry) and owes the loss sum_c ell_blk_cnt[b][c] log2 sigma_c per
+   * block: it needs this array whenever compute_loss is set and fails with ESPM_EINVAL without it.  Nothing else reads it. */
+  const float* ell_blk_cnt;
 } espm_mu_state;
 
 const char* espm_mu_version(void);
@@ -369,6 +375,9 @@ int espm_mu_pack_x(const void* src, int src_dtype, int src_layout, int64_t ld, i
  *          from which the channel lists are read with 16-byte loads (the lists come out the same); reset st->x_cm to NULL afterwards. */
 int espm_mu_ell_count(const espm_mu_state* st, const void* x_pm_u8, int32_t* cnt_px, int32_t* cnt_bc, float* ell_klc,
                       espm_stream_t stream);
+/* espm_mu_state.ell_blk_cnt from the same 8-bit matrix (the heavy elements already taken out of it): blk_cnt (nblk_w, n_pad) floats,
+ * caller-allocated, every entry written.  Needs of `st` what espm_mu_ell_count needs. */
+int espm_mu_ell_block_counts(const espm_mu_state* st, const void* x_pm_u8, float* blk_cnt, espm_stream_t stream);
 /* The same two steps with the lists' histograms of unit elements handed from count to fill, which saves the fill its first of two passes
  * over X: ESPM_ELL_BUCKETS bytes per list - its elements equal to 1 per residue class of their index (channel; pixel inside the block) mod
  * ESPM_ELL_BUCKETS, what the placement of the unit rows goes by.  bkt_px (p_pad, ESPM_ELL_BUCKETS) and bkt_bc (nblk_w, 64 n_cg,
