@@ -37,6 +37,7 @@ ABI_VERSION = _D["ESPM_MU_ABI_VERSION"]
 XCHG_HANDLE_BYTES = _D["ESPM_XCHG_HANDLE_BYTES"]
 ELL_TILE, ELL_PB, ELL_PBITS, ELL_LDS_MAX = _D["ESPM_ELL_TILE"], _D["ESPM_ELL_PB"], _D["ESPM_ELL_PBITS"], _D["ESPM_ELL_LDS_MAX"]
 ELL_STREAM_BYTES = _D["ESPM_ELL_STREAM_BYTES"]
+ELL_KEEP_BYTES = _D["ESPM_ELL_KEEP_BYTES"]
 ELL_BUCKETS = _D["ESPM_ELL_BUCKETS"]
 ELL_HEAVY_MIN, ELL_HEAVY_MAX = _D["ESPM_ELL_HEAVY_MIN"], _D["ESPM_ELL_HEAVY_MAX"]
 ELL_UNIT_ROWS, ELL_UNIT_MAX_N, ELL_PAIR_MAX_K = _D["ESPM_ELL_UNIT_ROWS"], _D["ESPM_ELL_UNIT_MAX_N"], _D["ESPM_ELL_PAIR_MAX_K"]

@@ -36,7 +36,7 @@ static int roundup(int v, int m) { return (v + m - 1) / m * m; }
   F(ell_h_off) F(ell_klc) F(ell_w) F(ell_w_off) F(chan_perm) F(ell_cbits) F(n_cg) F(pix_perm) F(g_t) F(breg_sr_px) \
   F(breg_sr_ch) F(h_rule) F(pg_gamma_w) F(pg_q) F(ell_fill_px) F(ell_fill_num) F(ell_fill_n) F(tail_mode) F(no_fused) \
   F(ell_pb) F(ell_stream) F(ell_hv_n) F(ell_hv_npx) F(ell_hv_ngrp) F(ell_hv_px) F(ell_hv_px_off) F(ell_hv_pm) F(ell_hv_klc) F(ell_hv_kl) \
-  F(ell_hv_grp) F(ell_hv_grp_off) F(ell_hv_wm) F(hpart_alt) F(ell_blk_cnt)
+  F(ell_hv_grp) F(ell_hv_grp_off) F(ell_hv_wm) F(hpart_alt) F(ell_blk_cnt) F(ell_keep_h) F(ell_keep_w)
 
 // the caller's view of the state must be this library's (include/espm_mu.h, ESPM_MU_ABI_VERSION): checked before any field is read
 static int check_abi(const espm_mu_state* st) {
@@ -66,6 +66,9 @@ static int check_state(const espm_mu_state* st) {
                  ESPM_ELL_TILE);
   }
   ESPM_REQUIRE(st->ell_stream == 0 || (st->ell_stream == 1 && st->x_dtype == ESPM_X_ELL), "ell_stream=%d: 0, or 1 with the sparse store", st->ell_stream);
+  // (the kept part of streamed lists: ignored without ell_stream, otherwise counted in list groups of a tile and channel groups of a block)
+  ESPM_REQUIRE(st->ell_stream == 0 || (st->ell_keep_h >= 0 && st->ell_keep_h <= st->tile_px / 64 && st->ell_keep_w >= 0 && st->ell_keep_w <= (st->n_cg < 255 ? st->n_cg : 255)),
+               "ell_keep_h=%d, ell_keep_w=%d: 0..%d list groups of a tile, 0..%d channel groups", st->ell_keep_h, st->ell_keep_w, st->tile_px / 64, st->n_cg);
   ESPM_REQUIRE(st->ell_fill_n >= 0 && (st->ell_fill_n == 0 || (st->x_dtype == ESPM_X_ELL && st->ell_fill_px && st->ell_fill_num)),
                "ell_fill_n=%d needs the sparse store, ell_fill_px and ell_fill_num", st->ell_fill_n);
   ESPM_REQUIRE(st->ell_hv_n >= 0 && (st->ell_hv_n == 0 || (st->x_dtype == ESPM_X_ELL && st->h_rule == 0 && !st->breg_sr_px && st->ell_hv_npx >= 1 &&
@@ -412,7 +415,7 @@ static int h_half(const espm_mu_state* st, int src, int write_h, const WTailArgs
   if (int rc = ell_pre_h(st, src, s)) return rc;
   if (int rc = record(at_launch, s)) return rc;
   if (fused) {
-    if (int rc = launch_fused_ell(a, make_w_args(st), st->nblk_w, s, st->no_fused == 2, st->ell_stream)) return rc;
+    if (int rc = launch_fused_ell(a, make_w_args(st), st->nblk_w, s, st->no_fused == 2, st->ell_stream ? (1 | st->ell_keep_h << 8 | st->ell_keep_w << 16) : 0)) return rc;   // (keep values: 0..255, check_state)
     return ell_post(st, 1 - src, true, true, s);
   }
   if (int rc = launch_h_ell(a, nblk_h(st), s)) return rc;

@@ -228,6 +228,16 @@ __device__ __forceinline__ uint32_t ell_list_load(const uint32_t* p) {
   if constexpr (STREAM) return __builtin_nontemporal_load(p);
   else return *p;
 }
+// A streamed launch may still KEEP part of its lists in the last-level cache (espm_mu_state.ell_keep_h, ell_keep_w): `g` of the `n` units
+// of a walk - list groups of a tile, channel groups of a block - read their rows with plain loads, the rest with non-temporal ones.  The kept
+// indices are spread evenly over 0 .. n - 1 (index j is kept where floor((j + 1) g / n) steps), the same in every workgroup: units are handed
+// out in index order, so kept and streamed units are in flight side by side through the whole walk and the workgroups stay level.
+// g = 0 keeps nothing, g = n everything.  espm_amd/ell.py has the same rule (keep_indices).
+__host__ __device__ __forceinline__ bool ell_kept(int j, int g, int n) { return ((j + 1) * g) / n != (j * g) / n; }
+template <bool B>
+struct EllStream {
+  static constexpr bool value = B;
+};
 // ell_walk_pre: `use_pre` (wave-uniform) - the first PF batches were requested by the caller ahead of time (ell_walk_request: the fused
 // kernel asks for a wave's first rows while its workgroup is still staging the table, so that the walk starts without a round trip to
 // memory of its own) and arrive in `pre`.

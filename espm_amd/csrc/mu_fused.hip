@@ -218,7 +218,13 @@ int launch_fused_ell(const HStepArgs& h, const WAccumArgs& w, int nblk, hipStrea
   fa.h = h;
   fa.w = w;
   fa.static_units = static_units;
-  fa.stream_lists = stream_lists;
+  // stream_lists: espm_mu_state.ell_stream in bit 0 and, with it, the kept part of the streamed lists - ell_keep_h in bits 8..15, ell_keep_w in
+  // bits 16..23 (list groups per tile, channel groups per block: checked by the caller, mu_api.hip); 0: plain loads, 1: every row non-temporal
+  ESPM_REQUIRE(stream_lists >= 0 && stream_lists < (1 << 24) && ((stream_lists & 1) || stream_lists == 0), "fused half-steps: stream_lists=%d", stream_lists);
+  fa.stream_lists = (unsigned char)(stream_lists & 1);
+  fa.keep_h = (unsigned char)((stream_lists >> 8) & 255);
+  fa.keep_w = (unsigned char)((stream_lists >> 16) & 255);
+  fa.keep_pad = 0;
   switch (h.k) {
 #if ESPM_MIN_K <= 8
 #define ESPM_X(KK) case KK: return launch_fused_k<KK>(fa, nblk, stream);

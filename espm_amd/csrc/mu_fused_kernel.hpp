@@ -138,7 +138,11 @@ struct FusedArgs {
   int h_segs;       // segments per list group of the H walk: below the full geometry at least 1024 / pb, at most ESPM_FUSED_MAX_SEGS; at the full
                     // geometry from 6 components on as many as the LDS holds partials for (FusedGeom<K>::S_MIN .. S_MAX)
   int w_split;      // the W walk's units are half channel groups, summed through two copies of the slab in LDS (needs slab_lds and room for the second copy)
-  int stream_lists; // espm_mu_state.ell_stream: the STREAM instance where one is built (the full geometry's lean instances)
+  // (four bytes in the place of ABI 7's `int stream_lists`: the argument block keeps its size and the other fields their offsets)
+  unsigned char stream_lists;   // espm_mu_state.ell_stream: the STREAM instance where one is built (the full geometry's lean instances)
+  unsigned char keep_h;         // espm_mu_state.ell_keep_h: the STREAM instance reads that many of a tile's 8 list groups with plain loads (mu_ell_kernel.hpp: ell_kept) ...
+  unsigned char keep_w;         // ... and espm_mu_state.ell_keep_w of the block's n_cg channel groups; 0, 0: every list row non-temporal
+  unsigned char keep_pad;
   int slab_lds;     // the W walk collects the block's slab in the numerators' region and the workgroup writes it out as rows (the launcher: where k n_pad floats fit there and the record reduction has scratch of its own)
 };
 
@@ -198,6 +202,8 @@ struct FusedGeom {
 // dynamic units, the slab collected in LDS, scratch of its own for the record reduction) - the launcher checks every one of them on the
 // host (launch_fused_k) and takes the generic instance otherwise.  Instantiated in mu_fused_plain.hip.
 // STREAM: the lists with non-temporal loads (mu_ell_kernel.hpp: ell_list_load; espm_mu_state.ell_stream) - instances of the full geometry only.
+// Of these lists FusedArgs::keep_h / keep_w units per tile / block are read with plain loads and stay in the last-level cache from one
+// iteration to the next (ell_kept): a unit calls one of two instances of its walk, the same rows in the same order - the same bits at every setting.
 template <int K, bool LOSS, int UNR_H, int UNR_W, int NT, bool FULL, bool PLAIN = false, bool STREAM = false>   // FULL: the full geometry, block and tile sizes are constants
 __global__ __launch_bounds__(NT) void mu_fused_ell_kernel(const FusedArgs fa) {
   static_assert(!FULL || NT == ESPM_ELL_WTHREADS, "full geometry: 1024 threads");
@@ -413,7 +419,14 @@ __global__ __launch_bounds__(NT) void mu_fused_ell_kernel(const FusedArgs fa) {
         for (int kk = 0; kk < K; ++kk) hk[kk] = a.h_in[(size_t)kk * a.p_pad + px];
         if constexpr (IMPL) ell_implicit_lane<K>(hk);
         const uint32_t* lrow = a.ell + (size_t)beg * 64 + lane;
-        ell_h_rows<K, LOSS, UNR_H, PF, PRIO, STREAM, true, WALK_PP, IMPL>(lrow, x0, x1, mid, tab, a.n_pad, a.ell_bits, hk, acc, kl);
+        if constexpr (STREAM) {   // every segment of a kept list group with plain loads (wave-uniform; ell_kept, mu_ell_kernel.hpp)
+          if (ell_kept(gi & ((1 << GPT_SHIFT) - 1), fa.keep_h, 1 << GPT_SHIFT))
+            ell_h_rows<K, LOSS, UNR_H, PF, PRIO, false, true, WALK_PP, IMPL>(lrow, x0, x1, mid, tab, a.n_pad, a.ell_bits, hk, acc, kl);
+          else
+            ell_h_rows<K, LOSS, UNR_H, PF, PRIO, true, true, WALK_PP, IMPL>(lrow, x0, x1, mid, tab, a.n_pad, a.ell_bits, hk, acc, kl);
+        } else {
+          ell_h_rows<K, LOSS, UNR_H, PF, PRIO, STREAM, true, WALK_PP, IMPL>(lrow, x0, x1, mid, tab, a.n_pad, a.ell_bits, hk, acc, kl);
+        }
         if constexpr (PRIO > 0) __builtin_amdgcn_s_setprio(0);
       }
     }
@@ -499,13 +512,28 @@ __global__ __launch_bounds__(NT) void mu_fused_ell_kernel(const FusedArgs fa) {
       }
     }
     const uint32_t* lrow = w.ell + (size_t)beg * 64 + lane;
-    ell_walk_pre<K, UNR_W, PF, PRIO, STREAM, WALK_PP>(lrow + (size_t)(u0 - beg) * 64, u1 - u0, EllGetUnitFix<K, IMPL>(PB), [&](float, const float (&h)[K]) {
-      ell_axpy_i<K, IMPL>(acc, h, __builtin_amdgcn_rcpf(ell_dot_i<K, IMPL>(h, gw)));
-    }, EllNoFlush(), wkind == 1, fw_rows);
-    ell_walk_pre<K, UNR_W, PF, PRIO, STREAM, WALK_PP>(lrow + (size_t)(g0 - beg) * 64, g1 - g0, EllGetFix<K, IMPL>(tab, PB, PBITS), [&](float x, const float (&h)[K]) {
-      const float r = x * __builtin_amdgcn_rcpf(ell_dot_i<K, IMPL>(h, gw));
-      ell_axpy_i<K, IMPL>(acc, h, r);
-    }, EllNoFlush(), wkind == 2, fw_rows);
+    if constexpr (STREAM) {   // a kept channel group with plain loads (wave-uniform; ell_kept, mu_ell_kernel.hpp), the others non-temporal: two instances of the walks below
+      auto walk_group = [&](auto streamed) {
+        constexpr bool ST = decltype(streamed)::value;
+        ell_walk_pre<K, UNR_W, PF, PRIO, ST, WALK_PP>(lrow + (size_t)(u0 - beg) * 64, u1 - u0, EllGetUnitFix<K, IMPL>(PB), [&](float, const float (&h)[K]) {
+          ell_axpy_i<K, IMPL>(acc, h, __builtin_amdgcn_rcpf(ell_dot_i<K, IMPL>(h, gw)));
+        }, EllNoFlush(), wkind == 1, fw_rows);
+        ell_walk_pre<K, UNR_W, PF, PRIO, ST, WALK_PP>(lrow + (size_t)(g0 - beg) * 64, g1 - g0, EllGetFix<K, IMPL>(tab, PB, PBITS), [&](float x, const float (&h)[K]) {
+          const float r = x * __builtin_amdgcn_rcpf(ell_dot_i<K, IMPL>(h, gw));
+          ell_axpy_i<K, IMPL>(acc, h, r);
+        }, EllNoFlush(), wkind == 2, fw_rows);
+      };
+      if (ell_kept(cg, fa.keep_w, w.n_cg)) walk_group(EllStream<false>());
+      else walk_group(EllStream<true>());
+    } else {
+      ell_walk_pre<K, UNR_W, PF, PRIO, STREAM, WALK_PP>(lrow + (size_t)(u0 - beg) * 64, u1 - u0, EllGetUnitFix<K, IMPL>(PB), [&](float, const float (&h)[K]) {
+        ell_axpy_i<K, IMPL>(acc, h, __builtin_amdgcn_rcpf(ell_dot_i<K, IMPL>(h, gw)));
+      }, EllNoFlush(), wkind == 1, fw_rows);
+      ell_walk_pre<K, UNR_W, PF, PRIO, STREAM, WALK_PP>(lrow + (size_t)(g0 - beg) * 64, g1 - g0, EllGetFix<K, IMPL>(tab, PB, PBITS), [&](float x, const float (&h)[K]) {
+        const float r = x * __builtin_amdgcn_rcpf(ell_dot_i<K, IMPL>(h, gw));
+        ell_axpy_i<K, IMPL>(acc, h, r);
+      }, EllNoFlush(), wkind == 2, fw_rows);
+    }
     if constexpr (PRIO > 0) __builtin_amdgcn_s_setprio(0);
     if constexpr (IMPL) {   // the last sum, once per unit: S - (the others), in a fixed order (its true value is >= 0)
       float low = acc[0];

@@ -269,6 +269,52 @@ def block_counts(Xpm, n_pad, tile_px=512):
     return out
 
 
+def keep_indices(keep, n):
+    """Which `keep` of the indices 0 .. n - 1 a streamed launch reads with plain loads (include/espm_mu.h: ell_keep_h, ell_keep_w): index j
+    where floor((j + 1) keep / n) steps - spread evenly, as the kernel decides it per unit (ell_kept, csrc/mu_ell_kernel.hpp)."""
+    return [j for j in range(n) if ((j + 1) * keep) // n != (j * keep) // n]
+
+
+def keep_group_bytes(h_off, w_off, groups_per_tile, n_cg):
+    """List bytes per unit index of the two walks: (per list-group index inside an H tile, summed over the tiles; per channel-group index,
+    summed over the W blocks), two lists of ints.  h_off, w_off: the offset arrays of the store (two words per group, rows of 256 bytes):
+    one small reduction each and one read-back."""
+    rows_h = (h_off[2::2] - h_off[0:-2:2]).to(torch.int64)
+    rows_w = (w_off[2::2] - w_off[0:-2:2]).to(torch.int64)
+    pad = (-rows_h.numel()) % groups_per_tile
+    if pad:
+        rows_h = torch.cat([rows_h, rows_h.new_zeros(pad)])
+    both = torch.cat([rows_h.view(-1, groups_per_tile).sum(0), rows_w.view(-1, n_cg).sum(0)]) * 256
+    both = [int(v) for v in both.cpu()]
+    return both[:groups_per_tile], both[groups_per_tile:]
+
+
+def keep_policy(bytes_h, bytes_w, budget, list_bytes=None, stream_bytes=_lib.ELL_STREAM_BYTES):
+    """(ell_stream, ell_keep_h, ell_keep_w) of include/espm_mu.h for a store whose lists hold bytes_h[j] / bytes_w[j] bytes in the units of
+    index j (keep_group_bytes) - a pure function of its arguments.
+    Lists of at most stream_bytes stay whole in the last-level cache with plain loads: (0, 0, 0), as before.  Larger lists are streamed
+    and the part of them kept in that cache is the largest that fits `budget` bytes: the H walk's share first - the largest keep value
+    whose kept set (keep_indices) holds at most the budget - and, once the H lists are kept whole, what is left of the budget for the
+    W walk.  (Measured at the headline image, profiles/r07_keep_sweep.log: one walk kept whole beats the same bytes spread over both,
+    and the H walk kept beats the W walk kept.)  Both values grow with the budget and the kept bytes never exceed it.
+    budget <= 0: nothing kept."""
+    if list_bytes is None:
+        list_bytes = sum(bytes_h) + sum(bytes_w)
+    if list_bytes <= stream_bytes:
+        return 0, 0, 0
+
+    def kept(sizes, keep):
+        return sum(sizes[j] for j in keep_indices(keep, len(sizes)))
+
+    def largest(sizes, share):
+        return max([keep for keep in range(1, len(sizes) + 1) if kept(sizes, keep) <= share], default=0)
+    if budget <= 0:
+        return 1, 0, 0
+    keep_h = largest(bytes_h, budget)
+    keep_w = largest(bytes_w, budget - kept(bytes_h, keep_h)) if keep_h == len(bytes_h) else 0
+    return 1, keep_h, keep_w
+
+
 def lds_bytes_h(n_pad, k):
     """LDS the sparse H-step needs: the GW table plus the partial numerators of a 512-pixel tile (two sets for k <= 6,
     where the list groups of a window are walked in pairs)."""

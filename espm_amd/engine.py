@@ -521,6 +521,17 @@ class MUEngine:
         # ESPM_ELL_STREAM_MB: another threshold, for A/B - 0 streams always, a huge one never)
         limit = float(os.environ["ESPM_ELL_STREAM_MB"]) * 2 ** 20 if os.environ.get("ESPM_ELL_STREAM_MB") else _lib.ELL_STREAM_BYTES
         st.ell_stream = int(self.x_store == "ell" and self.x_bytes > limit)
+        st.ell_keep_h = st.ell_keep_w = 0
+        if st.ell_stream:
+            # ... and of streamed lists a part is kept there all the same: they are fixed for the whole fit (include/espm_mu.h: ell_keep_h,
+            # ell_keep_w; ell.keep_policy).  ESPM_ELL_KEEP_MB: another budget (0: nothing kept); ESPM_ELL_KEEP_GROUPS=h:w: the two values
+            # themselves (A/B)
+            from . import ell as _ell
+            budget = int(float(os.environ["ESPM_ELL_KEEP_MB"]) * 2 ** 20) if os.environ.get("ESPM_ELL_KEEP_MB") else _lib.ELL_KEEP_BYTES
+            self.keep_bytes = _ell.keep_group_bytes(self.ell["ell_h_off"], self.ell["ell_w_off"], st.tile_px // 64, st.n_cg)
+            _, st.ell_keep_h, st.ell_keep_w = _ell.keep_policy(*self.keep_bytes, budget, list_bytes=self.x_bytes, stream_bytes=limit)
+            if os.environ.get("ESPM_ELL_KEEP_GROUPS"):
+                st.ell_keep_h, st.ell_keep_w = (int(v) for v in os.environ["ESPM_ELL_KEEP_GROUPS"].split(":"))
         # autotune: at the first load_state the launch plans that apply to this problem are timed on the ingested image and
         # the fastest is kept (see autotune_plan)
         # "auto": the policy of the product (SmoothNMF.fit hands it down, bench.py too): timing the plans costs ~35 ms of device

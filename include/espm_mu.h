@@ -112,6 +112,9 @@ enum { ESPM_LAYOUT_CM = 0 /* (n, p) channel-major */, ESPM_LAYOUT_PM = 1 /* (p, 
 #define ESPM_ELL_UNIT_MAX_N 4080 /* sparse store: H-step lists have unit rows when n <= this (index << 4 < 2^16, and at most 255 ones in any of the builder's 16 residue classes of a list: its 8-bit counters) */
 #define ESPM_ELL_PAIR_MAX_K 6 /* sparse store H-step: list groups are walked in pairs (2 partial numerators) up to this k */
 #define ESPM_ELL_STREAM_BYTES (256 << 20) /* sparse store: list bytes beyond which a caller sets espm_mu_state.ell_stream (the MI355X's last-level cache) */
+#define ESPM_ELL_KEEP_BYTES 207000000 /* sparse store, streamed lists: the bytes of them a caller keeps in that cache all the same (espm_mu_state.ell_keep_h,
+                                       * ell_keep_w): the best point of the sweep at 2048 x 512^2 - the H walk's 230.0 MB kept, the W walk's 233.5 MB
+                                       * streamed, profiles/r07_keep_sweep.log - less 10 %: the cache is shared with whatever else runs */
 #define ESPM_FUSED_MIN_PB 512 /* sparse store: W blocks (ell_pb) from which the fused launch is the default whatever their number           */
 #define ESPM_FUSED_MIN_BLOCKS 192 /* ... and smaller blocks when there are at least this many (one per CU, or nearly: a 64-row shard of the
                                    * headline image has 256 of 128 pixels; config 2's 128 blocks leave half the chip to the two launches,
@@ -165,7 +168,7 @@ enum { ESPM_LAYOUT_CM = 0 /* (n, p) channel-major */, ESPM_LAYOUT_PM = 1 /* (p, 
  * point that takes a state checks st->struct_size == sizeof(espm_mu_state) and st->abi_version == ESPM_MU_ABI_VERSION
  * first and fails with ESPM_EINVAL otherwise: a binding whose copy of the layout has drifted is refused instead of
  * having its pointers misread.  A binding can also compare its layout field by field with espm_mu_state_layout(). */
-#define ESPM_MU_ABI_VERSION 7
+#define ESPM_MU_ABI_VERSION 8
 
 typedef struct espm_mu_state {
   uint32_t struct_size;   /* sizeof(espm_mu_state) as the CALLER sees it                  */
@@ -303,7 +306,10 @@ typedef struct espm_mu_state {
    * last-level cache, i.e. exceed ESPM_ELL_STREAM_BYTES: the one-launch iteration then reads them with non-temporal loads, which
    * leave that cache to what IS read again (measured: -1.4 % at 2048 x 512^2, where the lists are 0.5 GB; +15 % if set on a
    * 64-row shard of it, whose lists stay in the cache from one iteration to the next).  A hint: results are the same bits
-   * either way, and a launch without a streamed form (blocks below ESPM_ELL_PB pixels, the generic instances) ignores it. */
+   * either way, and a launch without a streamed form (blocks below ESPM_ELL_PB pixels, the generic instances) ignores it.
+   * 0 or 1; anything else is ESPM_EINVAL.  ABI 8: with 1 a part of the lists can be kept in that cache all the same - the lists are
+   * fixed for a whole fit: ell_keep_h, ell_keep_w at the end of this struct (2048 x 512^2: the H walk's 230 MB kept behind the W walk's
+   * 234 MB streamed, 118.5-119.4 -> 113.8-114.5 us per iteration, profiles/r07_keep_sweep.log). */
   int32_t ell_stream;
   /* Sparse store, heavy elements: integer counts ESPM_ELL_HEAVY_MIN .. ESPM_ELL_HEAVY_MAX (256 .. 2^24; fp32 holds every integer up
    * to 2^24 exactly) are kept outside the 16-bit lists, with their exact values; the lists, ell_klc and the permutations are those of
@@ -342,6 +348,15 @@ typedef struct espm_mu_state {
    * of G W divided by their sums sigma_c (one 16-byte read per list entry) and owes the loss sum_c ell_blk_cnt[b][c] log2 sigma_c per
    * block: it needs this array whenever compute_loss is set and fails with ESPM_EINVAL without it.  Nothing else reads it. */
   const float* ell_blk_cnt;
+  /* Sparse store with ell_stream = 1: the part of the lists that is KEPT in the last-level cache.  The lists are fixed for a whole fit,
+   * so what stays on the die after one iteration need not come from memory in the next: ell_keep_h of the tile_px / 64 list groups of
+   * every H tile and ell_keep_w of the n_cg channel groups of every W block are read with plain loads, the rest with non-temporal ones.
+   * Which ones: index j of n is kept where floor((j + 1) keep / n) steps - spread evenly, the same in every tile and block (kernel:
+   * ell_kept, mu_ell_kernel.hpp; a caller: espm_amd/ell.py, keep_policy, which fits the kept bytes into ESPM_ELL_KEEP_BYTES).
+   * 0, 0: every list row non-temporal, as before ABI 8.  Ignored when ell_stream = 0; otherwise 0 <= ell_keep_h <= tile_px / 64 and
+   * 0 <= ell_keep_w <= n_cg or ESPM_EINVAL.  Hints like ell_stream: the same bits at every setting. */
+  int32_t ell_keep_h;
+  int32_t ell_keep_w;
 } espm_mu_state;
 
 const char* espm_mu_version(void);
