@@ -31,6 +31,7 @@ DIAG_MAX_K, DIAG_BLOCK, DIAG_CHUNK = _D["ESPM_DIAG_MAX_K"], _D["ESPM_DIAG_BLOCK"
 CDIAG_BLOCK, CDIAG_PCHUNK = _D["ESPM_CDIAG_BLOCK"], _D["ESPM_CDIAG_PCHUNK"]
 BIN_BLOCK, BIN_PARTS = _D["ESPM_BIN_BLOCK"], _D["ESPM_BIN_PARTS"]
 SPLIT_BLOCK, SPLIT_HEAVY, SPLIT_MAX_K = _D["ESPM_SPLIT_BLOCK"], _D["ESPM_SPLIT_HEAVY"], _D["ESPM_SPLIT_MAX_K"]
+SAMPLE_BLOCK, SAMPLE_HEAVY, SAMPLE_MAX_RATE, SAMPLE_MAX_K = (_D["ESPM_SAMPLE_" + n] for n in ("BLOCK", "HEAVY", "MAX_RATE", "MAX_K"))
 SRC_F32, SRC_F64 = 0, 1
 LAYOUT_CM, LAYOUT_PM = 0, 1
 ABI_VERSION = _D["ESPM_MU_ABI_VERSION"]
@@ -165,6 +166,9 @@ SYMBOLS = {
     "espm_thin_counts": (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int, _i64, _i64, _i64, C.c_uint64, _vp, _vp, _i64, _vp]),
     "espm_split_deviance": (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int, _i64, _i64, _i64, C.c_uint64, _vp, _vp, C.c_int, C.c_double,
                                       _vp, _vp, _vp, _vp]),
+    # Poisson sampling (csrc/mu_sample.hip): narrow build only, plain device pointers
+    "espm_poisson_sample": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _i64, _i64, C.c_uint64, _i64, _vp, C.c_int, C.c_int, _i64, _vp, _vp]),
+    "espm_sample_deviance": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _i64, _i64, C.c_uint64, _i64, C.c_int, C.c_double, _vp, _vp]),
 }
 
 

@@ -986,6 +986,143 @@ class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
         self.W_std_, self.D_std_ = out["W_std"], out["D_std"]
         return out
 
+    # ---- draws from the fitted model: a simulated image, a scale for the deviance map, the parametric bootstrap -------------------
+    def _sampling_model(self, who):
+        """(D, H): the fitted model ``G_ @ W_`` (n, k) and ``H_`` (k, p) in counts, in fp64, after the refusals of ``simulate``,
+        ``calibrate_deviance`` and ``bootstrap`` - all raised before anything is uploaded."""
+        from espm_amd import sampling
+        check_is_fitted(self, "W_")
+        if getattr(self, "_shard_group", None) is not None:
+            raise NotImplementedError(f"{who} does not cover shard(): the draws run on one GPU")
+        if getattr(self, "bin_", None) is not None:
+            raise ValueError(f"{who}: this estimator was fitted by fit_binned with bin {self.bin_}: its fit is a coarse fit and an "
+                             "H-only fit, which a draw from G_ W_ H_ does not stand for")
+        k = int(self.H_.shape[0])
+        if k > sampling.MAX_K:
+            raise NotImplementedError(f"{who}: {k} components (the sampling kernels are built for 1..{sampling.MAX_K})")
+        D = np.asarray(self.W_ if self._identity_G else self.G_ @ self.W_, dtype=np.float64)
+        return D, np.asarray(self.H_, dtype=np.float64)
+
+    def simulate(self, seed=0, replicate=0, device=False):
+        """A count image drawn from the fitted model: replicate ``replicate`` (0 .. 2^32 - 2) of ``G_ @ W_``, ``H_`` under ``seed``
+        (0 .. 2^64 - 1) by the rule of ``espm_amd.sampling`` - X* ~ Poisson(G_ W_ H_) entry by entry, a function of (model, seed,
+        replicate) alone, bit for bit.  The reference draws its synthetic images with ``np.random.poisson`` on the host
+        (datasets/base.py:68).
+
+        Returns uint16 counts, (channels, pixels), or (pixels, channels) with ``hspy_comp`` - the orientation ``fit`` takes - as a
+        host array, or with ``device=True`` a device tensor.  The model is in count units whatever ``normalize`` was (``W_`` is the
+        un-normalised one, as for ``pixel_diagnostics``).  ValueError if any entry saturated (a rate above 65535, or a draw above
+        it).  ``shard()``ed estimators raise NotImplementedError, estimators fitted by ``fit_binned`` ValueError, before anything is
+        uploaded."""
+        from espm_amd import sampling
+        D, H = self._sampling_model("simulate")
+        X, info = sampling.sample(D, H, seed=seed, replicate=replicate, dtype=np.uint16, layout="pm" if self.hspy_comp else "cm", device=device)
+        if info["saturated"] or info["invalid"]:
+            raise ValueError(f"simulate: {info['saturated']} entries saturated the 16-bit counts and {info['invalid']} had no valid rate")
+        return X
+
+    def calibrate_deviance(self, X=None, n_rep=100, seed=0):
+        """The deviance map on the scale of its own null distribution.  At EDS doses (a fraction of a count to a few counts per entry)
+        the Poisson deviance of a pixel is far from chi-square, so ``deviance_`` alone cannot say whether a pixel is badly fitted or
+        merely faint.  Runs ``pixel_diagnostics(X)`` for ``deviance_``, then ``sampling.null_deviance`` - the deviance of ``n_rep``
+        replicates (0 .. n_rep - 1 under ``seed``) of the fitted model against the fitted model, on the device, none of them stored -
+        and ``sampling.calibrate``.  Sets, each (p,): ``deviance_null_mean_``, ``deviance_null_std_`` (ddof = 1), ``deviance_z_`` =
+        (deviance_ - mean) / std and ``deviance_pvalue_`` = (1 + #{r : null_r >= deviance_}) / (n_rep + 1); and ``deviance_null_rep_``,
+        the number of replicates.  Returns them as a dict with ``deviance``.
+
+        The null is FRESH data against the generating model, not refitted to every replicate: the deviance of the fitted image is
+        in-sample and sits about k (the degrees of freedom a pixel's abundances took) lower than a fresh draw's, so the calibration is
+        conservative - a pixel flagged here is flagged with room to spare.
+
+        ``X`` as for ``pixel_diagnostics``; 1 .. 8 components, the diagnostics' limit; at least 2 replicates.  Refusals as for
+        ``simulate``, before anything is uploaded."""
+        from espm_amd import sampling
+        D, H = self._sampling_model("calibrate_deviance")
+        n_rep = sampling._check_n_rep(n_rep)
+        if n_rep < 2:
+            raise ValueError("calibrate_deviance needs at least two replicates (the null standard deviation has ddof = 1)")
+        from espm_amd.splitting import _check_seed
+        _check_seed(seed)
+        self.pixel_diagnostics(X)
+        null = sampling.null_deviance(D, H, n_rep=n_rep, seed=seed, replicate0=0, log_shift=self.log_shift)
+        cal = sampling.calibrate(self.deviance_, null)
+        self.deviance_null_mean_, self.deviance_null_std_ = cal["null_mean"], cal["null_std"]
+        self.deviance_z_, self.deviance_pvalue_, self.deviance_null_rep_ = cal["z"], cal["pvalue"], n_rep
+        return dict(deviance=self.deviance_, null_mean=cal["null_mean"], null_std=cal["null_std"], z=cal["z"], pvalue=cal["pvalue"])
+
+    def _bootstrap_start(self):
+        """(W, H) a refit of a replicate starts from: the fit itself - under ``normalize`` with W in the normalised units the fit
+        iterates in (``W_`` is divided by ``norm_factor_`` at the end of a fit)."""
+        W = np.asarray(self.W_)
+        return (W * self.norm_factor_ if self.normalize else W), np.asarray(self.H_)
+
+    def _bootstrap_copy(self, max_iter=None):
+        """An unfitted estimator with this one's parameters (``sklearn.base.clone``), the same G, ``shape_2d``, ``fixed_W`` /
+        ``fixed_H`` objects and precision mode."""
+        from sklearn.base import clone
+        boot = clone(self)
+        boot.G, boot.shape_2d, boot.fixed_W, boot.fixed_H = self.G, self.shape_2d, self.fixed_W, self.fixed_H
+        if self._fp64():
+            boot.set_precision("fp64")
+        if max_iter is not None:
+            boot.max_iter = int(max_iter)
+        return boot
+
+    def bootstrap(self, n_boot=20, seed=0, max_iter=None, return_samples=False):
+        """Parametric bootstrap of the fit AS IT WAS RUN: for r = 0 .. n_boot - 1, replicate r of the fitted model is drawn on the
+        device (``simulate(seed, r)``) and fitted by a copy of this estimator - ``sklearn.base.clone`` of its parameters with the same
+        G, ``shape_2d``, ``fixed_W`` / ``fixed_H`` and precision mode - warm-started at the fit (``fit_transform(X*, W=W_, H=H_)``,
+        W in the units the fit iterates in; ``max_iter``: the copies' limit, by default the estimator's own).  The spread of the
+        refits is the error bar of W and H TOGETHER, with ``mu``, ``lambda_L``, the simplex and the floors in force - what the
+        Cramer-Rao bounds ``H_std_`` (given the spectra) and ``W_std_`` (given the abundances) leave out.  It does not include the
+        bias of the fit, the error of the model itself (a missing phase), or starts other than the fit; with few iterations it is
+        the spread after that many iterations.  The warm start keeps the components' order: no matching step.
+
+        Sets ``W_boot_mean_``, ``W_boot_std_`` (the shape of ``W_``), ``H_boot_mean_``, ``H_boot_std_`` (k, p) and ``D_boot_std_``
+        (n, k: of the spectra ``G_ @ W_``) - means and standard deviations (ddof = 1) over the replicates, accumulated in fp64
+        (Welford) - and ``n_boot_``, ``boot_seed_``.  No fitted attribute of the estimator itself changes.  Returns them as a dict;
+        with ``return_samples=True`` the dict also holds ``W_samples`` (n_boot, ...) and ``H_samples`` (n_boot, k, p) for
+        percentile intervals.  At least 2 replicates; refusals as for ``simulate``, before anything is uploaded."""
+        from espm_amd import sampling
+        from espm_amd.splitting import _check_seed
+        D, H = self._sampling_model("bootstrap")
+        n_boot, seed = sampling._check_n_rep(n_boot), _check_seed(seed)
+        if n_boot < 2:
+            raise ValueError("bootstrap needs at least two replicates (the standard deviations have ddof = 1)")
+        sampling._check_replicate(0, n_boot)
+        D, H = sampling._model(D, H)
+        W0, H0 = self._bootstrap_start()
+        layout = "pm" if self.hspy_comp else "cm"
+        Dd, Hd, dev = sampling._upload(D, H)
+        stats = [None, None, None]   # (mean, M2) of W, H, G W
+        samples = ([], []) if return_samples else None
+        for r in range(n_boot):
+            Xr, saturated, invalid = sampling._draw(Dd, Hd, dev, seed, r, np.dtype(np.uint16), layout)
+            if saturated or invalid:
+                raise ValueError(f"bootstrap: replicate {r} has {saturated} saturated entries and {invalid} without a valid rate")
+            boot = self._bootstrap_copy(max_iter)
+            # (counts up to 65535 are exact in float32; handed over as integers, scikit-learn's validation would make them float64)
+            boot.fit_transform(Xr.cpu().numpy().astype(np.float64 if self._fp64() else np.float32), W=W0.copy(), H=H0.copy())
+            Wr, Hr = np.asarray(boot.W_, dtype=np.float64), np.asarray(boot.H_, dtype=np.float64)
+            for i, v in enumerate((Wr, Hr, Wr if boot._identity_G else np.asarray(boot.G_, dtype=np.float64) @ Wr)):
+                if stats[i] is None:
+                    stats[i] = [v.copy(), np.zeros_like(v)]
+                else:
+                    delta = v - stats[i][0]
+                    stats[i][0] += delta / (r + 1)
+                    stats[i][1] += delta * (v - stats[i][0])
+            if return_samples:
+                samples[0].append(Wr), samples[1].append(Hr)
+        std = [np.sqrt(m2 / (n_boot - 1)) for _, m2 in stats]
+        self.W_boot_mean_, self.W_boot_std_ = stats[0][0], std[0]
+        self.H_boot_mean_, self.H_boot_std_ = stats[1][0], std[1]
+        self.D_boot_std_ = std[2]
+        self.n_boot_, self.boot_seed_ = n_boot, seed
+        out = dict(W_mean=self.W_boot_mean_, W_std=self.W_boot_std_, H_mean=self.H_boot_mean_, H_std=self.H_boot_std_, D_std=self.D_boot_std_)
+        if return_samples:
+            out.update(W_samples=np.stack(samples[0]), H_samples=np.stack(samples[1]))
+        return out
+
     def inverse_transform(self, W):
         """G W H_ (espm/estimators/base.py:461-477)."""
         check_is_fitted(self)

@@ -26,6 +26,8 @@ What is here:
 * ``SpectrumImage.thin(q, seed)`` (``espm_amd.splitting``: two independent count images from one) and
   ``decompose(signal, est, split=(q, seed))``: the fit of the thinned image, scored on the held-out counts
   (``NMFEstimator.fit_split``).
+* ``SpectrumImage.simulate(est, seed, replicate)`` (``espm_amd.sampling``: a count image drawn from the fitted model),
+  ``calibrated_deviance_maps(est)`` and ``bootstrap_maps(est)``: the maps of ``NMFEstimator.calibrate_deviance`` / ``bootstrap``.
 * ``hyperspy_extension.yaml`` (next to this file) and the ``hyperspy.extensions`` entry point in ``pyproject.toml`` declare
   the signal type ``EDS_espm_amd`` -> ``EDSespmAMD`` below, defined only when hyperspy imports.
 """
@@ -95,6 +97,17 @@ class SpectrumImage:
         Xa, Xb = splitting.thin(self.unfolded(), q=q, seed=seed, layout="pm")
         return SpectrumImage(Xa.reshape(self.data.shape)), SpectrumImage(Xb.reshape(self.data.shape))
 
+    @staticmethod
+    def simulate(est, seed=0, replicate=0, shape_2d=None):
+        """A ``SpectrumImage`` (ny, nx, n) of 16-bit counts drawn from the fitted model of ``est`` (``NMFEstimator.simulate``: replicate
+        ``replicate`` of ``G_ @ W_``, ``H_`` by the rule of ``espm_amd.sampling``).  ``shape_2d``: the image grid, by default the
+        estimator's."""
+        X = est.simulate(seed=seed, replicate=replicate)
+        if not est.hspy_comp:
+            X = np.ascontiguousarray(X.T)
+        ny, nx = (int(v) for v in (shape_2d if shape_2d is not None else est.shape_2d))
+        return SpectrumImage(X.reshape((ny, nx, X.shape[1])))
+
     def decomposition(self, algorithm, output_dimension=None, return_info=False, bin=None, split=None, **kwargs):
         """hyperspy's ``decomposition(algorithm=<object>)`` for a custom estimator: ``fit_transform(data (p, n))`` ->
         loadings (p, k), ``components_`` (k, n) -> factors (n, k); the estimator stays in ``learning_results``.  ``bin=(by, bx)``:
@@ -143,6 +156,22 @@ def diagnostic_maps(est, shape_2d=None):
         raise AttributeError("call est.pixel_diagnostics() first: it sets deviance_ and H_std_")
     ny, nx = (int(v) for v in (shape_2d if shape_2d is not None else est.shape_2d))
     return np.asarray(est.deviance_).reshape((ny, nx)), np.asarray(est.H_std_).reshape((-1, ny, nx))
+
+
+def calibrated_deviance_maps(est, shape_2d=None):
+    """``est.deviance_z_`` and ``est.deviance_pvalue_`` (set by ``est.calibrate_deviance()``) in the navigation shape: (ny, nx) each."""
+    if not hasattr(est, "deviance_z_"):
+        raise AttributeError("call est.calibrate_deviance() first: it sets deviance_z_ and deviance_pvalue_")
+    ny, nx = (int(v) for v in (shape_2d if shape_2d is not None else est.shape_2d))
+    return np.asarray(est.deviance_z_).reshape((ny, nx)), np.asarray(est.deviance_pvalue_).reshape((ny, nx))
+
+
+def bootstrap_maps(est, shape_2d=None):
+    """``est.H_boot_std_`` (set by ``est.bootstrap()``) in the navigation shape, like the loadings: (k, ny, nx)."""
+    if not hasattr(est, "H_boot_std_"):
+        raise AttributeError("call est.bootstrap() first: it sets H_boot_std_")
+    ny, nx = (int(v) for v in (shape_2d if shape_2d is not None else est.shape_2d))
+    return np.asarray(est.H_boot_std_).reshape((-1, ny, nx))
 
 
 def diagnostic_spectra(est):

@@ -48,6 +48,8 @@
  *                            the four sums its risk estimate reduces to, from X on the device instead of a rebin and an upsample per candidate
  *   espm_thin_counts, espm_split_deviance <- (new) Poisson count splitting: a training and an independent held-out image from one measured
  *                            map, and the held-out deviance of a fit of the first; no reference analogue
+ *   espm_poisson_sample, espm_sample_deviance <- espm/datasets/base.py:68 (np.random.poisson of the model on the host) as a rule on the
+ *                            element's index: a count image drawn from a fitted model on the device, and the deviance of such draws
  *   espm_lu_pl            <- espm/estimators/updates.py:179 -> scikit-learn's _initialize_nmf -> _randomized_range_finder: the LU
  *                            normaliser of its power iterations (scipy.linalg.lu(A, permute_l=True)[0]) on tall device matrices
  *
@@ -829,6 +831,47 @@ int espm_thin_counts(const void* x, int x_dtype, int x_layout, int64_t ld, int n
 int espm_split_deviance(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, int64_t p_total, int64_t j0, int64_t q_threshold,
                         uint64_t seed, const double* d, const double* h, int k, double log_shift, double* dev_a, double* dev_b,
                         int64_t* cnt_b, espm_stream_t stream);
+
+/* ---- Poisson sampling (csrc/mu_sample.hip; espm_amd.sampling, NMFEstimator.simulate / calibrate_deviance / bootstrap) ----
+ * A count image drawn from a model: d (n, k) row-major, the spectra G W in counts, and h (k, p), the abundances of the pixels j0 .. j0 + p - 1
+ * of an image of p_total pixels (the whole image: j0 = 0, p_total = p).  Plain device pointers, no espm_mu_state.
+ * THE RULE (the sample is defined by it, not by the kernels).  The image is logically (n, p_total), channel-major: element (c, j) has the
+ * 64-bit index e = c * p_total + j - in either layout, in any slab - as in count splitting.
+ *   rate     y = sum_i d[c, i] h[i, j] in fp64, i ascending from 0, starting from +0; every product and every sum is rounded on its own (NO
+ *            fused multiply-add), so that a plain host loop gets the same bits of y and no libm function enters the rule.  y not finite
+ *            or negative: the entry is 0 and counted INVALID.  y > ESPM_SAMPLE_MAX_RATE: the entry is the dtype's maximum and counted
+ *            SATURATED; no draw is made for it.
+ *   words    block b of element e is Philox4x32-10 (Salmon et al. 2011) with the counter (e low 32, e high 32, b, replicate + 1) and the key
+ *            (seed low 32, seed high 32); replicate = 0 .. 2^32 - 2, so the fourth counter word is never 0: count splitting has 0 there,
+ *            and thinning a simulated image with the same seed shares no word with the sampler.
+ *   unit     a word w gives N(w) = #{ i in 0 .. 11 : w >= T_i } ~ Poisson(1), with T_i = floor(2^32 sum_{j <= i} e^-1 / j!):
+ *              5e2d58d8 bc5ab1b1 eb715e1d fb239797 ff1025f5 ffd90f3b fffa8b71 ffff540c ffffed1f fffffe21 ffffffd4 fffffffc
+ *            (mean 1 + 1.4e-9, variance 1 + 1.3e-8).
+ *   count    m = floor(y), thr = floor((y - m) 2^32), both exact in fp64.  With word_i = word (i mod 4) of block (i div 4) and
+ *            N0 = N(word_0):
+ *              x = sum_{i < m} N(word (i mod 4) of block (4 + i div 4))  +  #{ i in 1 .. N0 : word_i < thr }
+ *            - m unit pieces, and a Poisson(1) thinned to the fractional part (N0 <= 12: blocks 0 .. 3 serve it).  x ~ Poisson(y) up to
+ *            the 2^-32 quantisation of the fraction.  An x above the output dtype's maximum is stored as that maximum and counted SATURATED.
+ *   espm_poisson_sample   x: the replicate as x_dtype ESPM_DIAG_X_U8 or ESPM_DIAG_X_U16, (n, p) for ESPM_LAYOUT_CM or (p, n) for
+ *                        ESPM_LAYOUT_PM, rows ld apart.  counts[0] = saturated entries, counts[1] = invalid entries (zeroed by the call,
+ *                        on `stream`).  One launch: a pixel per thread, an entry of m >= ESPM_SAMPLE_HEAVY unit pieces is drawn by its whole
+ *                        wave.  The values use no atomics; the two counters are integer sums: exact, the same from call to call.
+ *   espm_sample_deviance  dev (n_rep, p): for replicate r = replicate0 .. replicate0 + n_rep - 1 and pixel j, with Y = max(y, log_shift)
+ *                        (a NaN rate stays NaN) and x the rule's draw as espm_poisson_sample stores it at 16 bits (invalid: 0,
+ *                        saturated: 65535), dev = 2 sum_c (x ln(x / Y) - x + Y), the first term 0 where x == 0.  The image is never
+ *                        stored.  The sums run in channel order in the pixel's own thread: two calls give the same bits.  One launch.
+ * k = 1..ESPM_SAMPLE_MAX_K.  ESPM_EINVAL, before the device is touched and with the offending values in the message, for a null pointer,
+ * k outside 1..ESPM_SAMPLE_MAX_K, n or p below 1, a slab outside 0 .. p_total, n x p_total beyond a 64-bit index, ld below the row
+ * length, a dtype other than u8 / u16, a layout that does not exist, replicate (or replicate0 + n_rep - 1) outside 0 .. 2^32 - 2,
+ * n_rep below 1, log_shift not positive.  Only the narrow build has the kernels; the wide builds return ESPM_EUNSUPPORTED. */
+#define ESPM_SAMPLE_BLOCK 256        /* pixels (threads) per workgroup                                                          */
+#define ESPM_SAMPLE_HEAVY 256        /* unit pieces from which the wave shares an entry's draws                                 */
+#define ESPM_SAMPLE_MAX_RATE 65535   /* rates above it are not drawn: the entry saturates                                       */
+#define ESPM_SAMPLE_MAX_K 32
+int espm_poisson_sample(const double* d, const double* h, int k, int n, int p, int64_t p_total, int64_t j0, uint64_t seed, int64_t replicate,
+                        void* x, int x_dtype, int x_layout, int64_t ld, int64_t* counts, espm_stream_t stream);
+int espm_sample_deviance(const double* d, const double* h, int k, int n, int p, int64_t p_total, int64_t j0, uint64_t seed, int64_t replicate0,
+                         int n_rep, double log_shift, double* dev, espm_stream_t stream);
 
 #ifdef __cplusplus
 }
