@@ -32,6 +32,7 @@ CDIAG_BLOCK, CDIAG_PCHUNK = _D["ESPM_CDIAG_BLOCK"], _D["ESPM_CDIAG_PCHUNK"]
 BIN_BLOCK, BIN_PARTS = _D["ESPM_BIN_BLOCK"], _D["ESPM_BIN_PARTS"]
 SPLIT_BLOCK, SPLIT_HEAVY, SPLIT_MAX_K = _D["ESPM_SPLIT_BLOCK"], _D["ESPM_SPLIT_HEAVY"], _D["ESPM_SPLIT_MAX_K"]
 SAMPLE_BLOCK, SAMPLE_HEAVY, SAMPLE_MAX_RATE, SAMPLE_MAX_K = (_D["ESPM_SAMPLE_" + n] for n in ("BLOCK", "HEAVY", "MAX_RATE", "MAX_K"))
+ATTRIB_BLOCK, ATTRIB_PCHUNK, ATTRIB_WALK, ATTRIB_HEAVY, ATTRIB_MAX_K = (_D["ESPM_ATTRIB_" + n] for n in ("BLOCK", "PCHUNK", "WALK", "HEAVY", "MAX_K"))
 SRC_F32, SRC_F64 = 0, 1
 LAYOUT_CM, LAYOUT_PM = 0, 1
 ABI_VERSION = _D["ESPM_MU_ABI_VERSION"]
@@ -169,6 +170,12 @@ SYMBOLS = {
     # Poisson sampling (csrc/mu_sample.hip): narrow build only, plain device pointers
     "espm_poisson_sample": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _i64, _i64, C.c_uint64, _i64, _vp, C.c_int, C.c_int, _i64, _vp, _vp]),
     "espm_sample_deviance": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _i64, _i64, C.c_uint64, _i64, C.c_int, C.c_double, _vp, _vp]),
+    # count attribution (csrc/mu_attrib.hip): narrow build only, plain device pointers
+    "espm_attribute_expected": (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp,
+                                          C.c_size_t, _vp]),
+    "espm_attribute_expected_scratch": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "espm_assign_counts": (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int, _i64, _i64, _vp, _vp, C.c_int, C.c_uint64, _vp, _i64, _i64,
+                                     _vp, _vp]),
 }
 
 

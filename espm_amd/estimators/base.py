@@ -986,6 +986,90 @@ class NMFEstimator(ABC, _PixelTransform, TransformerMixin, BaseEstimator):
         self.W_std_, self.D_std_ = out["W_std"], out["D_std"]
         return out
 
+    # ---- the measured counts behind every component: in expectation, and as a random split of the image ---------------------------
+    def attribute_counts(self, X=None):
+        """How many of the MEASURED counts stand behind every component (``espm_amd.attribution.expected`` on ``G_ @ W_`` and ``H_``):
+        entry (c, p) of X gives x d_cj h_jp / y counts to component j.  The reference quotes the MODELLED intensity instead
+        (``utils.get_explained_intensity_W``, the ``sqrt(N) / N`` of ``concentration_report(fit_error=True)``); the two agree at an
+        unregularised fixed point and differ with ``mu``, ``lambda_L``, a simplex, a floor or a fit that stopped early.
+
+        Sets ``pixel_counts_`` (k, p), oriented as ``H_``; ``channel_counts_`` (n, k); ``intensity_W_``, of ``W_``'s shape: the measured
+        counts behind every entry of ``W_`` (with a physics model or a dictionary G: W o (G^T R)); ``model_intensity_W_``: the
+        reference's function on ``G_``, ``W_``, ``H_``; ``intensity_rel_error_`` = 1 / sqrt(``intensity_W_``), inf where 0 (times 100:
+        the reference's percentage); ``component_counts_`` (k,); ``explained_counts_ratio_`` (k,) = ``component_counts_`` / total
+        counts, the NMF analogue of an explained-variance ratio; ``unattributed_counts_``: the counts of entries whose model fell
+        below ``log_shift``.  Returns them as a dict (keys without the underscore); with ``hspy_comp`` the returned
+        ``pixel_counts`` is (p, k), as ``fit_transform`` returns ``H_.T``.
+
+        ``X`` as for ``pixel_diagnostics``: the fitted image in counts, (channels, pixels), or (pixels, channels) with ``hspy_comp``;
+        ``X=None`` takes the fit's ``X_`` un-scaled, with the cost and the ``log_shift`` fill described there.  Computed in fp64
+        whatever the estimator's precision, on the current device (a ``shard()``ed estimator: every rank computes everything on its
+        own device).  1 .. 32 components."""
+        from espm_amd import attribution
+        from espm_amd.utils import get_explained_intensity_W
+        check_is_fitted(self, "W_")
+        k = int(self.H_.shape[0])
+        if k > attribution.MAX_K:
+            raise NotImplementedError(f"attribute_counts: {k} components (the kernels are built for 1..{attribution.MAX_K})")
+        layout = "cm"
+        if X is None:
+            check_is_fitted(self, "X_")
+            self._refuse_binned_X("attribute_counts")
+            X = np.asarray(self._X_fixed())
+        else:
+            if not hasattr(X, "shape") or getattr(X, "ndim", 0) != 2:
+                X = np.asarray(X)
+            if X.ndim != 2:
+                raise ValueError("X must be 2-D")
+            layout = "pm" if self.hspy_comp else "cm"
+            n, p = (X.shape[1], X.shape[0]) if self.hspy_comp else (X.shape[0], X.shape[1])
+            if n != self.G_.shape[0]:
+                raise ValueError(f"X has {n} channels, the fitted G_ has {self.G_.shape[0]}")
+            if p != self.H_.shape[1]:
+                raise ValueError(f"X has {p} pixels, the fitted H_ has {self.H_.shape[1]}")
+        W, H = np.asarray(self.W_, dtype=np.float64), np.asarray(self.H_, dtype=np.float64)
+        G = None if self._identity_G else np.asarray(self.G_, dtype=np.float64)
+        out = attribution.expected(X, W if G is None else G @ W, H, log_shift=self.log_shift, layout=layout)
+        self.pixel_counts_, self.channel_counts_ = out["pixel_counts"], out["channel_counts"]
+        self.intensity_W_ = attribution.intensity(G, W, out["ratio_sums"])
+        self.model_intensity_W_ = get_explained_intensity_W(np.asarray(self.G_, dtype=np.float64), W, H)
+        with np.errstate(divide="ignore"):
+            self.intensity_rel_error_ = 1.0 / np.sqrt(self.intensity_W_)
+        self.component_counts_ = self.pixel_counts_.sum(axis=1)
+        total = float(np.asarray(out["counts"], dtype=np.float64).sum())
+        self.explained_counts_ratio_ = self.component_counts_ / total if total > 0 else np.zeros(k)
+        self.unattributed_counts_ = float(out["unattributed"].sum())
+        return dict(pixel_counts=self.pixel_counts_.T if self.hspy_comp else self.pixel_counts_, channel_counts=self.channel_counts_,
+                    intensity_W=self.intensity_W_, model_intensity_W=self.model_intensity_W_, intensity_rel_error=self.intensity_rel_error_,
+                    component_counts=self.component_counts_, explained_counts_ratio=self.explained_counts_ratio_,
+                    unattributed_counts=self.unattributed_counts_)
+
+    def assign_counts(self, X, seed=0, device=False):
+        """The count image X split into k count images, one per component, that add up to X exactly
+        (``espm_amd.attribution.assign`` on ``G_ @ W_`` and ``H_``): every single count goes to component j with probability
+        d_cj h_jp / y.  By the Poisson splitting theorem each part is an honest noisy acquisition of its phase alone - integer
+        counts that keep whatever the model missed - where ``inverse_transform`` gives only the smooth model of a phase.
+
+        X is required (the fit's ``X_`` is not integer counts): 0 .. 65535, a host array or a device tensor, (channels, pixels), or
+        (pixels, channels) with ``hspy_comp``.  Returns (k, *X.shape) in the dtype X was uploaded in (uint8 or uint16), a host array
+        or with ``device=True`` a device tensor - k times the memory of X.  A function of (X, fit, seed) alone, bit for bit.
+        Non-zero entries without a valid modelled rate (none, where the fit kept ``H_`` and ``W_`` above the ``log_shift`` floor) go to
+        the first image, with a RuntimeWarning.  ``shard()``ed estimators raise NotImplementedError, estimators fitted by
+        ``fit_binned`` ValueError, floating-point X TypeError - all before anything is uploaded."""
+        from espm_amd import attribution
+        check_is_fitted(self, "W_")
+        if getattr(self, "_shard_group", None) is not None:
+            raise NotImplementedError("assign_counts does not cover shard(): the split runs on one GPU")
+        self._refuse_binned_X("assign_counts")
+        D = np.asarray(self.W_ if self._identity_G else self.G_ @ self.W_, dtype=np.float64)
+        parts, info = attribution.assign(X, D, np.asarray(self.H_, dtype=np.float64), seed=seed, layout="pm" if self.hspy_comp else "cm",
+                                         device=device)
+        if info["invalid"]:
+            import warnings
+            warnings.warn(f"assign_counts: {info['invalid']} non-zero entries have no valid modelled rate (not finite, or not above 0): "
+                          "their counts are in the first component's image", RuntimeWarning, stacklevel=2)
+        return parts
+
     # ---- draws from the fitted model: a simulated image, a scale for the deviance map, the parametric bootstrap -------------------
     def _sampling_model(self, who):
         """(D, H): the fitted model ``G_ @ W_`` (n, k) and ``H_`` (k, p) in counts, in fp64, after the refusals of ``simulate``,

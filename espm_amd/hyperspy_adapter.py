@@ -108,6 +108,17 @@ class SpectrumImage:
         ny, nx = (int(v) for v in (shape_2d if shape_2d is not None else est.shape_2d))
         return SpectrumImage(X.reshape((ny, nx, X.shape[1])))
 
+    def assign_counts(self, est, seed=0):
+        """A list of k ``SpectrumImage``s of this one's shape and dtype, one per component of the fitted ``est``: every count of this
+        image handed to one component by ``NMFEstimator.assign_counts`` (the rule of ``espm_amd.attribution``; integer counts
+        0 .. 65535).  They add up to this image exactly, and for Poisson counts each is an independent noisy acquisition of its phase
+        alone."""
+        X = self.unfolded() if est.hspy_comp else self.X
+        parts = est.assign_counts(X, seed=seed)
+        if not est.hspy_comp:
+            parts = np.ascontiguousarray(parts.transpose(0, 2, 1))
+        return [SpectrumImage(part.reshape(self.data.shape)) for part in parts]
+
     def decomposition(self, algorithm, output_dimension=None, return_info=False, bin=None, split=None, **kwargs):
         """hyperspy's ``decomposition(algorithm=<object>)`` for a custom estimator: ``fit_transform(data (p, n))`` ->
         loadings (p, k), ``components_`` (k, n) -> factors (n, k); the estimator stays in ``learning_results``.  ``bin=(by, bx)``:
@@ -172,6 +183,23 @@ def bootstrap_maps(est, shape_2d=None):
         raise AttributeError("call est.bootstrap() first: it sets H_boot_std_")
     ny, nx = (int(v) for v in (shape_2d if shape_2d is not None else est.shape_2d))
     return np.asarray(est.H_boot_std_).reshape((-1, ny, nx))
+
+
+def component_count_maps(est, shape_2d=None):
+    """``est.pixel_counts_`` (set by ``est.attribute_counts()``) in the navigation shape, like the loadings: (k, ny, nx) maps of the
+    measured counts behind every component.  ``shape_2d``: the image grid, by default the estimator's."""
+    if not hasattr(est, "pixel_counts_"):
+        raise AttributeError("call est.attribute_counts() first: it sets pixel_counts_ and channel_counts_")
+    ny, nx = (int(v) for v in (shape_2d if shape_2d is not None else est.shape_2d))
+    return np.asarray(est.pixel_counts_).reshape((-1, ny, nx))
+
+
+def component_spectra(est):
+    """``est.channel_counts_`` (set by ``est.attribute_counts()``) on the signal axis, like the factors: (k, n) spectra of the measured
+    counts behind every component; they add up to the measured sum spectrum (less the unattributed counts)."""
+    if not hasattr(est, "channel_counts_"):
+        raise AttributeError("call est.attribute_counts() first: it sets pixel_counts_ and channel_counts_")
+    return np.asarray(est.channel_counts_).T
 
 
 def diagnostic_spectra(est):

@@ -63,3 +63,11 @@ def rescaled_DH(D, H):
     if (s <= 0).any():
         s = np.maximum(nnls(H.T, o)[0], 1e-10)
     return D @ np.diag(1 / s), np.diag(s) @ H
+
+
+def get_explained_intensity_W(G, W, H):
+    """The modelled intensity behind every entry of W in the model G W H: entry (i, j) is sum_cp G_ci W_ij H_jp =
+    (sum_c G_ci) W_ij (sum_p H_jp) (espm/utils.py:396-414, what ``concentration_report(fit_error=True)`` takes its sqrt(N) / N from).
+    ``espm_amd.attribution`` gives the counts the DATA attribute to the same entry; the two agree at an unregularised fixed point."""
+    G, W, H = np.asarray(G), np.asarray(W), np.asarray(H)
+    return G.sum(0)[:, np.newaxis] * W * H.sum(1)[np.newaxis, :]

@@ -50,6 +50,9 @@
  *                            map, and the held-out deviance of a fit of the first; no reference analogue
  *   espm_poisson_sample, espm_sample_deviance <- espm/datasets/base.py:68 (np.random.poisson of the model on the host) as a rule on the
  *                            element's index: a count image drawn from a fitted model on the device, and the deviance of such draws
+ *   espm_attribute_expected, espm_assign_counts <- espm/utils.py:396-414 (get_explained_intensity_W, the modelled intensity behind
+ *                            every entry of W) for the MEASURED counts: the responsibilities of the components from a pass over X, and
+ *                            (new) the image split into k integer images, one per component, that add up to it
  *   espm_lu_pl            <- espm/estimators/updates.py:179 -> scikit-learn's _initialize_nmf -> _randomized_range_finder: the LU
  *                            normaliser of its power iterations (scipy.linalg.lu(A, permute_l=True)[0]) on tall device matrices
  *
@@ -872,6 +875,58 @@ int espm_poisson_sample(const double* d, const double* h, int k, int n, int p, i
                         void* x, int x_dtype, int x_layout, int64_t ld, int64_t* counts, espm_stream_t stream);
 int espm_sample_deviance(const double* d, const double* h, int k, int n, int p, int64_t p_total, int64_t j0, uint64_t seed, int64_t replicate0,
                          int n_rep, double log_shift, double* dev, espm_stream_t stream);
+
+/* ---- count attribution (csrc/mu_attrib.hip; espm_amd.attribution, NMFEstimator.attribute_counts / assign_counts) ----
+ * How many of the MEASURED counts stand behind every component of a model d (n, k) row-major, the spectra G W in counts, and h (k, p).
+ * Plain device pointers, no espm_mu_state; x, x_layout and ld as for the diagnostics.  y_cj = sum_i d[c, i] h[i, j].
+ *   espm_attribute_expected  x as x_dtype ESPM_DIAG_X_* (u8, u16, f32, f64).  With Y = max(y, log_shift), all arithmetic in fp64:
+ *                          num_h[i, j]  (k, p) = h[i, j] sum_c x_cj d[c, i] / Y_cj: the counts of pixel j attributed to component i (the EM
+ *                                         responsibilities, the numerator of the multiplicative update of h); the sum runs in channel order
+ *                                         in the pixel's own thread
+ *                          ratio[c, i]  (n, k) = sum_j x_cj h[i, j] / Y_cj: d o ratio are the counts of channel c attributed to component i,
+ *                                         and with d = G W, W o (G^T ratio) those behind every entry of W.  A workgroup takes
+ *                                         ESPM_ATTRIB_BLOCK channels and ESPM_ATTRIB_PCHUNK pixels and writes its partial sums to `scratch`
+ *                                         (device memory, espm_attribute_expected_scratch(n, p, k) bytes: chunks x k x n doubles); a last
+ *                                         launch adds the chunks in ascending order
+ *                          counts[j]    (p) = sum_c x_cj: int64_t (exact) for u8 / u16 x, double for f32 / f64 x
+ *                        An entry with x == 0 costs its read only.  Three launches on `stream` (one pass over x per side, the reduction).
+ *                        Nothing is accumulated atomically: two calls give the same bits, and so do the two layouts of one image.
+ *   espm_assign_counts   x as ESPM_DIAG_X_U8 or ESPM_DIAG_X_U16, the pixels j0 .. j0 + p - 1 of an image of p_total pixels (the whole image:
+ *                        j0 = 0, p_total = p), as for espm_thin_counts; h holds those p pixels.  parts: k images in x's dtype and layout,
+ *                        image i at parts + i * part_stride (elements), rows out_ld apart; their sum is x exactly.  counts[0] (zeroed by
+ *                        the call, on `stream`): the number of invalid entries.
+ * THE RULE of espm_assign_counts (the parts are defined by it, not by the kernel).  The image is logically (n, p_total), channel-major:
+ * element (c, j) has the 64-bit index e = c * p_total + j - in either layout, in any slab - as in count splitting.
+ *   rates    s_0 = d[c, 0] * h[0, j], s_i = s_(i-1) + d[c, i] * h[i, j] in fp64: every product and every sum is rounded on its own (NO fused
+ *            multiply-add), so that a plain host loop gets the same bits.  a = s_(k-1).
+ *   invalid  x > 0 and a not a finite number above 0: all x counts go to component 0 and the entry is counted INVALID.
+ *   words    count t = 0 .. x - 1 of a valid entry takes word (t mod 4) of Philox4x32-10 (Salmon et al. 2011) with the counter
+ *            (e low 32, e high 32, 0x80000000 | (t div 4), 0) and the key (seed low 32, seed high 32).  Count splitting has t div 4 < 2^14 in
+ *            the third word and Poisson sampling never 0 in the fourth: attributing a thinned or a simulated image under the same seed
+ *            shares no word with the call that made it.
+ *   count    with u = ((double)w * 2^-32) * a (the first product exact, the second rounded once), the count goes to the smallest i with
+ *            u < s_i, and to k - 1 if there is none.
+ * By the Poisson splitting theorem the parts of x ~ Poisson(a) are independent Poisson(d[c, i] h[i, j]) images.  One launch: channel-major x
+ * a pixel per thread (h in registers, d through LDS), pixel-major x a channel per thread (d in registers, h through LDS); a zero entry
+ * costs its read and its k stores, another one k products and ceil(x / 4) Philox calls; an entry of ESPM_ATTRIB_HEAVY or more is drawn
+ * by its whole wave.  The parts use no atomics; the counter is an integer sum: exact, the same from call to call.
+ * k = 1..ESPM_ATTRIB_MAX_K.  ESPM_EINVAL, before the device is touched and with the offending values in the message, for a null pointer,
+ * k outside 1..ESPM_ATTRIB_MAX_K, n or p below 1, a dtype or layout that does not exist (espm_assign_counts: a dtype other than u8 / u16),
+ * ld or out_ld below the row length, part_stride below one image, a slab outside 0 .. p_total, n x p_total beyond a 64-bit index,
+ * scratch_bytes below what the query returns, log_shift not positive.  Only the narrow build has the kernels; the wide builds return
+ * ESPM_EUNSUPPORTED, and their query returns 0. */
+#define ESPM_ATTRIB_BLOCK 256     /* threads per workgroup: pixels, or channels                                                  */
+#define ESPM_ATTRIB_PCHUNK 1024   /* pixels per workgroup of the channel side of espm_attribute_expected                         */
+#define ESPM_ATTRIB_WALK 512      /* channels (channel-major) or pixels (pixel-major) a workgroup of espm_assign_counts walks    */
+#define ESPM_ATTRIB_HEAVY 256     /* counts from which the wave shares an entry's draws (16-bit images only)                     */
+#define ESPM_ATTRIB_MAX_K 32
+int espm_attribute_expected(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, const double* d, const double* h, int k,
+                            double log_shift, double* num_h, double* ratio, void* counts, void* scratch, size_t scratch_bytes,
+                            espm_stream_t stream);
+size_t espm_attribute_expected_scratch(int n, int p, int k);
+int espm_assign_counts(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, int64_t p_total, int64_t j0, const double* d,
+                       const double* h, int k, uint64_t seed, void* parts, int64_t part_stride, int64_t out_ld, int64_t* counts,
+                       espm_stream_t stream);
 
 #ifdef __cplusplus
 }
