@@ -18,27 +18,9 @@ from __future__ import annotations
 
 import numpy as np
 
+from espm_amd._image_args import check_model, layout_code
+
 MAX_K = 32   # ESPM_ATTRIB_MAX_K
-
-
-def _model(X_shape, D, H, layout, who):
-    """(n, p, k, D, H) after every check of the shapes, D and H as C-contiguous fp64 host arrays: nothing is uploaded here."""
-    if layout not in ("cm", "pm"):
-        raise ValueError(f"layout must be 'cm' ((channels, pixels)) or 'pm' ((pixels, channels)), not {layout!r}")
-    if len(X_shape) != 2 or X_shape[0] < 1 or X_shape[1] < 1:
-        raise ValueError("X must be a non-empty 2-D array or tensor")
-    D, H = np.ascontiguousarray(D, dtype=np.float64), np.ascontiguousarray(H, dtype=np.float64)
-    if D.ndim != 2 or H.ndim != 2 or D.shape[1] != H.shape[0] or D.shape[1] < 1:
-        raise ValueError("D must be (channels, components) and H (components, pixels)")
-    n, p = (int(X_shape[0]), int(X_shape[1])) if layout == "cm" else (int(X_shape[1]), int(X_shape[0]))
-    k = int(D.shape[1])
-    if D.shape[0] != n:
-        raise ValueError(f"X has {n} channels, D has {D.shape[0]}")
-    if H.shape[1] != p:
-        raise ValueError(f"X has {p} pixels, H has {H.shape[1]}")
-    if k > MAX_K:
-        raise NotImplementedError(f"{who}: {k} components (the kernels are built for 1..{MAX_K})")
-    return n, p, k, D, H
 
 
 def _on_device(X):
@@ -62,7 +44,7 @@ def expected(X, D, H, log_shift=1e-14, layout="cm"):
     order, no atomics: two calls, and both layouts, give the same bits."""
     if getattr(X, "ndim", None) != 2:
         X = np.asarray(X)
-    n, p, k, D, H = _model(tuple(X.shape), D, H, layout, "expected")
+    n, p, k, D, H = check_model(D, H, "expected", MAX_K, tuple(X.shape), layout)
     if not log_shift > 0:
         raise ValueError("log_shift must be positive")
     import torch
@@ -77,7 +59,7 @@ def expected(X, D, H, log_shift=1e-14, layout="cm"):
         cnt = torch.empty(p, dtype=torch.int64 if code in (_lib.DIAG_X_U8, _lib.DIAG_X_U16) else torch.float64, device=dev)
         need = int(_lib.lib.espm_attribute_expected_scratch(n, p, k))
         scratch = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
-        _lib.check(_lib.lib.espm_attribute_expected(_ptr(Xd), code, _lib.LAYOUT_CM if layout == "cm" else _lib.LAYOUT_PM, int(Xd.stride(0)), n, p,
+        _lib.check(_lib.lib.espm_attribute_expected(_ptr(Xd), code, layout_code(layout), int(Xd.stride(0)), n, p,
                                                     _ptr(Dd), _ptr(Hd), k, float(log_shift), _ptr(num), _ptr(ratio), _ptr(cnt), _ptr(scratch),
                                                     need, _stream()))
         pixel_counts, ratio_sums, counts = num.cpu().numpy(), ratio.cpu().numpy(), cnt.cpu().numpy()
@@ -98,7 +80,7 @@ def assign(X, D, H, seed=0, layout="cm", device=False):
     from espm_amd import splitting
     seed = splitting._check_seed(seed)
     X, n, p = splitting._counts(X, layout)
-    n, p, k, D, H = _model(tuple(X.shape), D, H, layout, "assign")
+    n, p, k, D, H = check_model(D, H, "assign", MAX_K, tuple(X.shape), layout)
     import torch
 
     from espm_amd import _lib
@@ -108,7 +90,7 @@ def assign(X, D, H, seed=0, layout="cm", device=False):
         Dd, Hd = torch.from_numpy(D).to(dev), torch.from_numpy(H).to(dev)
         parts = torch.empty((k,) + tuple(Xd.shape), dtype=Xd.dtype, device=dev)
         cnt = torch.empty(1, dtype=torch.int64, device=dev)
-        _lib.check(_lib.lib.espm_assign_counts(_ptr(Xd), code, _lib.LAYOUT_CM if layout == "cm" else _lib.LAYOUT_PM, int(Xd.stride(0)), n, p, p, 0,
+        _lib.check(_lib.lib.espm_assign_counts(_ptr(Xd), code, layout_code(layout), int(Xd.stride(0)), n, p, p, 0,
                                                _ptr(Dd), _ptr(Hd), k, seed, _ptr(parts), int(parts.stride(0)), int(parts.stride(1)), _ptr(cnt),
                                                _stream()))
         invalid = int(cnt.item())

@@ -23,17 +23,18 @@ from __future__ import annotations
 
 import numpy as np
 
+from espm_amd._image_args import check_layout, image_dims, layout_code
+
 
 def _check(X, shape_2d, layout):
     """(n, ny, nx) before anything is uploaded."""
-    if layout not in ("cm", "pm"):
-        raise ValueError(f"layout must be 'cm' ((channels, pixels)) or 'pm' ((pixels, channels)), not {layout!r}")
+    check_layout(layout)
     if getattr(X, "ndim", None) != 2:
         raise ValueError("X must be a 2-D array or tensor")
     if shape_2d is None or len(shape_2d) != 2:
         raise ValueError("shape_2d must be (rows, columns) of the image")
     ny, nx = int(shape_2d[0]), int(shape_2d[1])
-    n, p = (int(X.shape[0]), int(X.shape[1])) if layout == "cm" else (int(X.shape[1]), int(X.shape[0]))
+    n, p = image_dims(X.shape, layout)
     if ny < 1 or nx < 1 or n < 1:
         raise ValueError("X and shape_2d must not be empty")
     if ny * nx != p:
@@ -107,7 +108,7 @@ def rebin(X, shape_2d, bin, layout="cm"):
             f32 = Xd.dtype == torch.float32
         gny, gnx = binned_shape((ny, nx), (by, bx))
         out = torch.empty((n, gny * gnx) if layout == "cm" else (gny * gnx, n), dtype=torch.float32 if f32 else torch.float64, device=dev)
-        _lib.check(_lib.lib.espm_rebin_pixels(_ptr(Xd), code, _lib.LAYOUT_CM if layout == "cm" else _lib.LAYOUT_PM, int(Xd.stride(0)), n, ny, nx,
+        _lib.check(_lib.lib.espm_rebin_pixels(_ptr(Xd), code, layout_code(layout), int(Xd.stride(0)), n, ny, nx,
                                               by, bx, _ptr(out), _lib.DIAG_X_F32 if f32 else _lib.DIAG_X_F64, int(out.stride(0)), _stream()))
         return out.cpu().numpy()
 
@@ -131,7 +132,7 @@ def binning_sums(X, shape_2d, bins, layout="cm"):
         out = torch.empty(2 + 2 * nb, dtype=torch.float64, device=dev)
         nbytes = int(_lib.lib.espm_binning_sums_scratch(n, ny, nx, nb))
         scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        _lib.check(_lib.lib.espm_binning_sums(_ptr(Xd), code, _lib.LAYOUT_CM if layout == "cm" else _lib.LAYOUT_PM, int(Xd.stride(0)), n, ny, nx,
+        _lib.check(_lib.lib.espm_binning_sums(_ptr(Xd), code, layout_code(layout), int(Xd.stride(0)), n, ny, nx,
                                               host_bins.ctypes.data, nb, _ptr(out), _ptr(scratch), nbytes, _stream()))
         host = out.cpu().numpy()
     return float(host[0]), float(host[1]), host[2::2].copy(), host[3::2].copy()

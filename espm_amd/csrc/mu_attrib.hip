@@ -2,12 +2,11 @@
 // model d h - in expectation (the EM responsibilities, the numerator of the multiplicative update) and as a random split of the image
 // into k integer images that add up to it exactly (the Poisson splitting theorem).
 //
-// Every kernel here has the same shape.  X is a matrix whose rows are ld apart; the index that runs along a row is the LANE index (a
-// thread owns one), the index that runs across the rows is the WALK index (a thread walks it).  Channel-major X: lane = pixel, walk =
-// channel; pixel-major X: lane = channel, walk = pixel.  A thread keeps its lane's k-vector in registers (h[:, pixel], or d[channel, :]);
-// the k-vectors of the walk (rows of d, or columns of h) go through LDS in chunks, padded with zeros to KP = 4, 8, 16 or 32 columns, and
-// are read back as broadcasts.  The model's value y = sum_i d_i h_i of an entry is the same expression whichever of the two vectors is
-// whose, so both layouts compute the same bits of it.
+// Every kernel here has the same shape (mu_image_pass.hpp's walk).  X is a matrix whose rows are ld apart; the index that runs along a
+// row is the LANE index (a thread owns one), the index that runs across the rows is the WALK index (a thread walks it).  Channel-major
+// X: lane = pixel, walk = channel; pixel-major X: lane = channel, walk = pixel.  A thread keeps its lane's k-vector in registers
+// (h[:, pixel], or d[channel, :]); the k-vectors of the walk go through LDS (stage) and are read back as broadcasts.  The model's value
+// y = sum_i d_i h_i of an entry is the same expression whichever of the two vectors is whose, so both layouts compute the same bits.
 //
 //   expected_kernel  what a lane gathers over its walk: acc_i = sum_walk (x / Y) g_i, g the walk's vector, Y = max(y, log_shift); an
 //                entry with x == 0 costs its read only.
@@ -20,13 +19,12 @@
 //   assign_kernel    the rule of the header, entry by entry: the k cumulative rates without fused multiply-adds, their running maximum
 //                m_i = max_{j <= i} s_j, and per count one Philox word w and t = (w 2^-32) a: "the smallest i with t < s_i" is at most
 //                i exactly when t < m_i, so cum_i = #{counts : t < m_i} and the parts are the differences of cum (the last one x - cum).
-//                An entry of ESPM_ATTRIB_HEAVY counts or more is drawn by its whole wave as in mu_split.hip: a ballot finds the lanes that
-//                hold one; for each in turn x, e, a and m are broadcast, lane l takes the blocks of four l, l + 64, ..., and the counts
-//                are added across the wave (integers: any order gives the same sum).
+//                An entry of ESPM_ATTRIB_HEAVY counts or more is drawn by its whole wave: mu_image_pass.hpp's for_each_heavy, with
+//                a and m broadcast beside x and e and k - 1 counters summed.  The loop is WRITTEN OUT in assign_entry: through the
+//                header's driver and a callable the widest 16-bit instance took two more vector and two more accumulation registers.
 //
-// No value is accumulated atomically.  The number of invalid entries of espm_assign_counts is a sum of integers (per thread, per wave,
-// then one 64-bit integer atomic per workgroup that saw one, onto the zeroed counter): exact, and the same from call to call.  Only the
-// narrow build (ESPM_KP == 8) instantiates the kernels; the wide builds export the entry points as stubs.
+// No value is accumulated atomically.  The number of invalid entries of espm_assign_counts is a sum of integers (block_count_add, onto
+// the zeroed counter).  Only the narrow build (ESPM_KP == 8) instantiates the kernels; the wide builds export the entry points as stubs.
 #include <type_traits>
 
 #include "mu_common.hpp"
@@ -34,6 +32,8 @@
 namespace espm {
 
 #if ESPM_KP == 8
+#include "mu_image_pass.hpp"
+
 namespace attribk {
 
 constexpr int BT = ESPM_ATTRIB_BLOCK;
@@ -43,28 +43,9 @@ constexpr uint32_t HEAVY = ESPM_ATTRIB_HEAVY;
 constexpr int TP = BT + 1;   // lane stride of the transposing tile
 static_assert(BT == 256, "four waves of 64 lanes");
 
-// component i of the k-vector of index q: ptr[i * cs + q * qs] (h: cs = p, qs = 1; d: cs = 1, qs = k)
-struct Vec {
-  const double* ptr;
-  int64_t cs, qs;
-};
-
-template <int KP>
-constexpr int stage_rows() { return KP <= 8 ? 256 : 2048 / KP; }   // walk indices per round: at most 16 KB of LDS
 static_assert(WALK % 256 == 0 && PC % 256 == 0, "whole rounds of the staged vectors");
 
-// the vectors of the walk indices w0 .. w0 + wn - 1, padded to KP columns, into LDS
-template <int KP>
-__device__ __forceinline__ void stage(double* ds, const Vec& v, int64_t w0, int wn, int k) {
-  for (int i = threadIdx.x; i < wn * KP; i += BT) {
-    const int w = i / KP, j = i % KP;
-    ds[i] = j < k ? v.ptr[(int64_t)j * v.cs + (w0 + w) * v.qs] : 0.0;
-  }
-}
-
-// walk indices per tile of the transposing path (u8: 16 KB, the others 33 KB)
-template <typename XT>
-constexpr int tile_rows() { return sizeof(XT) <= 2 ? 64 : sizeof(XT) == 4 ? 32 : 16; }
+struct Vec : espm::Vec {};   // the kernels' parameter type (its name is part of their symbols): the header's
 
 // ---- expected attribution ---------------------------------------------------------------------------------------------------------
 // PIXEL_SIDE: lane = pixel, grid (lane blocks), the whole walk; out = num_h (cs apart), scaled by the lane's vector; counts written.
@@ -106,7 +87,7 @@ __global__ __launch_bounds__(BT) void expected_kernel(const XT* __restrict__ x, 
   for (int64_t c0 = w_begin; c0 < w_end; c0 += CH) {
     const int cn = (int)(w_end - c0 < CH ? w_end - c0 : CH);
     __syncthreads();
-    stage<KP>(ds, wv, c0, cn, k);
+    stage<KP, BT>(ds, wv, c0, cn, k);
     __syncthreads();
     if constexpr (!TILE) {
       const XT* xp = x + c0 * ld + l;
@@ -124,15 +105,7 @@ __global__ __launch_bounds__(BT) void expected_kernel(const XT* __restrict__ x, 
       for (int t0 = 0; t0 < cn; t0 += TS) {
         const int tn = cn - t0 < TS ? cn - t0 : TS;
         __syncthreads();   // (the tile's readers of the round before)
-        // element el of the tile: lane el / TS, walk index el % TS - consecutive threads read consecutive entries of one row of x
-#pragma unroll 8
-        for (int i = 0; i < TS; ++i) {
-          const int el = i * BT + threadIdx.x;
-          const int li = el / TS, w = el % TS;
-          XT v = XT(0);
-          if (l0 + li < lanes && w < tn) v = x[(l0 + li) * ld + (c0 + t0 + w)];
-          tile[w * TP + li] = v;
-        }
+        fill_tile<XT, BT>(tile, x, ld, l0, lanes, c0 + t0, tn);
         __syncthreads();
         for (int c = 0; c < tn; ++c) add(valid ? tile[c * TP + threadIdx.x] : XT(0), ds + (t0 + c) * KP);
       }
@@ -180,38 +153,10 @@ int launch_expected(const void* x, int layout, int64_t ld, int n, int p, const d
   return check_hip(hipGetLastError(), "expected attribution launch");
 }
 
-template <int KP>
-int launch_expected_x(const void* x, int x_dtype, int layout, int64_t ld, int n, int p, const double* d, const double* h, int k, double log_shift,
-                      double* num_h, void* counts, double* part, hipStream_t s) {
-  switch (x_dtype) {
-    case ESPM_DIAG_X_U8: return launch_expected<KP, uint8_t>(x, layout, ld, n, p, d, h, k, log_shift, num_h, counts, part, s);
-    case ESPM_DIAG_X_U16: return launch_expected<KP, uint16_t>(x, layout, ld, n, p, d, h, k, log_shift, num_h, counts, part, s);
-    case ESPM_DIAG_X_F32: return launch_expected<KP, float>(x, layout, ld, n, p, d, h, k, log_shift, num_h, counts, part, s);
-    default: return launch_expected<KP, double>(x, layout, ld, n, p, d, h, k, log_shift, num_h, counts, part, s);
-  }
-}
-
 // ---- random attribution -----------------------------------------------------------------------------------------------------------
 struct Rule {
   uint32_t key0, key1;
 };
-
-// Philox4x32-10 (Salmon, Moraes, Dror, Shaw 2011): counter (c0, c1, c2, 0)
-__device__ __forceinline__ void philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t k0, uint32_t k1, uint32_t (&w)[4]) {
-  uint32_t c3 = 0;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  w[0] = c0, w[1] = c1, w[2] = c2, w[3] = c3;
-}
 
 // the cumulative rates of one entry as their running maximum m_i = max_{j <= i} s_j, and a = s_{k - 1}: products and sums rounded one
 // by one, components in ascending order (a contraction to a fused multiply-add would change the bits the rule is defined by)
@@ -238,7 +183,7 @@ __device__ __forceinline__ void block_of_four(uint32_t x, uint64_t e, uint32_t b
                                               uint32_t (&cum)[KP]) {
 #pragma clang fp contract(off)
   uint32_t w[4];
-  philox((uint32_t)e, (uint32_t)(e >> 32), 0x80000000u | b, r.key0, r.key1, w);
+  philox4x32_10((uint32_t)e, (uint32_t)(e >> 32), 0x80000000u | b, 0u, r.key0, r.key1, w);
   const uint32_t left = x - 4u * b;   // draws from this block on: at least 1
 #pragma unroll
   for (uint32_t d = 0; d < 4; ++d) {
@@ -250,12 +195,6 @@ __device__ __forceinline__ void block_of_four(uint32_t x, uint64_t e, uint32_t b
         if (i < k - 1) cum[i] += (uint32_t)(t < m[i]);
     }
   }
-}
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v += (uint32_t)__shfl_xor((int)v, s, 64);
-  return v;
 }
 
 // the k parts of one entry per lane.  EVERY lane of the wave calls this together (a lane without an entry passes x = 0): the heavy
@@ -273,7 +212,7 @@ __device__ __forceinline__ bool assign_entry(uint32_t x, uint64_t e, const Rule&
   const bool heavy = sizeof(XT) > 1 && x >= HEAVY && ok;
   if (x && ok && !heavy)
     for (uint32_t b = 0; 4u * b < x; ++b) block_of_four<KP>(x, e, b, r, m, a, k, cum);
-  if constexpr (sizeof(XT) > 1) {
+  if constexpr (sizeof(XT) > 1) {   // (for_each_heavy's loop, written out: the file comment)
     const int lane = threadIdx.x & 63;
     unsigned long long todo = __ballot(heavy);
     while (todo) {   // (wave-uniform)
@@ -316,7 +255,7 @@ __global__ __launch_bounds__(BT) void assign_kernel(const XT* __restrict__ x, in
                                                     unsigned long long* __restrict__ counts) {
   constexpr int CH = stage_rows<KP>();
   __shared__ double ds[CH * KP];
-  __shared__ uint32_t part_inv[BT / 64];
+  __shared__ uint32_t part_inv[1][BT / 64];
   const int64_t l = (int64_t)(pm ? blockIdx.y : blockIdx.x) * BT + threadIdx.x;
   const bool valid = l < lanes;
   const int64_t w_begin = (int64_t)(pm ? blockIdx.x : blockIdx.y) * WALK;
@@ -332,7 +271,7 @@ __global__ __launch_bounds__(BT) void assign_kernel(const XT* __restrict__ x, in
   for (int64_t c0 = w_begin; c0 < w_end; c0 += CH) {
     const int cn = (int)(w_end - c0 < CH ? w_end - c0 : CH);
     __syncthreads();
-    stage<KP>(ds, wv, c0, cn, k);
+    stage<KP, BT>(ds, wv, c0, cn, k);
     __syncthreads();
     const XT* xp = x + c0 * ld + l;
     XT* op = parts + c0 * out_ld + l;
@@ -355,15 +294,7 @@ __global__ __launch_bounds__(BT) void assign_kernel(const XT* __restrict__ x, in
       }
     }
   }
-  // the invalid entries: the wave's sum, then the workgroup's, then one integer atomic
-  n_inv = wave_sum_u32(n_inv);
-  if ((threadIdx.x & 63) == 0) part_inv[threadIdx.x >> 6] = n_inv;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long s = 0;
-    for (int w = 0; w < BT / 64; ++w) s += part_inv[w];
-    if (s) atomicAdd(counts, s);
-  }
+  block_count_add<1>(part_inv, {n_inv}, counts);
 }
 
 template <int KP, typename XT>
@@ -377,14 +308,6 @@ int launch_assign(const void* x, int layout, int64_t ld, int n, int p, int64_t p
   hipLaunchKernelGGL((assign_kernel<KP, XT>), grid, block, 0, s, static_cast<const XT*>(x), ld, lanes, walks, (int)pm, p_total, j0, rule,
                      pm ? dv : hv, pm ? hv : dv, k, static_cast<XT*>(parts), part_stride, out_ld, reinterpret_cast<unsigned long long*>(counts));
   return check_hip(hipGetLastError(), "count assignment launch");
-}
-
-template <int KP>
-int launch_assign_x(const void* x, int x_dtype, int layout, int64_t ld, int n, int p, int64_t p_total, int64_t j0, const Rule& rule, const double* d,
-                    const double* h, int k, void* parts, int64_t part_stride, int64_t out_ld, int64_t* counts, hipStream_t s) {
-  if (x_dtype == ESPM_DIAG_X_U8)
-    return launch_assign<KP, uint8_t>(x, layout, ld, n, p, p_total, j0, rule, d, h, k, parts, part_stride, out_ld, counts, s);
-  return launch_assign<KP, uint16_t>(x, layout, ld, n, p, p_total, j0, rule, d, h, k, parts, part_stride, out_ld, counts, s);
 }
 
 }  // namespace attribk
@@ -401,11 +324,7 @@ static int attrib_check(const char* who, const void* x, int x_dtype, int max_dty
   ESPM_REQUIRE(x && d && h, "%s: bad arguments (x %p, d %p, h %p)", who, x, (const void*)d, (const void*)h);
   ESPM_REQUIRE(n >= 1 && p >= 1, "%s: bad arguments (n=%d, p=%d)", who, n, p);
   ESPM_REQUIRE(k >= 1 && k <= ESPM_ATTRIB_MAX_K, "%s: k=%d (1..%d components)", who, k, ESPM_ATTRIB_MAX_K);
-  ESPM_REQUIRE(x_layout == ESPM_LAYOUT_CM || x_layout == ESPM_LAYOUT_PM, "%s: x_layout %d", who, x_layout);
-  ESPM_REQUIRE(x_dtype >= ESPM_DIAG_X_U8 && x_dtype <= max_dtype, "%s: x_dtype %d%s", who, x_dtype,
-               max_dtype == ESPM_DIAG_X_U16 ? " (counts: u8 or u16)" : "");
-  const int row = x_layout == ESPM_LAYOUT_CM ? p : n;
-  ESPM_REQUIRE(ld >= row, "%s: ld=%lld below the row length %d", who, (long long)ld, row);
+  if (int rc = check_image(who, x, x_dtype, max_dtype, x_layout, ld, n, p)) return rc;
   ESPM_REQUIRE((n + ESPM_ATTRIB_BLOCK - 1) / ESPM_ATTRIB_BLOCK <= 65535, "%s: n=%d (at most %d channels)", who, n, 65535 * ESPM_ATTRIB_BLOCK);
   return ESPM_OK;
 }
@@ -437,13 +356,12 @@ extern "C" int espm_attribute_expected(const void* x, int x_dtype, int x_layout,
                need);
   hipStream_t s = static_cast<hipStream_t>(stream);
   double* part = static_cast<double*>(scratch);
-  int rc = ESPM_OK;
-#define ESPM_ATTRIB_CASE(KP) rc = attribk::launch_expected_x<KP>(x, x_dtype, x_layout, ld, n, p, d, h, k, log_shift, num_h, counts, part, s)
-  if (k <= 4) ESPM_ATTRIB_CASE(4);
-  else if (k <= 8) ESPM_ATTRIB_CASE(8);
-  else if (k <= 16) ESPM_ATTRIB_CASE(16);
-  else ESPM_ATTRIB_CASE(32);
-#undef ESPM_ATTRIB_CASE
+  const int rc = dispatch_kp(k, [&](auto kp) {
+    return dispatch_xt<ESPM_DIAG_X_F64>(x_dtype, [&](auto xt) {
+      return attribk::launch_expected<decltype(kp)::value, typename decltype(xt)::type>(x, x_layout, ld, n, p, d, h, k, log_shift, num_h, counts,
+                                                                                         part, s);
+    });
+  });
   if (rc) return rc;
   const int n_chunks = (int)(((int64_t)p + ESPM_ATTRIB_PCHUNK - 1) / ESPM_ATTRIB_PCHUNK);
   const unsigned blocks = (unsigned)(((int64_t)k * n + 255) / 256);
@@ -464,19 +382,16 @@ extern "C" int espm_assign_counts(const void* x, int x_dtype, int x_layout, int6
   ESPM_REQUIRE(out_ld >= row, "assign counts: out_ld=%lld below the row length %d", (long long)out_ld, row);
   ESPM_REQUIRE(out_ld <= (INT64_MAX - row) / rows && part_stride >= (int64_t)(rows - 1) * out_ld + row,
                "assign counts: part_stride=%lld below one image (%d rows, out_ld=%lld apart)", (long long)part_stride, rows, (long long)out_ld);
-  ESPM_REQUIRE(j0 >= 0 && p_total >= p && j0 <= p_total - p, "assign counts: pixels j0=%lld .. j0 + p=%lld of p_total=%lld", (long long)j0,
-               (long long)j0 + p, (long long)p_total);
-  ESPM_REQUIRE(p_total <= INT64_MAX / n, "assign counts: n=%d x p_total=%lld elements (a 64-bit index)", n, (long long)p_total);
+  if (int rc = check_slab("assign counts", n, p, p_total, j0)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   attribk::Rule rule;
   rule.key0 = (uint32_t)seed, rule.key1 = (uint32_t)(seed >> 32);
   if (int rc = check_hip(hipMemsetAsync(counts, 0, sizeof(int64_t), s), "assign counts: zeroing the counter")) return rc;
-#define ESPM_ATTRIB_CASE(KP) \
-  return attribk::launch_assign_x<KP>(x, x_dtype, x_layout, ld, n, p, p_total, j0, rule, d, h, k, parts, part_stride, out_ld, counts, s)
-  if (k <= 4) ESPM_ATTRIB_CASE(4);
-  if (k <= 8) ESPM_ATTRIB_CASE(8);
-  if (k <= 16) ESPM_ATTRIB_CASE(16);
-  ESPM_ATTRIB_CASE(32);
-#undef ESPM_ATTRIB_CASE
+  return dispatch_kp(k, [&](auto kp) {
+    return dispatch_xt<ESPM_DIAG_X_U16>(x_dtype, [&](auto xt) {
+      return attribk::launch_assign<decltype(kp)::value, typename decltype(xt)::type>(x, x_layout, ld, n, p, p_total, j0, rule, d, h, k, parts,
+                                                                                       part_stride, out_ld, counts, s);
+    });
+  });
 #endif
 }

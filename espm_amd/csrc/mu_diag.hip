@@ -4,29 +4,28 @@
 //   one pixel per thread, ESPM_DIAG_BLOCK pixels per workgroup; D staged through LDS in chunks of ESPM_DIAG_CHUNK channels
 //   per channel: y = max(D h, log_shift) (k FMAs), one division, one log where x > 0, k (k + 1) / 2 FMAs into the lower triangle of
 //                F = D^T diag(1 / y) D, kept in registers
-//   channel-major X is read coalesced across the workgroup's pixels; pixel-major X ((p, n), hyperspy's layout) goes through an LDS
-//                tile of (channel slice, pixels) that is filled with loads running along the channels
+//   channel-major X is read coalesced across the workgroup's pixels; pixel-major X ((p, n), hyperspy's layout) goes through
+//                mu_image_pass.hpp's transposing tile.  D is staged UNPADDED and every sum runs over the exact K (no KP here)
 //   after the channels: root-free Cholesky F = L diag(d) L^T, the k forward solves for diag(F^-1), the constrained form under the
 //                simplex - all on the template K, unrolled, in registers
 //
 // No float atomics (a pixel belongs to one thread); the only atomic is the integer count of singular pixels.  Only the narrow
 // build (ESPM_KP == 8) instantiates the kernels; the wide builds export the entry point as a stub.
 #include <cfloat>
+#include <type_traits>
 
 #include "mu_common.hpp"
 
 namespace espm {
 
 #if ESPM_KP == 8
+#include "mu_image_pass.hpp"
+
 namespace diagk {
 
 constexpr int B = ESPM_DIAG_BLOCK;
 constexpr int CH = ESPM_DIAG_CHUNK;
 constexpr int TP = B + 1;   // pixel stride of the pixel-major tile
-
-// channels per tile of the pixel-major path: a row segment of 64-128 bytes per pixel, a tile of 16-33 KB
-template <typename XT>
-struct Slice { static constexpr int N = sizeof(XT) == 1 ? 64 : sizeof(XT) == 2 ? 64 : sizeof(XT) == 4 ? 32 : 16; };
 
 __device__ __forceinline__ constexpr int tri(int i, int j) { return i * (i + 1) / 2 + j; }   // (i, j), j <= i, of the lower triangle
 
@@ -88,20 +87,12 @@ __global__ __launch_bounds__(B) void pixel_kernel(const XT* __restrict__ x, int6
         for (int c = 0; c < cn; ++c) a.add((double)xp[(size_t)c * ld], ds + c * K);
       }
     } else {
-      constexpr int TS = Slice<XT>::N;
+      constexpr int TS = tile_rows<XT>();
       __shared__ XT tile[TS * TP];
       for (int t0 = 0; t0 < cn; t0 += TS) {
         const int tn = min(TS, cn - t0);
         __syncthreads();   // (the tile's readers of the round before)
-        // element e of the tile: pixel e / TS, channel e % TS - consecutive lanes read consecutive channels of one pixel's row
-#pragma unroll 8
-        for (int i = 0; i < TS; ++i) {
-          const int e = i * B + threadIdx.x;
-          const int px = e / TS, c = e % TS;
-          XT v = 0;
-          if (q0 + px < p && c < tn) v = x[(size_t)(q0 + px) * ld + (c0 + t0 + c)];
-          tile[c * TP + px] = v;
-        }
+        fill_tile<XT, B>(tile, x, ld, q0, p, c0 + t0, tn);
         __syncthreads();
         if (valid)
           for (int c = 0; c < tn; ++c) a.add((double)tile[c * TP + threadIdx.x], ds + (t0 + c) * K);
@@ -192,18 +183,6 @@ int launch(const void* x, int x_layout, int64_t ld, int n, int p, const double* 
   return check_hip(hipGetLastError(), "pixel diagnostics launch");
 }
 
-template <int K>
-int launch_x(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, const double* d, const double* h, double log_shift,
-             int simplex, double* dev, double* h_std, int32_t* n_singular, hipStream_t s) {
-  switch (x_dtype) {
-    case ESPM_DIAG_X_U8: return launch<K, uint8_t>(x, x_layout, ld, n, p, d, h, log_shift, simplex, dev, h_std, n_singular, s);
-    case ESPM_DIAG_X_U16: return launch<K, uint16_t>(x, x_layout, ld, n, p, d, h, log_shift, simplex, dev, h_std, n_singular, s);
-    case ESPM_DIAG_X_F32: return launch<K, float>(x, x_layout, ld, n, p, d, h, log_shift, simplex, dev, h_std, n_singular, s);
-    case ESPM_DIAG_X_F64: return launch<K, double>(x, x_layout, ld, n, p, d, h, log_shift, simplex, dev, h_std, n_singular, s);
-    default: return set_error(ESPM_EINVAL, "pixel diagnostics: x_dtype %d", x_dtype);
-  }
-}
-
 }  // namespace diagk
 #endif
 
@@ -219,20 +198,16 @@ extern "C" int espm_pixel_diagnostics(const void* x, int x_dtype, int x_layout, 
 #else
   if (k < 1 || k > ESPM_DIAG_MAX_K) return set_error(ESPM_EUNSUPPORTED, "pixel diagnostics: k=%d (1..%d components)", k, ESPM_DIAG_MAX_K);
   ESPM_REQUIRE(x && d && h && dev && h_std && n >= 1 && p >= 1, "pixel diagnostics: bad arguments");
-  ESPM_REQUIRE(x_layout == ESPM_LAYOUT_CM || x_layout == ESPM_LAYOUT_PM, "pixel diagnostics: x_layout %d", x_layout);
-  ESPM_REQUIRE(ld >= (x_layout == ESPM_LAYOUT_CM ? p : n), "pixel diagnostics: ld=%lld below the row length %d", (long long)ld,
-               x_layout == ESPM_LAYOUT_CM ? p : n);
+  if (int rc = check_image("pixel diagnostics", x, x_dtype, ESPM_DIAG_X_F64, x_layout, ld, n, p)) return rc;
   ESPM_REQUIRE(log_shift > 0, "pixel diagnostics: log_shift must be positive");
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (n_singular)
     if (int rc = check_hip(hipMemsetAsync(n_singular, 0, sizeof(int32_t), s), "pixel diagnostics counter")) return rc;
-  switch (k) {
-#define ESPM_DIAG_CASE(KK) \
-  case KK: return diagk::launch_x<KK>(x, x_dtype, x_layout, ld, n, p, d, h, log_shift, simplex, dev, h_std, n_singular, s);
-    ESPM_DIAG_CASE(1) ESPM_DIAG_CASE(2) ESPM_DIAG_CASE(3) ESPM_DIAG_CASE(4)
-    ESPM_DIAG_CASE(5) ESPM_DIAG_CASE(6) ESPM_DIAG_CASE(7) ESPM_DIAG_CASE(8)
-#undef ESPM_DIAG_CASE
-  }
-  return ESPM_OK;
+  return dispatch_k_exact(k, [&](auto kk) {
+    return dispatch_xt<ESPM_DIAG_X_F64>(x_dtype, [&](auto xt) {
+      return diagk::launch<decltype(kk)::value, typename decltype(xt)::type>(x, x_layout, ld, n, p, d, h, log_shift, simplex, dev, h_std,
+                                                                               n_singular, s);
+    });
+  });
 #endif
 }

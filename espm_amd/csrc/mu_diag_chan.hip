@@ -15,11 +15,15 @@
 //                chunks in ascending order.  No float atomics: two calls give the same bits.
 //
 // Only the narrow build (ESPM_KP == 8) instantiates the kernels; the wide builds export the entry points as stubs.
+#include <type_traits>
+
 #include "mu_common.hpp"
 
 namespace espm {
 
 #if ESPM_KP == 8
+#include "mu_image_pass.hpp"   // (the host side only: this tile has a geometry of its own)
+
 namespace cdiagk {
 
 constexpr int CB = ESPM_CDIAG_BLOCK;
@@ -162,18 +166,6 @@ int launch(const void* x, int x_layout, int64_t ld, int n, int p, const double* 
   return check_hip(hipGetLastError(), "channel diagnostics launch");
 }
 
-template <int K>
-int launch_x(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, const double* d, const double* h, double log_shift,
-             double* part, hipStream_t s) {
-  switch (x_dtype) {
-    case ESPM_DIAG_X_U8: return launch<K, uint8_t>(x, x_layout, ld, n, p, d, h, log_shift, part, s);
-    case ESPM_DIAG_X_U16: return launch<K, uint16_t>(x, x_layout, ld, n, p, d, h, log_shift, part, s);
-    case ESPM_DIAG_X_F32: return launch<K, float>(x, x_layout, ld, n, p, d, h, log_shift, part, s);
-    case ESPM_DIAG_X_F64: return launch<K, double>(x, x_layout, ld, n, p, d, h, log_shift, part, s);
-    default: return set_error(ESPM_EINVAL, "channel diagnostics: x_dtype %d", x_dtype);
-  }
-}
-
 }  // namespace cdiagk
 #endif
 
@@ -200,10 +192,7 @@ extern "C" int espm_channel_diagnostics(const void* x, int x_dtype, int x_layout
 #else
   if (k < 1 || k > ESPM_DIAG_MAX_K) return set_error(ESPM_EUNSUPPORTED, "channel diagnostics: k=%d (1..%d components)", k, ESPM_DIAG_MAX_K);
   ESPM_REQUIRE(x && d && h && dev && xsum && ysum && m_tri && scratch && n >= 1 && p >= 1, "channel diagnostics: bad arguments");
-  ESPM_REQUIRE(x_layout == ESPM_LAYOUT_CM || x_layout == ESPM_LAYOUT_PM, "channel diagnostics: x_layout %d", x_layout);
-  ESPM_REQUIRE(ld >= (x_layout == ESPM_LAYOUT_CM ? p : n), "channel diagnostics: ld=%lld below the row length %d", (long long)ld,
-               x_layout == ESPM_LAYOUT_CM ? p : n);
-  ESPM_REQUIRE(x_dtype >= ESPM_DIAG_X_U8 && x_dtype <= ESPM_DIAG_X_F64, "channel diagnostics: x_dtype %d", x_dtype);
+  if (int rc = check_image("channel diagnostics", x, x_dtype, ESPM_DIAG_X_F64, x_layout, ld, n, p)) return rc;
   ESPM_REQUIRE(log_shift > 0, "channel diagnostics: log_shift must be positive");
   ESPM_REQUIRE((n + ESPM_CDIAG_BLOCK - 1) / ESPM_CDIAG_BLOCK <= 65535, "channel diagnostics: n=%d (at most %d channels)", n,
                65535 * ESPM_CDIAG_BLOCK);
@@ -212,14 +201,11 @@ extern "C" int espm_channel_diagnostics(const void* x, int x_dtype, int x_layout
                scratch_bytes, need);
   hipStream_t s = static_cast<hipStream_t>(stream);
   double* part = static_cast<double*>(scratch);
-  int rc = ESPM_OK;
-  switch (k) {
-#define ESPM_CDIAG_CASE(KK) \
-  case KK: rc = cdiagk::launch_x<KK>(x, x_dtype, x_layout, ld, n, p, d, h, log_shift, part, s); break;
-    ESPM_CDIAG_CASE(1) ESPM_CDIAG_CASE(2) ESPM_CDIAG_CASE(3) ESPM_CDIAG_CASE(4)
-    ESPM_CDIAG_CASE(5) ESPM_CDIAG_CASE(6) ESPM_CDIAG_CASE(7) ESPM_CDIAG_CASE(8)
-#undef ESPM_CDIAG_CASE
-  }
+  const int rc = dispatch_k_exact(k, [&](auto kk) {
+    return dispatch_xt<ESPM_DIAG_X_F64>(x_dtype, [&](auto xt) {
+      return cdiagk::launch<decltype(kk)::value, typename decltype(xt)::type>(x, x_layout, ld, n, p, d, h, log_shift, part, s);
+    });
+  });
   if (rc) return rc;
   const int na = cdiagk::n_acc(k);
   const int n_chunks = (int)(((int64_t)p + ESPM_CDIAG_PCHUNK - 1) / ESPM_CDIAG_PCHUNK);

@@ -8,30 +8,28 @@
 // a Poisson(1) draw.  x = sum_{i < m} N(word i mod 4 of block 4 + i div 4) + #{i in 1 .. N(word 0 of block 0) : word i mod 4 of block
 // i div 4 < thr}: m unit pieces and a Poisson(1) thinned to the fractional part.
 //
-//   sample_kernel:   mu_split.hip's deviance_kernel turned round - a pixel per thread, d staged through LDS in channel chunks (its k columns
-//                padded with zeros to KP = 4, 8, 16 or 32: a padded product is an exact +0 and y + 0 is y), pixel-major output through an LDS
-//                tile so that consecutive lanes store consecutive channels.
-//   heavy entries (m >= ESPM_SAMPLE_HEAVY): the wave shares the unit pieces, as thin_entry does - a ballot finds the lanes that hold one;
-//                for each in turn m and e are broadcast, lane l takes the unit-piece blocks 4 + l, 4 + l + 64, ..., and the 64 counts are
-//                added across the wave (integers: any order gives the same sum).
+//   sample_kernel:   a pixel per thread over mu_image_pass.hpp's walk (d staged padded to KP: a padded product is an exact +0 and y + 0
+//                is y), pixel-major output through the tile, written where the other passes read it.
+//   heavy entries (m >= ESPM_SAMPLE_HEAVY): the wave shares the unit pieces (for_each_heavy), lane l the blocks 4 + l, 4 + l + 64, ...
 //   deviance_kernel: the same walk for replicate blockIdx.y (and every gridDim.y-th after it); each entry's x is drawn and its term
 //                x ln(x / Y) - x + Y added in channel order in the pixel's own thread: two calls give the same bits.
 //
-// The sample values use no atomics.  The two counters of espm_poisson_sample are sums of integers (per thread, then per wave, then one
-// 64-bit integer atomic per workgroup onto the zeroed pair): exact, and the same from call to call.  Only the narrow build
-// (ESPM_KP == 8) instantiates the kernels; the wide builds export the entry points as stubs.
+// The sample values use no atomics.  The two counters of espm_poisson_sample are sums of integers (block_count_add, onto the zeroed
+// pair).  Only the narrow build (ESPM_KP == 8) instantiates the kernels; the wide builds export the entry points as stubs.
+#include <type_traits>
+
 #include "mu_common.hpp"
 
 namespace espm {
 
 #if ESPM_KP == 8
+#include "mu_image_pass.hpp"
+
 namespace samplek {
 
 constexpr int BT = ESPM_SAMPLE_BLOCK;
 constexpr uint32_t HEAVY = ESPM_SAMPLE_HEAVY;
 constexpr double MAX_RATE = (double)ESPM_SAMPLE_MAX_RATE;
-constexpr int TP = BT + 1;                 // pixel stride of the pixel-major tile
-constexpr int TS = 64;                     // channels per tile of the pixel-major path (u8: 16 KB, u16: 33 KB)
 static_assert(BT == 256, "four waves of 64 lanes");
 
 // T_i = floor(2^32 sum_{j <= i} e^-1 / j!), i = 0 .. 11 (include/espm_mu.h)
@@ -42,24 +40,8 @@ struct Rule {
   uint32_t key0, key1, rep1;   // seed low, seed high, replicate + 1
 };
 
-// Philox4x32-10 (Salmon, Moraes, Dror, Shaw 2011): counter (c0, c1, c2, c3)
-__device__ __forceinline__ void philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&w)[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  w[0] = c0, w[1] = c1, w[2] = c2, w[3] = c3;
-}
-
 __device__ __forceinline__ void block(uint64_t e, uint32_t b, const Rule& r, uint32_t (&w)[4]) {
-  philox((uint32_t)e, (uint32_t)(e >> 32), b, r.rep1, r.key0, r.key1, w);
+  philox4x32_10((uint32_t)e, (uint32_t)(e >> 32), b, r.rep1, r.key0, r.key1, w);
 }
 
 // N(w): a word as a Poisson(1) draw.  A word reaches T6 once in 12000: the last six comparisons stay behind a branch.
@@ -96,12 +78,6 @@ __device__ __forceinline__ uint32_t remainder(uint32_t thr, uint64_t e, const Ru
   return s;
 }
 
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v += (uint32_t)__shfl_xor((int)v, s, 64);
-  return v;
-}
-
 // one entry per lane, classified: m unit pieces and the threshold of the fractional part (both 0 where nothing is drawn)
 struct Entry {
   uint32_t m, thr;
@@ -125,18 +101,10 @@ __device__ __forceinline__ uint32_t draw(uint32_t m, uint32_t thr, uint64_t e, c
   if (thr) x = remainder(thr, e, r);   // (thr == 0: no count of the fractional part is kept, whatever the words)
   if (m && !heavy)
     for (uint32_t b = 0; 4u * b < m; ++b) x += unit_block(m, e, b, r);
-  const int lane = threadIdx.x & 63;
-  unsigned long long todo = __ballot(heavy);
-  while (todo) {   // (wave-uniform)
-    const int src = __ffsll((long long)todo) - 1;
-    todo &= todo - 1;
-    const uint32_t mh = (uint32_t)__shfl((int)m, src, 64);
-    const uint64_t eh = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(e >> 32), src, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)e, src, 64);
-    uint32_t mine = 0;
-    for (uint32_t b = (uint32_t)lane; 4u * b < mh; b += 64u) mine += unit_block(mh, eh, b, r);
-    const uint32_t total = wave_sum_u32(mine);
-    if (lane == src) x += total;
-  }
+  for_each_heavy(heavy, m, e, [&](int src, uint32_t mh, uint64_t eh) {
+    const uint32_t total = wave_blocks_sum(mh, [&](uint32_t b) { return unit_block(mh, eh, b, r); });
+    if ((int)(threadIdx.x & 63) == src) x += total;
+  });
   return x;
 }
 
@@ -154,19 +122,10 @@ __device__ __forceinline__ double rate(const double (&h)[KP], const double* __re
   return y;
 }
 
-// d rows c0 .. c0 + cn - 1, padded to KP columns, into LDS
-template <int KP>
-__device__ __forceinline__ void stage_d(double* ds, const double* __restrict__ d, int c0, int cn, int k) {
-  for (int i = threadIdx.x; i < cn * KP; i += BT) {
-    const int c = i / KP, j = i % KP;
-    ds[i] = j < k ? d[(size_t)(c0 + c) * k + j] : 0.0;
-  }
-}
-
 template <int KP, typename XT, bool PM>
 __global__ __launch_bounds__(BT) void sample_kernel(const double* __restrict__ d, const double* __restrict__ h, int k, int n, int p, int64_t p_total,
                                                     int64_t j0, Rule rule, XT* __restrict__ x, int64_t ld, unsigned long long* __restrict__ counts) {
-  constexpr int CH = KP <= 8 ? 256 : 2048 / KP;   // channels of d per round: at most 16 KB of LDS
+  constexpr int CH = stage_rows<KP>();   // channels of d per round
   constexpr uint32_t XMAX = sizeof(XT) == 1 ? 255u : 65535u;
   __shared__ double ds[CH * KP];
   __shared__ uint32_t part[2][BT / 64];
@@ -177,6 +136,7 @@ __global__ __launch_bounds__(BT) void sample_kernel(const double* __restrict__ d
 #pragma unroll
   for (int j = 0; j < KP; ++j) hq[j] = valid && j < k ? h[(size_t)j * p + q] : 0.0;
   const uint64_t ej = (uint64_t)(j0 + q);
+  const Vec dv = {d, 1, (int64_t)(uint32_t)k};   // (k >= 1: the entry point checked it)
   uint32_t n_sat = 0, n_inv = 0;
 
   // one entry: its value as stored (every lane of the wave comes here together)
@@ -191,7 +151,7 @@ __global__ __launch_bounds__(BT) void sample_kernel(const double* __restrict__ d
   for (int c0 = 0; c0 < n; c0 += CH) {
     const int cn = min(CH, n - c0);
     __syncthreads();
-    stage_d<KP>(ds, d, c0, cn, k);
+    stage<KP, BT>(ds, dv, c0, cn, k);
     __syncthreads();
     if constexpr (!PM) {
       XT* xp = x + (size_t)c0 * ld + q;
@@ -200,37 +160,29 @@ __global__ __launch_bounds__(BT) void sample_kernel(const double* __restrict__ d
         if (valid) xp[(size_t)c * ld] = v;
       }
     } else {
-      __shared__ XT tile[TS * TP];
+      constexpr int TS = tile_rows<XT>();
+      __shared__ XT tile[TS * (BT + 1)];
       for (int t0 = 0; t0 < cn; t0 += TS) {
         const int tn = min(TS, cn - t0);
         __syncthreads();   // (the tile's readers of the round before)
-        for (int c = 0; c < tn; ++c) tile[c * TP + threadIdx.x] = entry(c0 + t0 + c, ds + (t0 + c) * KP);
+        for (int c = 0; c < tn; ++c) tile[c * (BT + 1) + threadIdx.x] = entry(c0 + t0 + c, ds + (t0 + c) * KP);
         __syncthreads();
-        // element i of the tile: pixel i / TS, channel i % TS - consecutive lanes store consecutive channels of one pixel's row
 #pragma unroll 8
-        for (int i = 0; i < TS; ++i) {
-          const int el = i * BT + threadIdx.x;
-          const int px = el / TS, c = el % TS;
-          if (q0 + px < p && c < tn) x[(size_t)(q0 + px) * ld + (c0 + t0 + c)] = tile[c * TP + px];
+        for (int i = 0; i < TS; ++i) {   // (fill_tile's pass, storing)
+          int px, c;
+          const int at = tile_slot<XT, BT>(i, px, c);
+          if (q0 + px < p && c < tn) x[(size_t)(q0 + px) * ld + (c0 + t0 + c)] = tile[at];
         }
       }
     }
   }
-  // the two counters: the wave's sums, then the workgroup's, then one integer atomic each
-  n_sat = wave_sum_u32(n_sat), n_inv = wave_sum_u32(n_inv);
-  if ((threadIdx.x & 63) == 0) part[0][threadIdx.x >> 6] = n_sat, part[1][threadIdx.x >> 6] = n_inv;
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    unsigned long long s = 0;
-    for (int w = 0; w < BT / 64; ++w) s += part[threadIdx.x][w];
-    if (s) atomicAdd(counts + threadIdx.x, s);
-  }
+  block_count_add<2>(part, {n_sat, n_inv}, counts);
 }
 
 template <int KP>
 __global__ __launch_bounds__(BT) void deviance_kernel(const double* __restrict__ d, const double* __restrict__ h, int k, int n, int p, int64_t p_total,
                                                       int64_t j0, Rule rule, int n_rep, double log_shift, double* __restrict__ dev) {
-  constexpr int CH = KP <= 8 ? 256 : 2048 / KP;
+  constexpr int CH = stage_rows<KP>();
   __shared__ double ds[CH * KP];
   const int64_t q = (int64_t)blockIdx.x * BT + threadIdx.x;
   const bool valid = q < p;
@@ -238,6 +190,7 @@ __global__ __launch_bounds__(BT) void deviance_kernel(const double* __restrict__
 #pragma unroll
   for (int j = 0; j < KP; ++j) hq[j] = valid && j < k ? h[(size_t)j * p + q] : 0.0;
   const uint64_t ej = (uint64_t)(j0 + q);
+  const Vec dv = {d, 1, (int64_t)(uint32_t)k};   // (k >= 1: the entry point checked it)
   const uint32_t rep1 = rule.rep1;   // (replicate0 + 1)
 
   for (int rep = blockIdx.y; rep < n_rep; rep += gridDim.y) {   // (uniform over the workgroup)
@@ -246,7 +199,7 @@ __global__ __launch_bounds__(BT) void deviance_kernel(const double* __restrict__
     for (int c0 = 0; c0 < n; c0 += CH) {
       const int cn = min(CH, n - c0);
       __syncthreads();
-      stage_d<KP>(ds, d, c0, cn, k);
+      stage<KP, BT>(ds, dv, c0, cn, k);
       __syncthreads();
       for (int c = 0; c < cn; ++c) {   // (every lane walks: draw is the wave's)
         const double y = rate<KP>(hq, ds + c * KP);
@@ -278,13 +231,6 @@ int launch_sample(const double* d, const double* h, int k, int n, int p, int64_t
 }
 
 template <int KP>
-int launch_sample_x(const double* d, const double* h, int k, int n, int p, int64_t p_total, int64_t j0, const Rule& rule, void* x, int x_dtype,
-                    int layout, int64_t ld, int64_t* counts, hipStream_t s) {
-  if (x_dtype == ESPM_DIAG_X_U8) return launch_sample<KP, uint8_t>(d, h, k, n, p, p_total, j0, rule, x, layout, ld, counts, s);
-  return launch_sample<KP, uint16_t>(d, h, k, n, p, p_total, j0, rule, x, layout, ld, counts, s);
-}
-
-template <int KP>
 int launch_deviance(const double* d, const double* h, int k, int n, int p, int64_t p_total, int64_t j0, const Rule& rule, int n_rep,
                     double log_shift, double* dev, hipStream_t s) {
   const dim3 grid((unsigned)(((int64_t)p + BT - 1) / BT), (unsigned)(n_rep < 65535 ? n_rep : 65535)), block(BT);
@@ -306,9 +252,7 @@ static int sample_check(const char* who, const double* d, const double* h, int k
   ESPM_REQUIRE(d && h, "%s: bad arguments (d %p, h %p)", who, (const void*)d, (const void*)h);
   ESPM_REQUIRE(k >= 1 && k <= ESPM_SAMPLE_MAX_K, "%s: k=%d (1..%d components)", who, k, ESPM_SAMPLE_MAX_K);
   ESPM_REQUIRE(n >= 1 && p >= 1, "%s: bad arguments (n=%d, p=%d)", who, n, p);
-  ESPM_REQUIRE(j0 >= 0 && p_total >= p && j0 <= p_total - p, "%s: pixels j0=%lld .. j0 + p=%lld of p_total=%lld", who, (long long)j0,
-               (long long)j0 + p, (long long)p_total);
-  ESPM_REQUIRE(p_total <= INT64_MAX / n, "%s: n=%d x p_total=%lld elements (a 64-bit index)", who, n, (long long)p_total);
+  if (int rc = check_slab(who, n, p, p_total, j0)) return rc;
   ESPM_REQUIRE(first_rep >= 0 && last_rep <= (int64_t)0xFFFFFFFEll, "%s: replicate=%lld .. %lld (0 .. 2^32 - 2)", who, (long long)first_rep,
                (long long)last_rep);
   return ESPM_OK;
@@ -328,19 +272,15 @@ extern "C" int espm_poisson_sample(const double* d, const double* h, int k, int 
 #else
   if (int rc = sample_check("poisson sample", d, h, k, n, p, p_total, j0, replicate, replicate)) return rc;
   ESPM_REQUIRE(x && counts, "poisson sample: bad arguments (x %p, counts %p)", x, (void*)counts);
-  ESPM_REQUIRE(x_layout == ESPM_LAYOUT_CM || x_layout == ESPM_LAYOUT_PM, "poisson sample: x_layout %d", x_layout);
-  ESPM_REQUIRE(x_dtype == ESPM_DIAG_X_U8 || x_dtype == ESPM_DIAG_X_U16, "poisson sample: x_dtype %d (counts: u8 or u16)", x_dtype);
-  const int row = x_layout == ESPM_LAYOUT_CM ? p : n;
-  ESPM_REQUIRE(ld >= row, "poisson sample: ld=%lld below the row length %d", (long long)ld, row);
+  if (int rc = check_image("poisson sample", x, x_dtype, ESPM_DIAG_X_U16, x_layout, ld, n, p)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const samplek::Rule rule = sample_rule(seed, replicate);
   if (int rc = check_hip(hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), s), "poisson sample: zeroing the counters")) return rc;
-#define ESPM_SAMPLE_CASE(KP) return samplek::launch_sample_x<KP>(d, h, k, n, p, p_total, j0, rule, x, x_dtype, x_layout, ld, counts, s)
-  if (k <= 4) ESPM_SAMPLE_CASE(4);
-  if (k <= 8) ESPM_SAMPLE_CASE(8);
-  if (k <= 16) ESPM_SAMPLE_CASE(16);
-  ESPM_SAMPLE_CASE(32);
-#undef ESPM_SAMPLE_CASE
+  return dispatch_kp(k, [&](auto kp) {
+    return dispatch_xt<ESPM_DIAG_X_U16>(x_dtype, [&](auto xt) {
+      return samplek::launch_sample<decltype(kp)::value, typename decltype(xt)::type>(d, h, k, n, p, p_total, j0, rule, x, x_layout, ld, counts, s);
+    });
+  });
 #endif
 }
 
@@ -356,11 +296,8 @@ extern "C" int espm_sample_deviance(const double* d, const double* h, int k, int
   ESPM_REQUIRE(log_shift > 0, "sample deviance: log_shift=%g must be positive", log_shift);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const samplek::Rule rule = sample_rule(seed, replicate0);
-#define ESPM_SAMPLE_CASE(KP) return samplek::launch_deviance<KP>(d, h, k, n, p, p_total, j0, rule, n_rep, log_shift, dev, s)
-  if (k <= 4) ESPM_SAMPLE_CASE(4);
-  if (k <= 8) ESPM_SAMPLE_CASE(8);
-  if (k <= 16) ESPM_SAMPLE_CASE(16);
-  ESPM_SAMPLE_CASE(32);
-#undef ESPM_SAMPLE_CASE
+  return dispatch_kp(k, [&](auto kp) {
+    return samplek::launch_deviance<decltype(kp)::value>(d, h, k, n, p, p_total, j0, rule, n_rep, log_shift, dev, s);
+  });
 #endif
 }

@@ -5,6 +5,7 @@ import ctypes as C
 
 import numpy as np
 
+from espm_amd._image_args import check_layout, image_dims, layout_code
 from espm_amd.conf import log_shift
 
 
@@ -269,15 +270,14 @@ def _diag_host_dtype(dt):
 
 def _diag_check(X, D, H, layout, log_shift):
     """Shapes and arguments of pixel_diagnostics, before any device is touched: (n, p, k, D, H) with D, H as C-contiguous fp64."""
-    if layout not in ("cm", "pm"):
-        raise ValueError(f"layout must be 'cm' ((channels, pixels)) or 'pm' ((pixels, channels)), not {layout!r}")
+    check_layout(layout)
     if getattr(X, "ndim", None) != 2:
         raise ValueError("X must be a 2-D array or tensor")
     D = np.ascontiguousarray(D, dtype=np.float64)
     H = np.ascontiguousarray(H, dtype=np.float64)
     if D.ndim != 2 or H.ndim != 2 or D.shape[1] != H.shape[0]:
         raise ValueError(f"D must be (channels, k) and H (k, pixels): got {D.shape} and {H.shape}")
-    n, p = (int(X.shape[0]), int(X.shape[1])) if layout == "cm" else (int(X.shape[1]), int(X.shape[0]))
+    n, p = image_dims(X.shape, layout)
     k = int(D.shape[1])
     if D.shape[0] != n:
         raise ValueError(f"X has {n} channels, D has {D.shape[0]}")
@@ -349,7 +349,7 @@ def pixel_diagnostics(X, D, H, *, simplex_H=False, log_shift=log_shift, layout="
         dv = torch.empty(p, dtype=torch.float64, device=dev)
         hs = torch.empty((k, p), dtype=torch.float64, device=dev)
         ns = torch.zeros(1, dtype=torch.int32, device=dev)
-        _lib.check(_lib.lib.espm_pixel_diagnostics(_ptr(Xd), code, _lib.LAYOUT_CM if layout == "cm" else _lib.LAYOUT_PM, int(Xd.stride(0)),
+        _lib.check(_lib.lib.espm_pixel_diagnostics(_ptr(Xd), code, layout_code(layout), int(Xd.stride(0)),
                                                    n, p, _ptr(Dd), _ptr(Hd), k, float(log_shift), int(bool(simplex_H)), _ptr(dv), _ptr(hs),
                                                    _ptr(ns), _stream()))
         return dict(deviance=dv.cpu().numpy(), H_std=hs.cpu().numpy(), n_singular=int(ns.item()))
@@ -530,7 +530,7 @@ def spectral_diagnostics(X, D_or_W, H, *, G=None, simplex_rows=None, log_shift=l
         out = torch.empty((3 + nt) * n, dtype=torch.float64, device=dev)   # dev, xsum, ysum, then m_tri (n, nt)
         nbytes = int(_lib.lib.espm_channel_diagnostics_scratch(n, p, k))
         scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        _lib.check(_lib.lib.espm_channel_diagnostics(_ptr(Xd), code, _lib.LAYOUT_CM if layout == "cm" else _lib.LAYOUT_PM,
+        _lib.check(_lib.lib.espm_channel_diagnostics(_ptr(Xd), code, layout_code(layout),
                                                      int(Xd.stride(0)), n, p, _ptr(Dd), _ptr(Hd), k, float(log_shift), _ptr(out[:n]),
                                                      _ptr(out[n:2 * n]), _ptr(out[2 * n:3 * n]), _ptr(out[3 * n:]), _ptr(scratch),
                                                      nbytes, _stream()))

@@ -16,6 +16,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from espm_amd._image_args import check_layout, check_model, layout_code
+
 # T_i = floor(2^32 sum_{j <= i} e^-1 / j!): a 32-bit word w is the Poisson(1) draw #{i : w >= UNIT_CDF[i]}
 UNIT_CDF = (0x5e2d58d8, 0xbc5ab1b1, 0xeb715e1d, 0xfb239797, 0xff1025f5, 0xffd90f3b, 0xfffa8b71, 0xffff540c, 0xffffed1f, 0xfffffe21,
             0xffffffd4, 0xfffffffc)
@@ -38,12 +40,7 @@ def _check_n_rep(n_rep):
 
 def _model(D, H):
     """D (n, k) and H (k, p) as contiguous fp64 host arrays after every check: nothing is uploaded here."""
-    D, H = np.ascontiguousarray(D, dtype=np.float64), np.ascontiguousarray(H, dtype=np.float64)
-    if D.ndim != 2 or H.ndim != 2 or D.shape[1] != H.shape[0] or D.size == 0 or H.size == 0:
-        raise ValueError("D must be (channels, components) and H (components, pixels), both non-empty")
-    k = int(D.shape[1])
-    if k > MAX_K:
-        raise NotImplementedError(f"sampling: {k} components (the kernels are built for 1..{MAX_K})")
+    _, _, _, D, H = check_model(D, H, "sampling", MAX_K)
     for name, A in (("D", D), ("H", H)):
         if not np.isfinite(A).all():
             raise ValueError(f"{name} holds values that are not finite")
@@ -75,7 +72,7 @@ def _draw(Dd, Hd, dev, seed, replicate, dtype, layout):
         counts = torch.empty(2, dtype=torch.int64, device=dev)
         _lib.check(_lib.lib.espm_poisson_sample(_ptr(Dd), _ptr(Hd), k, n, p, p, 0, seed, replicate, _ptr(X),
                                                 _lib.DIAG_X_U8 if dtype == np.uint8 else _lib.DIAG_X_U16,
-                                                _lib.LAYOUT_CM if layout == "cm" else _lib.LAYOUT_PM, int(X.stride(0)), _ptr(counts), _stream()))
+                                                layout_code(layout), int(X.stride(0)), _ptr(counts), _stream()))
         saturated, invalid = (int(v) for v in counts.cpu().numpy())
     return X, saturated, invalid
 
@@ -86,8 +83,7 @@ def _check_sample_args(seed, replicate, dtype, layout):
     dtype = np.dtype(dtype)
     if dtype not in (np.dtype(np.uint8), np.dtype(np.uint16)):
         raise ValueError(f"dtype must be uint8 or uint16 (counts), not {dtype}")
-    if layout not in ("cm", "pm"):
-        raise ValueError(f"layout must be 'cm' ((channels, pixels)) or 'pm' ((pixels, channels)), not {layout!r}")
+    check_layout(layout)
     return seed, replicate, dtype
 
 

@@ -19,6 +19,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from espm_amd._image_args import check_layout, check_model, image_dims, layout_code
+
 MAX_COUNT = 65535
 
 
@@ -45,8 +47,7 @@ def _counts(X, layout):
     """X as the kernels read it - a host array or a device tensor of uint8 / uint16 - and (n, p): TypeError for an X that is no image of
     counts, ValueError for values outside 0 .. 65535.  Nothing is uploaded here."""
     import torch
-    if layout not in ("cm", "pm"):
-        raise ValueError(f"layout must be 'cm' ((channels, pixels)) or 'pm' ((pixels, channels)), not {layout!r}")
+    check_layout(layout)
     is_t = isinstance(X, torch.Tensor)
     if not is_t:
         X = np.asarray(X)
@@ -55,7 +56,7 @@ def _counts(X, layout):
     integer = (not (X.dtype.is_floating_point or X.dtype.is_complex)) if is_t else X.dtype.kind in "iub"
     if not integer:
         raise TypeError(f"thinning is defined for counts: X has dtype {X.dtype} (an integer dtype with values 0 .. {MAX_COUNT})")
-    n, p = (int(X.shape[0]), int(X.shape[1])) if layout == "cm" else (int(X.shape[1]), int(X.shape[0]))
+    n, p = image_dims(X.shape, layout)
     if X.dtype in ((torch.uint8, torch.uint16) if is_t else (np.uint8, np.uint16)):
         return X, n, p
     if is_t:
@@ -96,7 +97,7 @@ def _thin(X, q, seed, layout, want_b):
     with torch.cuda.device(dev):
         Xa = torch.empty(Xd.shape, dtype=Xd.dtype, device=dev)
         Xb = torch.empty(Xd.shape, dtype=Xd.dtype, device=dev) if want_b else None
-        _lib.check(_lib.lib.espm_thin_counts(_ptr(Xd), code, _lib.LAYOUT_CM if layout == "cm" else _lib.LAYOUT_PM, int(Xd.stride(0)), n, p, p, 0,
+        _lib.check(_lib.lib.espm_thin_counts(_ptr(Xd), code, layout_code(layout), int(Xd.stride(0)), n, p, p, 0,
                                              thr, seed, _ptr(Xa), _ptr(Xb) if want_b else None, int(Xa.stride(0)), _stream()))
     return Xa, Xb, q_eff
 
@@ -135,19 +136,10 @@ def split_deviance(X, D, H, q=0.5, seed=0, log_shift=1e-14, layout="cm"):
     thr, q_eff = threshold(q)
     seed = _check_seed(seed)
     X, n, p = _counts(X, layout)
-    D, H = np.ascontiguousarray(D, dtype=np.float64), np.ascontiguousarray(H, dtype=np.float64)
-    if D.ndim != 2 or H.ndim != 2 or D.shape[1] != H.shape[0]:
-        raise ValueError("D must be (channels, components) and H (components, pixels)")
-    k = int(D.shape[1])
-    if D.shape[0] != n:
-        raise ValueError(f"X has {n} channels, D has {D.shape[0]}")
-    if H.shape[1] != p:
-        raise ValueError(f"X has {p} pixels, H has {H.shape[1]}")
+    from espm_amd import _lib
+    n, p, k, D, H = check_model(D, H, "split_deviance", _lib.SPLIT_MAX_K, tuple(X.shape), layout)
     if not log_shift > 0:
         raise ValueError("log_shift must be positive")
-    from espm_amd import _lib
-    if not 1 <= k <= _lib.SPLIT_MAX_K:
-        raise NotImplementedError(f"split_deviance: {k} components (the kernel is built for 1..{_lib.SPLIT_MAX_K})")
     import torch
 
     from espm_amd.engine import _ptr, _stream
@@ -157,7 +149,7 @@ def split_deviance(X, D, H, q=0.5, seed=0, log_shift=1e-14, layout="cm"):
         da = torch.empty(p, dtype=torch.float64, device=dev)
         db = torch.empty(p, dtype=torch.float64, device=dev)
         cb = torch.empty(p, dtype=torch.int64, device=dev)
-        _lib.check(_lib.lib.espm_split_deviance(_ptr(Xd), code, _lib.LAYOUT_CM if layout == "cm" else _lib.LAYOUT_PM, int(Xd.stride(0)), n, p, p, 0,
+        _lib.check(_lib.lib.espm_split_deviance(_ptr(Xd), code, layout_code(layout), int(Xd.stride(0)), n, p, p, 0,
                                                 thr, seed, _ptr(Dd), _ptr(Hd), k, float(log_shift), _ptr(da), _ptr(db), _ptr(cb), _stream()))
         train_map, heldout_map, counts = da.cpu().numpy(), db.cpu().numpy(), cb.cpu().numpy()
     return dict(train_map=train_map, heldout_map=heldout_map, train=_ordered_sum(train_map), heldout=_ordered_sum(heldout_map),

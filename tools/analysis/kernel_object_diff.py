@@ -36,7 +36,9 @@ def code_object(obj, tmp):
 
 
 def kernels(obj, tmp):
-    """{kernel symbol: (metadata text, disassembly text)} of one object."""
+    """{kernel symbol: (metadata text, disassembly text)} of one object; none for a unit of host stubs (no device code at all)."""
+    if ".hip_fatbin" not in run(f"{BIN}/llvm-readelf", "-SW", obj):
+        return {}
     co = code_object(obj, tmp)
     meta = {}
     for entry in re.split(r"\n  - ", run(f"{BIN}/llvm-readelf", "--notes", co).split("amdhsa.kernels:")[1].split("amdhsa.target:")[0]):
