@@ -51,6 +51,16 @@ WIDE_MAX_K = 16      # libespm_mu_wide.so: 9..16 components (and the sparse coun
 WIDEST_MAX_K = 32    # libespm_mu_wide32.so: 17..32 components, dense stores only
 TAIL_DEFER, TAIL_RIDE = _D["ESPM_TAIL_DEFER"], _D["ESPM_TAIL_RIDE"]
 HI_KLX, HI_REG, HI_LAP, HI_SUMY, HI_BAD, HI_REL_W, HI_REL_H = (_D["ESPM_HI_" + n] for n in ("KLX", "REG", "LAP", "SUMY", "BAD", "REL_W", "REL_H"))
+# espm_mu_w_update_form: the forms of the W update by name, in the header's order
+W_FORMS = {_D["ESPM_W_FORM_" + n]: n.lower() for n in ("LOCAL", "SIMPLEX_SPLIT", "DICT_COLUMNS", "DICT_TWO_LAUNCH", "ONE_WG_REGISTERS", "ONE_WG_GENERAL")}
+W_FORMS_BY_NAME = {name: value for value, name in W_FORMS.items()}
+
+
+def w_form_detail(detail):
+    """espm_mu_w_update_form's `detail` unpacked (include/espm_mu.h: ESPM_W_DETAIL_*); {} for 0 - every form but the register-resident one."""
+    if not detail:
+        return {}
+    return dict(threads=detail & 0xfff, rows=(detail >> 12) & 0xf, channels=(detail >> 16) & 0xf, gta_all_threads=bool((detail >> 20) & 1))
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -76,6 +86,7 @@ SYMBOLS = {
     "espm_mu_state_layout": (C.c_char_p, []),
     "espm_mu_query": (C.c_int, [_SP]),
     "espm_mu_w_update_is_local": (C.c_int, [_SP]),
+    "espm_mu_w_update_form": (C.c_int, [_SP, C.POINTER(C.c_int)]),
     "espm_mu_w_update_tail": (C.c_int, [_SP, C.c_int, C.c_int, _vp]),
     "espm_mu_pack_x": (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "espm_mu_ell_count": (C.c_int, [_SP, _vp, _vp, _vp, _vp, _vp]),

@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "mu_common.hpp"
+#include "mu_w_plan.hpp"
 #include "mu_xchg.hpp"
 
 namespace espm {
@@ -316,17 +317,21 @@ int espm_mu_hstat(const espm_mu_state* st, int which, espm_stream_t stream) {
   return launch_hstat(st->h[which], st->k, st->p, st->p_pad, st->hstat[which], static_cast<hipStream_t>(stream));
 }
 
-// W' needs nothing global but the row sums of the new H: the reduction workgroups finish W themselves
-static bool w_update_is_local(const espm_mu_state* st) {
-  return st->m == 0 && !st->simplex_w && st->n >= 64 && st->w_scratch != nullptr;
+// The forms of the W update that run inside the slab reduction's launches, ahead of launch_w_finish (0: neither - the plan of
+// launch_w_finish decides, mu_w_plan.hpp: plan_w_finish).  The half-steps below switch on this; espm_mu_w_update_form returns it.
+// ESPM_W_FORM_LOCAL: W' needs nothing global but the row sums of the new H: the reduction workgroups finish W themselves.
+// ESPM_W_FORM_SIMPLEX_SPLIT: the simplex over W with G = identity and every row in the simplex: the multipliers follow from
+// per-component sums over the channels, so the update runs as two many-workgroup launches (slab reduction + those sums, then
+// w_simplex_update_kernel) instead of the reduction and ONE workgroup that finds the multipliers (mu_w_reduce.hip against
+// mu_w_finish.hip).  Its tail is the local update's.
+static int w_form_ahead(const espm_mu_state* st) {
+  if (st->m != 0 || st->n < 64 || st->w_scratch == nullptr) return 0;
+  if (!st->simplex_w) return ESPM_W_FORM_LOCAL;
+  if (!st->simplex_rows && !st->breg_sr_ch && !(st->pg_gamma_w > 0.f) && st->n_pad % 32 == 0 && st->no_fused != 1) return ESPM_W_FORM_SIMPLEX_SPLIT;
+  return 0;
 }
-// The simplex over W with G = identity and every row in the simplex: the multipliers follow from per-component sums over the
-// channels, so the update runs as two many-workgroup launches (slab reduction + those sums, then w_simplex_update_kernel)
-// instead of the reduction and ONE workgroup that finds the multipliers (mu_w_reduce.hip against mu_w_finish.hip).  Its tail is the local update's.
-static bool w_simplex_split(const espm_mu_state* st) {
-  return st->m == 0 && st->simplex_w && !st->simplex_rows && !st->breg_sr_ch && !(st->pg_gamma_w > 0.f) && st->n >= 64 &&
-         st->w_scratch != nullptr && st->n_pad % 32 == 0 && st->no_fused != 1;
-}
+static bool w_update_is_local(const espm_mu_state* st) { return w_form_ahead(st) == ESPM_W_FORM_LOCAL; }
+static bool w_simplex_split(const espm_mu_state* st) { return w_form_ahead(st) == ESPM_W_FORM_SIMPLEX_SPLIT; }
 // where the partials of the bracket live: behind the tail's three arrays of k * nbk doubles in w_scratch (2 n k floats)
 static double* simplex_bparts(const espm_mu_state* st) {
   return reinterpret_cast<double*>(st->w_scratch) + 3 * (size_t)st->k * ((st->n_pad + 31) / 32);
@@ -461,16 +466,18 @@ static int simplex_update(const espm_mu_state* st, int src, int slot, WTailArgs*
 // records rides in the reduction's launch (null: hstat[1 - src] is already reduced).  tail_out: the update's tail is handed to the
 // caller instead of being launched (null: launched; the one-workgroup finish has no tail).
 static int w_half(const espm_mu_state* st, int src, int slot, const HFinalizeArgs* fin, WTailArgs* tail_out, hipStream_t s) {
-  if (w_update_is_local(st))
-    return launch_w_reduce_update(update_args(st, src, slot), st->a_slab, (size_t)st->k * st->n_pad * sizeof(float), st->nblk_w, st->a,
-                                  fin ? st->hpart : nullptr, nblk_h(st), fin ? nullptr : st->hstat[1 - src], 0, nullptr, fin, s, tail_out);
-  if (w_simplex_split(st)) {   // st->a_slab -> st->a and the bracket's partials; then the update
-    if (int rc = simplex_w_feasible(st, st->n)) return rc;
-    if (int rc = launch_w_reduce(st->a_slab, st->a, st->nblk_w, st->k * st->n_pad, fin, s, st->w[src], simplex_bparts(st), st->n, st->k, st->n_pad)) return rc;
-    return simplex_update(st, src, slot, tail_out, s);
+  switch (w_form_ahead(st)) {
+    case ESPM_W_FORM_LOCAL:
+      return launch_w_reduce_update(update_args(st, src, slot), st->a_slab, (size_t)st->k * st->n_pad * sizeof(float), st->nblk_w, st->a,
+                                    fin ? st->hpart : nullptr, nblk_h(st), fin ? nullptr : st->hstat[1 - src], 0, nullptr, fin, s, tail_out);
+    case ESPM_W_FORM_SIMPLEX_SPLIT:   // st->a_slab -> st->a and the bracket's partials; then the update
+      if (int rc = simplex_w_feasible(st, st->n)) return rc;
+      if (int rc = launch_w_reduce(st->a_slab, st->a, st->nblk_w, st->k * st->n_pad, fin, s, st->w[src], simplex_bparts(st), st->n, st->k, st->n_pad)) return rc;
+      return simplex_update(st, src, slot, tail_out, s);
+    default:   // launch_w_finish's plan chooses among the other four forms
+      if (int rc = launch_w_reduce(st->a_slab, st->a, st->nblk_w, st->k * st->n_pad, fin, s)) return rc;
+      return w_finish(st, src, 1 - src, slot + 1, s);
   }
-  if (int rc = launch_w_reduce(st->a_slab, st->a, st->nblk_w, st->k * st->n_pad, fin, s)) return rc;
-  return w_finish(st, src, 1 - src, slot + 1, s);
 }
 // the same from the gathered records of `world` ranks: their sum, the global statistics of the new H, the W update
 static int shard_combine_finish(const espm_mu_state* st, const void* records, int world, int src, int slot, WTailArgs* tail_out, hipStream_t s) {
@@ -578,6 +585,16 @@ int espm_mu_shard_combine_finish(const espm_mu_state* st, const void* records, i
 int espm_mu_w_update_is_local(const espm_mu_state* st) {
   if (check_state(st)) return 0;
   return w_update_is_local(st) ? 1 : 0;
+}
+
+int espm_mu_w_update_form(const espm_mu_state* st, int* detail) {
+  if (int rc = check_state(st)) return rc;   // (negative: a state the library cannot read)
+  if (detail) *detail = 0;
+  if (const int ahead = w_form_ahead(st)) return ahead;
+  // what w_half's launch_w_finish plans for an update (its arguments but for the history row, which no form depends on)
+  const WFinishPlan pl = plan_w_finish(finish_args(st, st->cur == 1 ? 1 : 0, 0, -1, 1));
+  if (detail && pl.form == ESPM_W_FORM_ONE_WG_REGISTERS) *detail = pl.nt | pl.rows << 12 | pl.crows << 16 | pl.gta_all << 20;
+  return pl.form;
 }
 
 int espm_mu_w_update_tail(const espm_mu_state* st, int src, int slot, espm_stream_t stream) {

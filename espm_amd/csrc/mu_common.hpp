@@ -1002,6 +1002,15 @@ int launch_w_exchange_update(const WFinishArgs& f, const void* slabs, size_t sla
                              const HFinalizeArgs& fin, const struct ::espm_xchg* xc, unsigned int seq, const float* h_new, int nx, int ny,
                              int p_pad, int with_halo, hipStream_t stream, WTailArgs* defer_tail, double* simplex_bparts = nullptr);
 bool w_gsplit_applies(const WFinishArgs& args);   // the W finish with a dictionary G as many-workgroup launches (mu_w_dict.hip)
+// What launch_w_finish runs for these arguments (plan_w_finish, mu_w_plan.hpp): the launchers switch on this plan and
+// espm_mu_w_update_form returns it, so the answer cannot drift from the launch.  form: ESPM_W_FORM_DICT_COLUMNS, _DICT_TWO_LAUNCH, _ONE_WG_REGISTERS or
+// _ONE_WG_GENERAL (the two forms ahead of launch_w_finish are mu_api.hip's: plan_w_update).  For the register-resident finish:
+// the instance w_finish_fast_kernel<k, rows, nt, crows> and whether its G^T A is the all-threads one.
+struct WFinishPlan {
+  int form = 0;
+  int nt = 0, rows = 0, crows = 0, gta_all = 0;
+  size_t lds = 0;   // dynamic LDS of the register-resident finish
+};
 int launch_w_gxchg_update(const WFinishArgs& f, const struct ::espm_xchg* xc, unsigned int seq, const double* hstat_local, double* hstat_out,
                           const float* h_new, int nx, int ny, int p_pad, int with_halo, hipStream_t stream);
 WTailArgs make_w_tail_args(const WFinishArgs& f);

@@ -303,7 +303,7 @@ __global__ __launch_bounds__(256) void w_gxchg_update_kernel(const WGxchgArgs x)
 // process's launch count).  The entries of W' the finisher compares are stored write-through (sc1) and drained before the granule, and read
 // with sc1 loads behind it (MI355X_MICROARCH.md, valid forms: data-tagged granules; sc1 payload drained before the flag, sc1 loads).
 // Built for m <= GC_MMAX columns and n_pad <= GC_CPT * GC_THREADS channels; anything else keeps the launches above.
-constexpr int GC_THREADS = 1024, GC_CPT = 2, GC_MMAX = 32;
+// (GC_THREADS, GC_CPT, GC_MMAX: mu_w_plan.hpp, with the predicate of this form)
 
 // the extra workgroup of a sharded exchange launch: boundary rows of H' (16-byte write-through stores), this rank's statistics as granules, the rows' flag
 __device__ __forceinline__ void gxchg_extra_role(const WGxchgArgs& x, int nthreads) {
@@ -567,13 +567,6 @@ bool w_gsplit_applies(const WFinishArgs& args) {
   static const bool enabled = w_env_knob("ESPM_W_GSPLIT", true);
   return enabled;
 }
-// the column form applies where the two-launch form does, the dictionary has at most GC_MMAX columns and a thread holds its channels
-bool w_gcol_applies(const WFinishArgs& args) {
-  if (!(w_gsplit_applies(args) && args.m <= GC_MMAX && args.n_pad <= GC_CPT * GC_THREADS && args.k <= KP && (size_t)2 * args.m * args.k * sizeof(float) >= (size_t)args.k * 8))
-    return false;
-  static const bool enabled = w_env_knob("ESPM_W_GCOL", true);
-  return enabled;
-}
 static unsigned int w_gcol_nonce() {
   static std::atomic<unsigned int> count{0};
   unsigned int v = ++count;
@@ -613,17 +606,12 @@ int launch_w_gxchg_update(const WFinishArgs& f, const espm_xchg* xc, unsigned in
   return launch_w_gfinish_gw(f, stream);
 }
 
-// launch_w_finish's way in: the column form, else the two launches, else false (the one-workgroup finish, mu_w_finish.hip)
-bool launch_w_dict_finish(const WFinishArgs& args, hipStream_t stream, int* rc) {
-  if (w_gcol_applies(args)) {
-    *rc = launch_w_gcol(args, stream);
-    return true;
-  }
-  if (!w_gsplit_applies(args)) return false;
+// launch_w_finish's: the form that plan_w_dict chose
+int launch_w_dict_finish(const WFinishArgs& args, int form, hipStream_t stream) {
+  if (form == ESPM_W_FORM_DICT_COLUMNS) return launch_w_gcol(args, stream);
   hipLaunchKernelGGL(w_gfinish_update_kernel, dim3((unsigned)args.m * args.k), dim3(256), 0, stream, args);
-  *rc = check_hip(hipGetLastError(), "w_finish (dictionary G: update)");
-  if (*rc == 0) *rc = launch_w_gfinish_gw(args, stream);
-  return true;
+  if (int rc = check_hip(hipGetLastError(), "w_finish (dictionary G: update)")) return rc;
+  return launch_w_gfinish_gw(args, stream);
 }
 
 }  // namespace espm

@@ -6,15 +6,7 @@ namespace espm {
 
 // ---- W finish: one workgroup of 1024 threads --------------------------------------------------
 
-constexpr int WF_THREADS = 1024;
-#ifndef ESPM_WF_FEW_THREADS
-#define ESPM_WF_FEW_THREADS 512
-#endif
-constexpr int WF_FEW_THREADS = ESPM_WF_FEW_THREADS;   // threads of the register-resident W finish for G = identity, k <= WF_HALF_MAX_K (A/B: 256)
-#ifndef ESPM_WF_HALF_MAX_K
-#define ESPM_WF_HALF_MAX_K 8
-#endif
-constexpr int WF_HALF_MAX_K = ESPM_WF_HALF_MAX_K;   // component counts up to which the register-resident W finish also exists with 512 threads
+// (WF_THREADS, WF_FEW_THREADS, WF_HALF_MAX_K, WF_GTA_MAX, WF_GTA_PAR: mu_w_plan.hpp, with the plan that chooses among the kernels below)
 
 // Register-resident variant for M <= WF_ROWS * 1024 rows (and M * k <= WF_GTA_MAX when G is given): thread t
 // owns rows t, t + 1024, ... of W and keeps their old / numerator / denominator / new entries in registers
@@ -22,9 +14,6 @@ constexpr int WF_HALF_MAX_K = ESPM_WF_HALF_MAX_K;   // component counts up to wh
 // (sum over the `nsplit` partials, fixed order) is folded into the load of A; G^T A is formed by one wave
 // per output entry and G W' reads W' from LDS.  Same arithmetic and the same global-stop bisection as
 // w_finish_kernel below; only the data movement differs.
-constexpr int WF_GTA_MAX = 8192;
-constexpr int WF_GTA_PAR = 512;  // M * k up to which G^T A uses the all-threads path (16 x M k floats of LDS)
-
 // One step of a packed butterfly sum over the lanes of a wave: of the first N values a lane keeps one half
 // (the upper one when `up`) and adds the partner's copy of that half, which the partner sends instead of keeping.
 template <int N>
@@ -721,63 +710,58 @@ __global__ __launch_bounds__(WF_THREADS) void w_finish_kernel(const WFinishArgs 
     for (int kk = 0; kk < KP; ++kk) a.colsum_gw[kk] = cs[kk];
 }
 
+// the instance w_finish_fast_kernel<KK, rows, NT, crows> that the plan names (plan_w_finish, mu_w_plan.hpp, has chosen among those built)
 template <int KK, int NT>
-static void launch_fast(const WFinishArgs& args, int rows, int crows, size_t lds, hipStream_t stream) {
-  if (crows > rows && rows <= 1) {   // dictionary G with at most NT rows: W state of one row per thread, 2 or 4 channels per thread for G^T A
-    if (crows <= 2)
+static void launch_fast(const WFinishPlan& pl, const WFinishArgs& args, hipStream_t stream) {
+  const size_t lds = pl.lds;
+  if (pl.crows != pl.rows) {   // dictionary G with at most NT rows: W state of one row per thread, 2 or 4 channels per thread for G^T A
+    if (pl.crows == 2)
       hipLaunchKernelGGL((w_finish_fast_kernel<KK, 1, NT, 2>), dim3(1), dim3(NT), lds, stream, args);
     else
       hipLaunchKernelGGL((w_finish_fast_kernel<KK, 1, NT, 4>), dim3(1), dim3(NT), lds, stream, args);
     return;
   }
-  if (crows > rows) rows = crows;
-  if constexpr (NT == 256) {   // (4 waves: 8 rows per thread at 2048 channels)
-    if (rows > 4) {
+  // (NT == 256 exists only in the A/B build with -DESPM_WF_FEW_THREADS=256, and so does its instance of 8 rows per thread - 4 waves at
+  //  2048 channels; the product's plan never names either)
+  if constexpr (NT == 256) {
+    if (pl.rows == 8) {
       hipLaunchKernelGGL((w_finish_fast_kernel<KK, 8, NT>), dim3(1), dim3(NT), lds, stream, args);
       return;
     }
   }
-  if (rows <= 1)
+  if (pl.rows == 1)
     hipLaunchKernelGGL((w_finish_fast_kernel<KK, 1, NT>), dim3(1), dim3(NT), lds, stream, args);
-  else if (rows <= 2)
+  else if (pl.rows == 2)
     hipLaunchKernelGGL((w_finish_fast_kernel<KK, 2, NT>), dim3(1), dim3(NT), lds, stream, args);
   else
     hipLaunchKernelGGL((w_finish_fast_kernel<KK, 4, NT>), dim3(1), dim3(NT), lds, stream, args);
 }
 
+// (which form, and which instance: plan_w_finish, mu_w_plan.hpp)
 int launch_w_finish(const WFinishArgs& args, hipStream_t stream) {
-  const int M = args.m > 0 ? args.m : args.n;
-  const long mk = (long)M * args.k;
-  int rc;
-  if (launch_w_dict_finish(args, stream, &rc)) return rc;   // a dictionary G one of the many-workgroup forms applies to
-  const int span = M > args.n_cm ? M : args.n_cm;
-  // G = identity, up to 8 components (the narrow build), up to 2048 rows: 8 waves with 256 registers each (with the simplex
-  // over W at the headline size 49 -> 37 us at k = 5, iteration 278 -> 248 us at k = 8); a dictionary G keeps the 16 waves
-  // (its loops over the rows of G want them: C5 141 vs 151 us)
-  const int nt = (!args.g && args.k <= WF_HALF_MAX_K && span <= 4 * 512) ? WF_FEW_THREADS : WF_THREADS;
-  const int crows = (span + nt - 1) / nt;               // channels (or, with G = identity, rows of W) per thread
-  const int rows = args.g ? (M + nt - 1) / nt : crows;   // rows of W per thread
-  // G given: [M][k rounded up to 4] new W, [M k] G^T A, and the per-wave partials of the all-threads G^T A (within the 64 KB a
-  // kernel gets without asking)
-  const size_t lds = args.g ? ((size_t)M * ((args.k + 3) / 4 * 4) + (size_t)mk * (1 + (args.g_t && mk <= WF_GTA_PAR ? WF_THREADS / 64 : 0))) * sizeof(float) : 0;
-  // (the widest build - 17..32 components - has the general one-workgroup finish only: the register-resident ones are not built there;
-  //  ESPM_W_FINISH_GENERAL=1 sends the other builds there too - tests: images small enough for the register-resident kernels never reach it)
-  static const bool general_only = w_env_knob("ESPM_W_FINISH_GENERAL", false);
-  if (KP <= 16 && !general_only && crows <= (nt == 256 ? 8 : 4) && rows <= (nt == 256 ? 8 : 4) && (!args.g || (mk <= WF_GTA_MAX && lds <= 64 * 1024))) {
-    switch (args.k) {
+  const WFinishPlan pl = plan_w_finish(args);
+  switch (pl.form) {
+    case ESPM_W_FORM_DICT_COLUMNS:
+    case ESPM_W_FORM_DICT_TWO_LAUNCH: return launch_w_dict_finish(args, pl.form, stream);
+    case ESPM_W_FORM_ONE_WG_GENERAL:
+      // (w_finish_kernel keeps numerators and denominators of an update in the workspace; the register-resident finishes need none,
+      //  which is how a state without one gets here at all - mu_api.hip: w_form_ahead)
+      ESPM_REQUIRE(!args.update_w || args.scratch, "w_finish: the general one-workgroup W update of %d x %d entries needs w_scratch", args.m > 0 ? args.m : args.n, args.k);
+      hipLaunchKernelGGL(w_finish_kernel, dim3(1), dim3(WF_THREADS), 0, stream, args);
+      break;
+    default:
+      switch (args.k) {
 #if ESPM_KP <= 16
 #define ESPM_X(KK)                                                              \
   case KK:                                                                      \
-    if (nt == WF_FEW_THREADS) launch_fast<KK, (KK <= WF_HALF_MAX_K ? WF_FEW_THREADS : WF_THREADS)>(args, rows, crows, lds, stream); \
-    else launch_fast<KK, WF_THREADS>(args, rows, crows, lds, stream);                  \
+    if (pl.nt == WF_FEW_THREADS) launch_fast<KK, (KK <= WF_HALF_MAX_K ? WF_FEW_THREADS : WF_THREADS)>(pl, args, stream); \
+    else launch_fast<KK, WF_THREADS>(pl, args, stream);                  \
     break;
-      ESPM_K_CASES(ESPM_X)
+        ESPM_K_CASES(ESPM_X)
 #undef ESPM_X
 #endif
-      default: return set_error(ESPM_EUNSUPPORTED, "w_finish: k=%d not built", args.k);
-    }
-  } else {
-    hipLaunchKernelGGL(w_finish_kernel, dim3(1), dim3(WF_THREADS), 0, stream, args);
+        default: return set_error(ESPM_EUNSUPPORTED, "w_finish: k=%d not built", args.k);
+      }
   }
   return check_hip(hipGetLastError(), "w_finish launch");
 }

@@ -17,6 +17,7 @@
 #include <stdlib.h>
 
 #include "mu_common.hpp"
+#include "mu_w_plan.hpp"
 #include "mu_xchg.hpp"
 
 namespace espm {
@@ -187,18 +188,11 @@ __device__ __forceinline__ double block_max1(double v, double* scratch) {
   return bc;
 }
 
-// An on / off knob of the environment (README.md: ESPM_W_GCOL, ESPM_W_GSPLIT, ESPM_W_FINISH_GENERAL): `dflt` unless the variable is
-// set and begins with the other value's digit.  Its user keeps the answer in a function-local static: read once per process.
-static inline bool w_env_knob(const char* name, bool dflt) {
-  const char* e = getenv(name);
-  return e ? (dflt ? e[0] != '0' : e[0] == '1') : dflt;
-}
-
 #pragma GCC visibility push(hidden)   // between the units: not part of the library's interface
 // mu_w_reduce.hip: the tail of a many-workgroup update, handed to the caller (it rides in a later launch) or launched here; the launches' status as `what`
 int w_tail_defer_or_launch(const WFinishArgs& f, WTailArgs* defer_tail, hipStream_t stream, const char* what);
-// mu_w_dict.hip: the W finish of a dictionary G as many-workgroup launches, where one applies (then true, its status in *rc)
-bool launch_w_dict_finish(const WFinishArgs& args, hipStream_t stream, int* rc);
+// mu_w_dict.hip: the W finish of a dictionary G as the many-workgroup form that plan_w_dict chose (mu_w_plan.hpp)
+int launch_w_dict_finish(const WFinishArgs& args, int form, hipStream_t stream);
 #pragma GCC visibility pop
 
 }  // namespace espm

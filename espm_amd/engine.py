@@ -1063,6 +1063,17 @@ class MUEngine:
         """Whether ``iterate_h`` runs one launch per iteration (include/espm_mu.h: espm_mu_h_chain_applies)."""
         return int(self.lib.espm_mu_h_chain_applies(C.byref(self.st))) == 1
 
+    def w_update_form(self):
+        """Which form the unsharded W half-step takes for this state, from the plan the launch itself switches on
+        (include/espm_mu.h: espm_mu_w_update_form): ``(name, detail)`` - one of ``_lib.W_FORMS``' names ("local", "simplex_split",
+        "dict_columns", "dict_two_launch", "one_wg_registers", "one_wg_general") and, for the register-resident finish, the kernel
+        instance as ``dict(threads, rows, channels, gta_all_threads)``; ``{}`` for the other forms."""
+        detail = C.c_int(0)
+        form = int(self.lib.espm_mu_w_update_form(C.byref(self.st), C.byref(detail)))
+        if form <= 0:
+            self._check(form)
+        return _lib.W_FORMS[form], _lib.w_form_detail(detail.value)
+
     def advance_h_only(self):
         """One H-only iteration, host-sequenced (the granular step of a stop-rule loop): the H-step from the current state and the
         reduction of its records - history slot ``it`` gets the loss pieces of the current state - then the new H is the current one.

@@ -224,7 +224,8 @@ typedef struct espm_mu_state {
   double* hstat[2];         /* (ESPM_HS_STRIDE) statistics of h[0] / h[1] (global)       */
   float* a_slab;            /* (nblk_w, k, n_pad)                                        */
   float* a;                 /* (k, n_pad)                                                */
-  float* w_scratch;         /* (2, m or n, k), zero before the first call (a ticket of the dictionary-G W finish lives there) */
+  float* w_scratch;         /* (2, m or n, k), zero before the first call (a ticket of the dictionary-G W finish lives there); NULL keeps the W update
+                             * off its many-workgroup forms (A/B, tests) - the general one-workgroup finish then refuses an update (ESPM_EINVAL) */
   double* hist;             /* (hist_len, ESPM_HI_STRIDE), zero-initialised              */
   int32_t hist_len;
   int32_t cur;              /* index of the current W/H buffers (0/1), flipped by iterate */
@@ -493,6 +494,32 @@ int espm_mu_h_chain_applies(const espm_mu_state* st);
 /* 1 when the W update needs nothing global (G = identity, no simplex over W, ...): the slab / record reduction updates W
  * itself and a tail workgroup finishes (tail_mode above); 0: espm_mu_w_finish does the update, there is no tail. */
 int espm_mu_w_update_is_local(const espm_mu_state* st);
+/* Which form the unsharded W half-step takes for this state, as espm_mu_iterate / espm_mu_w_reduce_finish sequence it (the local
+ * update and the simplex split run inside the slab reduction's launches) and, behind those two, as espm_mu_w_finish launches it.
+ * Answered from the plan that the launch itself switches on.  No predicate depends on the pixel count.
+ *   ESPM_W_FORM_LOCAL          the reduction workgroups update their own entries of W (what espm_mu_w_update_is_local says)
+ *   ESPM_W_FORM_SIMPLEX_SPLIT  simplex over every row of W with G = identity: slab reduction + bracket sums, then a many-workgroup update
+ *   ESPM_W_FORM_DICT_COLUMNS   dictionary G with at most 32 columns over at most 2048 padded channels: one launch, a workgroup per component
+ *   ESPM_W_FORM_DICT_TWO_LAUNCH  dictionary G without simplex / projected gradient / Bregman, m k <= 8192: update per entry, then rows of G W'
+ *   ESPM_W_FORM_ONE_WG_REGISTERS  one workgroup that keeps its rows of W in registers (1..16 components)
+ *   ESPM_W_FORM_ONE_WG_GENERAL   one workgroup, nothing register-resident: everything else, and all of the 17..32 build
+ * (ESPM_W_GCOL=0, ESPM_W_GSPLIT=0 and ESPM_W_FINISH_GENERAL=1 in the environment, read once per process, move a state down this list.)
+ * detail (may be NULL): 0 except for ESPM_W_FORM_ONE_WG_REGISTERS, where it packs the kernel instance -
+ *   bits 0..11 threads of the workgroup (512 or 1024), bits 12..15 rows of W per thread (1, 2, 4), bits 16..19 channels per thread
+ *   in the phase that forms G^T A (1, 2, 4; equal to the rows with G = identity), bit 20 set when G^T A is the all-threads one
+ *   (dictionary G, m k <= 512, k <= 8) and not one wave per entry.  ESPM_W_DETAIL_* below unpack it.
+ * A negative espm_status for a state the library refuses. */
+#define ESPM_W_FORM_LOCAL 1
+#define ESPM_W_FORM_SIMPLEX_SPLIT 2
+#define ESPM_W_FORM_DICT_COLUMNS 3
+#define ESPM_W_FORM_DICT_TWO_LAUNCH 4
+#define ESPM_W_FORM_ONE_WG_REGISTERS 5
+#define ESPM_W_FORM_ONE_WG_GENERAL 6
+#define ESPM_W_DETAIL_THREADS(d) ((d) & 0xfff)
+#define ESPM_W_DETAIL_ROWS(d) (((d) >> 12) & 0xf)
+#define ESPM_W_DETAIL_CHANNELS(d) (((d) >> 16) & 0xf)
+#define ESPM_W_DETAIL_GTA_ALL_THREADS(d) (((d) >> 20) & 1)
+int espm_mu_w_update_form(const espm_mu_state* st, int* detail);
 /* The tail of the update w[src] -> w[1 - src] that produced state slot + 1, as a launch of its own (after a finish call
  * with ESPM_TAIL_DEFER when no H-step will carry it). */
 int espm_mu_w_update_tail(const espm_mu_state* st, int src, int slot, espm_stream_t stream);

@@ -1134,10 +1134,11 @@ def test_sparse_store_at_the_160_kb_limits(k, n):
 
 @pytest.mark.parametrize("algo", ["projected_gradient", "log_surrogate"])
 def test_w_finishes_of_a_dictionary_over_5000_channels(SmoothNMF, algo):
-    """A dictionary G over MORE than 4096 channels.  projected_gradient: the one-workgroup W finish that keeps nothing in registers (the
-    register-resident finishes hold up to four channels per thread) - the branch it lacked until round 5.  log_surrogate: the two-launch finish
-    (`w_gfinish_update_kernel` + `w_gfinish_gw_kernel`), which configuration 5 ran until its one-launch column form took over at up to 2048
-    channels.  Against the oracle."""
+    """A dictionary G over MORE than 4096 channels: both rules run the one-workgroup W finish that keeps nothing in registers
+    (`w_finish_kernel`: the register-resident finishes hold up to four channels per thread).  projected_gradient: the branch it lacked
+    until round 5.  log_surrogate: with m = 9 and k = 3 the workspace of 2 m k floats (216 bytes) does not hold the 20 row workgroups'
+    partial column sums (1296), so the two-launch finish does not apply here either - its case at 5000 channels is the row
+    n-dict-two-5000 of tests/test_gpu_w_update_forms.py.  Against the oracle."""
     rng = np.random.default_rng(11)
     n, nx, ny, k, m = 5000, 10, 12, 3, 9
     p = nx * ny
@@ -1162,6 +1163,7 @@ def test_w_finishes_of_a_dictionary_over_5000_channels(SmoothNMF, algo):
     assert np.isfinite(ref["losses"]).all() and (np.diff(ref["losses"]) <= 0).all()
     est = SmoothNMF(n_components=k, G=G, shape_2d=(nx, ny), algo=algo, tol=0, no_stop_criterion=True, max_iter=5, verbose=0, **extra, **kw)
     quiet(est.fit, X, W=W0.copy(), H=H0.copy())
+    assert est._engine.w_update_form() == ("one_wg_general", {})
     np.testing.assert_allclose(est.losses_, ref["losses"], rtol=1e-4)
     np.testing.assert_allclose(est.H_, ref["H"], rtol=2e-3, atol=2e-4)
     np.testing.assert_allclose(est.W_, ref["W"], rtol=2e-3, atol=2e-3 * np.abs(ref["W"]).mean())

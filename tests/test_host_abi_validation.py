@@ -73,6 +73,21 @@ def test_a_state_that_was_never_queried_is_refused(lib):
         assert rc != 0 and lib.lib.espm_mu_last_error(), (name, rc)      # (no buffers: refused, or the runtime's own error without a device)
 
 
+def test_w_update_form_is_a_query(lib):
+    """espm_mu_w_update_form refuses a state without its derived fields like the compute entry points (a negative status, never a form),
+    answers a queried one without a single buffer - it launches nothing - and takes NULL for `detail`
+    (the forms themselves: tests/test_w_update_form_cpu.py)."""
+    st = lib.MUState()
+    st.n, st.p, st.k, st.x_dtype, st.xscale = 64, 64, 3, lib.X_F32, 1.0
+    assert lib.lib.espm_mu_w_update_form(C.byref(st), None) == lib.EINVAL and b"espm_mu_query" in lib.lib.espm_mu_last_error()
+    assert lib.lib.espm_mu_query(C.byref(st)) == 0
+    detail = C.c_int(-1)
+    form = lib.lib.espm_mu_w_update_form(C.byref(st), C.byref(detail))
+    assert form in lib.W_FORMS and form == lib.lib.espm_mu_w_update_form(C.byref(st), None)
+    assert (detail.value != 0) == (lib.W_FORMS[form] == "one_wg_registers")
+    assert lib.SYMBOLS["espm_mu_w_update_form"][0] is C.c_int and len(lib.SYMBOLS["espm_mu_w_update_form"][1]) == 2
+
+
 def test_exchange_and_helper_entry_points_validate_their_arguments(lib):
     L = lib.lib
     ctx = C.c_void_p()
