@@ -18,11 +18,13 @@ LIB_PATH = os.environ.get("ESPM_MU_LIB", os.path.join(_HERE, "lib", "libespm_mu.
 
 from . import _abi
 
-# ---- constants and the state layout come from include/espm_mu.h itself (espm_amd/_abi.py parses it): no hand-kept copy ----
+# ---- constants, enums, the state layout and every prototype come from include/espm_mu.h itself (espm_amd/_abi.py parses it):
+# ---- no hand-kept copy of any of them ----
 _HEADER_TEXT = _abi.header_text()
 _D = _abi.parse_defines(_HEADER_TEXT)
-OK, EINVAL, ENOSOLUTION, EHIP, EUNSUPPORTED = 0, -1, -2, -3, -4          # enum espm_status
-X_F32, X_BF16, X_U8, X_ELL = 0, 1, 2, 3                                  # enum ESPM_X_*
+_E = _abi.parse_enums(_HEADER_TEXT)
+OK, EINVAL, ENOSOLUTION, EHIP, EUNSUPPORTED = (_E["ESPM_" + n] for n in ("OK", "EINVAL", "ENOSOLUTION", "EHIP", "EUNSUPPORTED"))   # enum espm_status
+X_F32, X_BF16, X_U8, X_ELL = (_E["ESPM_X_" + n] for n in ("F32", "BF16", "U8", "ELL"))
 F64_X_U8, F64_X_BF16, F64_X_F32, F64_X_F64 = (_D["ESPM_F64_X_" + n] for n in ("U8", "BF16", "F32", "F64"))
 F64_MAX_K, F64_MAXIT = _D["ESPM_F64_MAX_K"], _D["ESPM_F64_MAXIT"]
 F64S_MAX_COUNT, F64S_MAX_N, F64S_WBLOCK = _D["ESPM_F64S_MAX_COUNT"], _D["ESPM_F64S_MAX_N"], _D["ESPM_F64S_WBLOCK"]
@@ -33,8 +35,8 @@ BIN_BLOCK, BIN_PARTS = _D["ESPM_BIN_BLOCK"], _D["ESPM_BIN_PARTS"]
 SPLIT_BLOCK, SPLIT_HEAVY, SPLIT_MAX_K = _D["ESPM_SPLIT_BLOCK"], _D["ESPM_SPLIT_HEAVY"], _D["ESPM_SPLIT_MAX_K"]
 SAMPLE_BLOCK, SAMPLE_HEAVY, SAMPLE_MAX_RATE, SAMPLE_MAX_K = (_D["ESPM_SAMPLE_" + n] for n in ("BLOCK", "HEAVY", "MAX_RATE", "MAX_K"))
 ATTRIB_BLOCK, ATTRIB_PCHUNK, ATTRIB_WALK, ATTRIB_HEAVY, ATTRIB_MAX_K = (_D["ESPM_ATTRIB_" + n] for n in ("BLOCK", "PCHUNK", "WALK", "HEAVY", "MAX_K"))
-SRC_F32, SRC_F64 = 0, 1
-LAYOUT_CM, LAYOUT_PM = 0, 1
+SRC_F32, SRC_F64 = _E["ESPM_SRC_F32"], _E["ESPM_SRC_F64"]
+LAYOUT_CM, LAYOUT_PM = _E["ESPM_LAYOUT_CM"], _E["ESPM_LAYOUT_PM"]
 ABI_VERSION = _D["ESPM_MU_ABI_VERSION"]
 XCHG_HANDLE_BYTES = _D["ESPM_XCHG_HANDLE_BYTES"]
 ELL_TILE, ELL_PB, ELL_PBITS, ELL_LDS_MAX = _D["ESPM_ELL_TILE"], _D["ESPM_ELL_PB"], _D["ESPM_ELL_PBITS"], _D["ESPM_ELL_LDS_MAX"]
@@ -45,8 +47,8 @@ ELL_HEAVY_MIN, ELL_HEAVY_MAX = _D["ESPM_ELL_HEAVY_MIN"], _D["ESPM_ELL_HEAVY_MAX"
 ELL_UNIT_ROWS, ELL_UNIT_MAX_N, ELL_PAIR_MAX_K = _D["ESPM_ELL_UNIT_ROWS"], _D["ESPM_ELL_UNIT_MAX_N"], _D["ESPM_ELL_PAIR_MAX_K"]
 KP, PPAD, NPAD = _D["ESPM_KP"], _D["ESPM_PPAD"], _D["ESPM_NPAD"]         # (the default build; `variant(k)` below for the wide one)
 MAX_K = KP
-HP_STRIDE, HS_STRIDE, HI_STRIDE = 8 + 2 * KP, 2 * KP, _D["ESPM_HI_STRIDE"]
-HS_ROWSUM, HS_MAX = 0, KP
+HP_STRIDE, HS_STRIDE, HI_STRIDE = _D["ESPM_HP_STRIDE"], _D["ESPM_HS_STRIDE"], _D["ESPM_HI_STRIDE"]
+HS_ROWSUM, HS_MAX = _D["ESPM_HS_ROWSUM"], _D["ESPM_HS_MAX"]
 WIDE_MAX_K = 16      # libespm_mu_wide.so: 9..16 components (and the sparse count store's limit)
 WIDEST_MAX_K = 32    # libespm_mu_wide32.so: 17..32 components, dense stores only
 TAIL_DEFER, TAIL_RIDE = _D["ESPM_TAIL_DEFER"], _D["ESPM_TAIL_RIDE"]
@@ -62,8 +64,6 @@ def w_form_detail(detail):
         return {}
     return dict(threads=detail & 0xfff, rows=(detail >> 12) & 0xf, channels=(detail >> 16) & 0xf, gta_all_threads=bool((detail >> 20) & 1))
 
-_vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-
 
 class MUState(C.Structure):
     """struct espm_mu_state: fields, order and types parsed from include/espm_mu.h.  A fresh instance carries
@@ -76,118 +76,9 @@ class MUState(C.Structure):
         self.abi_version = ABI_VERSION
 
 
-# every symbol include/espm_mu.h declares: name -> (restype, argtypes)
+# every function include/espm_mu.h declares: name -> (restype, argtypes), read from its declaration once per process
 _SP = C.POINTER(MUState)
-SYMBOLS = {
-    "espm_mu_version": (C.c_char_p, []),
-    "espm_mu_last_error": (C.c_char_p, []),
-    "espm_mu_state_size": (C.c_size_t, []),
-    "espm_mu_abi_version": (C.c_int, []),
-    "espm_mu_state_layout": (C.c_char_p, []),
-    "espm_mu_query": (C.c_int, [_SP]),
-    "espm_mu_w_update_is_local": (C.c_int, [_SP]),
-    "espm_mu_w_update_form": (C.c_int, [_SP, C.POINTER(C.c_int)]),
-    "espm_mu_w_update_tail": (C.c_int, [_SP, C.c_int, C.c_int, _vp]),
-    "espm_mu_pack_x": (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
-    "espm_mu_ell_count": (C.c_int, [_SP, _vp, _vp, _vp, _vp, _vp]),
-    "espm_mu_ell_block_counts": (C.c_int, [_SP, _vp, _vp, _vp]),
-    "espm_mu_ell_count_hist": (C.c_int, [_SP, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "espm_mu_ell_fill_hist": (C.c_int, [_SP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "espm_mu_ell_plan": (C.c_int, [_SP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "espm_mu_ell_fill": (C.c_int, [_SP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "espm_mu_ell_heavy_count": (C.c_int, [_SP, _vp, C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp]),
-    "espm_mu_ell_heavy_fill": (C.c_int, [_SP, _vp, C.c_int, C.c_int, _i64, _vp, _vp, _vp]),
-    "espm_mu_hstat": (C.c_int, [_SP, C.c_int, _vp]),
-    "espm_mu_build_gw": (C.c_int, [_SP, C.c_int, _vp]),
-    "espm_mu_step_h": (C.c_int, [_SP, C.c_int, C.c_int, _vp]),
-    "espm_mu_h_finalize": (C.c_int, [_SP, C.c_int, C.c_int, _vp]),
-    "espm_mu_loss_only": (C.c_int, [_SP, C.c_int, C.c_int, _vp]),
-    "espm_mu_w_accum": (C.c_int, [_SP, _vp]),
-    "espm_mu_step_hw": (C.c_int, [_SP, C.c_int, _vp]),
-    "espm_mu_fused_applies": (C.c_int, [_SP]),
-    "espm_mu_w_reduce": (C.c_int, [_SP, _vp]),
-    "espm_mu_w_reduce_finalize": (C.c_int, [_SP, C.c_int, C.c_int, _vp]),
-    "espm_mu_w_finish": (C.c_int, [_SP, C.c_int, C.c_int, C.c_int, _vp]),
-    "espm_mu_iterate_timed": (C.c_int, [_SP, C.c_int, _vp, _vp, _vp]),
-    "espm_mu_iterate": (C.c_int, [_SP, C.c_int, C.c_int, _vp]),
-    "espm_mu_iterate_h": (C.c_int, [_SP, C.c_int, C.c_int, _vp]),
-    "espm_mu_h_chain_applies": (C.c_int, [_SP]),
-    "espm_mu_shard_record_bytes": (C.c_size_t, [_SP]),
-    "espm_mu_shard_pack": (C.c_int, [_SP, C.c_int, _vp, _vp]),
-    "espm_mu_shard_combine": (C.c_int, [_SP, _vp, C.c_int, C.c_int, _vp]),
-    "espm_mu_shard_combine_finish": (C.c_int, [_SP, _vp, C.c_int, C.c_int, C.c_int, _vp]),
-    "espm_mu_w_reduce_finish": (C.c_int, [_SP, C.c_int, C.c_int, C.c_int, _vp]),
-    "espm_mu_w_reduce_pack": (C.c_int, [_SP, C.c_int, C.c_int, _vp, _vp]),
-    "espm_xchg_create": (C.c_int, [C.c_int, C.c_int, C.c_size_t, C.POINTER(_vp)]),
-    "espm_xchg_handle": (C.c_int, [_vp, _vp]),
-    "espm_xchg_connect": (C.c_int, [_vp, _vp]),
-    "espm_xchg_staging": (_vp, [_vp]),
-    "espm_xchg_records": (_vp, [_vp, C.c_int]),
-    "espm_xchg_post": (C.c_int, [_vp, C.c_uint32, _vp]),
-    "espm_xchg_wait": (C.c_int, [_vp, C.c_uint32, _vp]),
-    "espm_xchg_timeouts": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
-    "espm_xchg_set_order": (C.c_int, [_vp, C.c_int]),
-    "espm_xchg_order": (C.c_int, [_vp]),
-    "espm_xchg_destroy": (C.c_int, [_vp]),
-    "espm_mu_shard_exchange_finish": (C.c_int, [_SP, _vp, C.c_uint32, C.c_int, C.c_int, _vp]),
-    "espm_mu_iterate_sharded": (C.c_int, [_SP, _vp, C.POINTER(C.c_uint32), C.c_int, C.c_int, _vp]),
-    "espm_mu_linesearch_terms": (C.c_int, [_SP, C.c_int, C.c_int, _vp, _vp]),
-    "espm_mu_linesearch_terms_sharded": (C.c_int, [_SP, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
-    "espm_surrogate_terms": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]),
-    "espm_dichotomy_simplex_acc": (C.c_int, [C.c_double, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp]),
-    "espm_dichotomy_simplex_pg": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _vp, _vp]),
-    "espm_mu_l2_step_h": (C.c_int, [_SP, C.c_int, _vp, _vp, C.c_int, _vp]),
-    "espm_mu_l2_step_w": (C.c_int, [_SP, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
-    "espm_mu_l2_w_partials": (C.c_int, [_SP, _vp, _vp, C.c_int, _vp]),
-    "espm_mu_l2_w_finish": (C.c_int, [_SP, C.c_int, _vp, _vp, _vp]),
-    "espm_simplex_root_f32": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
-    "espm_dichotomy_simplex": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp]),
-    "espm_mu_laplacian": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _i64, _vp, _vp]),
-    "espm_lu_pl_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "espm_lu_pl": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _i64, _vp, _vp, C.c_size_t, _vp]),
-    # fp64 mode (csrc/mu_fp64.hip): kernels in the narrow build, stubs returning ESPM_EUNSUPPORTED in the wide ones
-    "espm_f64_scratch_doubles": (_i64, [C.c_int, C.c_int, C.c_int, _i64]),
-    "espm_f64_gw": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp]),
-    "espm_f64_hstat": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp]),
-    "espm_f64_h_pass": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_double,
-                                  C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "espm_f64_bisect": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp]),
-    "espm_f64_rel": (C.c_int, [_vp, _vp, _i64, C.c_double, _vp, _vp, _vp]),
-    "espm_f64_w_accum": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp]),
-    "espm_f64_w_finish": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_double, C.c_double,
-                                    C.c_int, _vp, _vp, _vp, _vp]),
-    # fp64 mode on the sparse store (csrc/mu_fp64_sparse.hip)
-    "espm_f64_sparse_scratch_doubles": (_i64, [C.c_int, C.c_int, C.c_int]),
-    "espm_f64_sparse_h_pass": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp,
-                                         C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _vp, _vp, _vp,
-                                         _vp, _vp, _vp]),
-    "espm_f64_sparse_w_accum": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp, C.c_int, C.c_double, _vp, _vp,
-                                          _vp]),
-    # pixel diagnostics (csrc/mu_diag.hip): narrow build only, plain device pointers
-    "espm_pixel_diagnostics": (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_double, C.c_int, _vp, _vp,
-                                         _vp, _vp]),
-    # channel diagnostics (csrc/mu_diag_chan.hip): narrow build only, plain device pointers
-    "espm_channel_diagnostics": (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp,
-                                           _vp, C.c_size_t, _vp]),
-    "espm_channel_diagnostics_scratch": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    # pixel binning (csrc/mu_binning.hip): narrow build only, plain device pointers (the candidate bins: a host array of int32 pairs)
-    "espm_rebin_pixels": (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _i64, _vp]),
-    "espm_binning_sums": (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp]),
-    "espm_binning_sums_scratch": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    # count splitting (csrc/mu_split.hip): narrow build only, plain device pointers
-    "espm_thin_counts": (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int, _i64, _i64, _i64, C.c_uint64, _vp, _vp, _i64, _vp]),
-    "espm_split_deviance": (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int, _i64, _i64, _i64, C.c_uint64, _vp, _vp, C.c_int, C.c_double,
-                                      _vp, _vp, _vp, _vp]),
-    # Poisson sampling (csrc/mu_sample.hip): narrow build only, plain device pointers
-    "espm_poisson_sample": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _i64, _i64, C.c_uint64, _i64, _vp, C.c_int, C.c_int, _i64, _vp, _vp]),
-    "espm_sample_deviance": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _i64, _i64, C.c_uint64, _i64, C.c_int, C.c_double, _vp, _vp]),
-    # count attribution (csrc/mu_attrib.hip): narrow build only, plain device pointers
-    "espm_attribute_expected": (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp,
-                                          C.c_size_t, _vp]),
-    "espm_attribute_expected_scratch": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "espm_assign_counts": (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int, _i64, _i64, _vp, _vp, C.c_int, C.c_uint64, _vp, _i64, _i64,
-                                     _vp, _vp]),
-}
+SYMBOLS = _abi.parse_prototypes(_HEADER_TEXT, _SP)
 
 
 class EspmError(RuntimeError):
@@ -242,7 +133,8 @@ class Variant:
 
     def __init__(self, handle, kp, min_k, max_k):
         self.lib, self.KP, self.MIN_K, self.MAX_K = handle, kp, min_k, max_k
-        self.HP_STRIDE, self.HS_STRIDE, self.HS_MAX = 8 + 2 * kp, 2 * kp, kp
+        d = _abi.parse_defines(_HEADER_TEXT, predefined={"ESPM_KP": kp})   # the header as this build's -DESPM_KP compiled it
+        self.HP_STRIDE, self.HS_STRIDE, self.HS_MAX = d["ESPM_HP_STRIDE"], d["ESPM_HS_STRIDE"], d["ESPM_HS_MAX"]
 
     def check(self, rc):
         check(rc, self.lib)

@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+from abi_header import CTYPE, _declared
 import attribution_reference as ar
 import splitting_reference as sr
 
@@ -163,21 +164,6 @@ def test_explained_intensity_against_the_triple_loop_and_the_reference(lib):
 
 
 # ---- the binding ----------------------------------------------------------------------------------------------------------------------------
-def _declared(name):
-    """The parameter list of ``name`` in include/espm_mu.h, as a list of C types."""
-    import re
-
-    from espm_amd import _abi
-    text = re.sub(r"/\*.*?\*/", "", _abi.header_text(), flags=re.S)
-    m = re.search(r"^(\w[\w \*]*?) *\b" + name + r"\s*\(([^)]*)\)\s*;", text, flags=re.M)
-    assert m, name
-    return m.group(1).strip(), [" ".join(a.split()[:-1]) + ("*" if a.split()[-1].startswith("*") else "") for a in m.group(2).split(",")]
-
-
-CTYPE = {"const void*": C.c_void_p, "void*": C.c_void_p, "double*": C.c_void_p, "const double*": C.c_void_p, "int64_t*": C.c_void_p,
-         "int": C.c_int, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "double": C.c_double, "size_t": C.c_size_t, "espm_stream_t": C.c_void_p}
-
-
 @pytest.mark.parametrize("name", ["espm_attribute_expected", "espm_attribute_expected_scratch", "espm_assign_counts"])
 def test_symbols_are_bound_with_the_headers_signatures(lib, name):
     res, args = lib.SYMBOLS[name]

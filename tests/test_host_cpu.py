@@ -9,6 +9,7 @@ import re
 import numpy as np
 import pytest
 
+import abi_header
 from oracle import mu_oracle as oc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,6 +48,19 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
     assert widest.lib.espm_mu_state_size() == lib.lib.espm_mu_state_size()
     with pytest.raises(NotImplementedError):
         lib.variant(33)
+
+
+@pytest.mark.parametrize("name", abi_header.declared_functions())
+def test_every_declared_function_is_bound_with_the_headers_signature(lib, name):
+    """The binding derives its prototypes from the header (espm_amd/_abi.py: parse_prototypes); the tests' own reading of the same
+    declarations (tests/abi_header.py) must give the same return type, argument count and type of every argument."""
+    res, args = lib.SYMBOLS[name]
+    want_res, want_args = abi_header.signature(name, lib._SP)
+    assert res is want_res
+    assert len(args) == len(want_args)
+    for i, (have, want) in enumerate(zip(args, want_args)):
+        assert have is want, f"argument {i} of {name}"
+    assert len(lib.SYMBOLS) == len(abi_header.declared_functions()) == len(_declared_functions())
 
 
 def test_header_constants_and_struct_match_ctypes(lib):

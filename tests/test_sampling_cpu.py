@@ -1,11 +1,11 @@
 """Poisson sampling without a device: the table of the unit draw re-derived, the rule in numpy (tests/sampling_reference.py) as a
 Poisson sampler, ``calibrate`` against hand-computed values, the binding, and what ``sample``, ``null_deviance`` and the estimator's
 ``simulate`` / ``calibrate_deviance`` / ``bootstrap`` refuse before anything is uploaded."""
-import ctypes as C
 
 import numpy as np
 import pytest
 
+from abi_header import CTYPE, _declared
 import sampling_reference as sref
 import splitting_reference as sr
 
@@ -149,20 +149,6 @@ def test_calibrate_against_hand_computed_values(lib):
 
 
 # ---- the binding ------------------------------------------------------------------------------------------------------------------------
-def _declared(name):
-    import re
-
-    from espm_amd import _abi
-    text = re.sub(r"/\*.*?\*/", "", _abi.header_text(), flags=re.S)
-    m = re.search(r"^(\w[\w \*]*?) *\b" + name + r"\s*\(([^)]*)\)\s*;", text, flags=re.M)
-    assert m, name
-    return m.group(1).strip(), [" ".join(a.split()[:-1]) + ("*" if a.split()[-1].startswith("*") else "") for a in m.group(2).split(",")]
-
-
-CTYPE = {"const void*": C.c_void_p, "void*": C.c_void_p, "double*": C.c_void_p, "const double*": C.c_void_p, "int64_t*": C.c_void_p,
-         "int": C.c_int, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "double": C.c_double, "espm_stream_t": C.c_void_p}
-
-
 @pytest.mark.parametrize("name", ["espm_poisson_sample", "espm_sample_deviance"])
 def test_symbols_are_bound_with_the_headers_signatures(lib, name):
     res, args = lib.SYMBOLS[name]

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from abi_header import CTYPE, _declared
 import splitting_reference as sr
 
 
@@ -118,21 +119,6 @@ def test_reference_deviances():
 
 
 # ---- the binding ----------------------------------------------------------------------------------------------------------------------
-def _declared(name):
-    """The parameter list of ``name`` in include/espm_mu.h, as a list of C types."""
-    import re
-
-    from espm_amd import _abi
-    text = re.sub(r"/\*.*?\*/", "", _abi.header_text(), flags=re.S)
-    m = re.search(r"^(\w[\w \*]*?) *\b" + name + r"\s*\(([^)]*)\)\s*;", text, flags=re.M)
-    assert m, name
-    return m.group(1).strip(), [" ".join(a.split()[:-1]) + ("*" if a.split()[-1].startswith("*") else "") for a in m.group(2).split(",")]
-
-
-CTYPE = {"const void*": C.c_void_p, "void*": C.c_void_p, "double*": C.c_void_p, "const double*": C.c_void_p, "int64_t*": C.c_void_p,
-         "int": C.c_int, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "double": C.c_double, "espm_stream_t": C.c_void_p}
-
-
 @pytest.mark.parametrize("name", ["espm_thin_counts", "espm_split_deviance"])
 def test_symbols_are_bound_with_the_headers_signatures(lib, name):
     res, args = lib.SYMBOLS[name]
