@@ -35,6 +35,8 @@ BIN_BLOCK, BIN_PARTS = _D["ESPM_BIN_BLOCK"], _D["ESPM_BIN_PARTS"]
 SPLIT_BLOCK, SPLIT_HEAVY, SPLIT_MAX_K = _D["ESPM_SPLIT_BLOCK"], _D["ESPM_SPLIT_HEAVY"], _D["ESPM_SPLIT_MAX_K"]
 SAMPLE_BLOCK, SAMPLE_HEAVY, SAMPLE_MAX_RATE, SAMPLE_MAX_K = (_D["ESPM_SAMPLE_" + n] for n in ("BLOCK", "HEAVY", "MAX_RATE", "MAX_K"))
 ATTRIB_BLOCK, ATTRIB_PCHUNK, ATTRIB_WALK, ATTRIB_HEAVY, ATTRIB_MAX_K = (_D["ESPM_ATTRIB_" + n] for n in ("BLOCK", "PCHUNK", "WALK", "HEAVY", "MAX_K"))
+MARG_MAX_G, MARG_MAX_K, MARG_BLOCK, MARG_PCHUNK = (_D["ESPM_MARG_" + n] for n in ("MAX_G", "MAX_K", "BLOCK", "PCHUNK"))
+MARG_PIXELS, MARG_CHANNELS = _E["ESPM_MARG_PIXELS"], _E["ESPM_MARG_CHANNELS"]
 SRC_F32, SRC_F64 = _E["ESPM_SRC_F32"], _E["ESPM_SRC_F64"]
 LAYOUT_CM, LAYOUT_PM = _E["ESPM_LAYOUT_CM"], _E["ESPM_LAYOUT_PM"]
 ABI_VERSION = _D["ESPM_MU_ABI_VERSION"]

@@ -1,4 +1,4 @@
-// What the passes over a count image share (mu_diag.hip, mu_diag_chan.hip, mu_split.hip, mu_sample.hip, mu_attrib.hip): the pieces of
+// What the passes over a count image share (mu_diag.hip, mu_diag_chan.hip, mu_split.hip, mu_sample.hip, mu_attrib.hip, mu_marginals.hip): the pieces of
 // the rules of include/espm_mu.h that are defined bit for bit, the walk of "a lane owns one index, a thread walks the other", and the
 // host side's checks and dispatch.  ONE copy of each: a changed Philox constant, a wrong broadcast of e's high word or a tile index off
 // by one still gives plausible counts.  DESIGN.md ("the image-pass header") lists what lives here and what deliberately does not.
@@ -70,6 +70,25 @@ __device__ __forceinline__ void stage(double* ds, const Vec& v, IT w0, int wn, i
     const int w = i / KP, j = i % KP;
     ds[i] = j < k ? v.ptr[(int64_t)(w0 + w) * v.qs + (int64_t)j * v.cs] : 0.0;
   }
+}
+
+// a round of BT walk indices, every thread its OWN index w0 + threadIdx.x: that index's vector into ds[threadIdx.x * KP ..], zeros beyond
+// k and beyond wn.  The KP loads of a thread are independent and, where qs == 1 (h, or weights that run along the walk), those of one
+// component are consecutive over the threads - where `stage` would walk such a vector KP rows at a time.  Returns whether any component
+// of the thread's vector is not 0 (margk: the walk indices that carry a weight).
+template <int KP, int BT, typename IT>
+__device__ __forceinline__ bool stage_own(double* ds, const Vec& v, IT w0, int wn, int k) {
+  const bool in = (int)threadIdx.x < wn;
+  double c[KP];
+#pragma unroll
+  for (int j = 0; j < KP; ++j) c[j] = in && j < k ? v.ptr[(int64_t)(w0 + threadIdx.x) * v.qs + (int64_t)j * v.cs] : 0.0;
+  bool any = false;
+#pragma unroll
+  for (int j = 0; j < KP; ++j) {
+    ds[threadIdx.x * KP + j] = c[j];
+    any |= c[j] != 0.0;
+  }
+  return any;
 }
 
 // The transposing tile of the layout whose rows run along the walk: tile_rows<XT>() walk indices of BT lanes (u8: 16 KB, the others

@@ -1,7 +1,7 @@
 """What an estimator does with a fit besides fitting (no reference analogue; ``NMFEstimator`` inherits the mixin): the fits around
 ``fit_transform`` - on the binned image, on a thinned image - and the analyses of a fitted model - diagnostics, count attribution,
-draws from the model.  Each method prepares host arrays and hands them to ``espm_amd.binning``, ``splitting``, ``measures``,
-``attribution`` or ``sampling``, imported when it is called; the set-up they share stands once, ahead of them.  The fit itself, ``unmix``
+line maps and region spectra, draws from the model.  Each method prepares host arrays and hands them to ``espm_amd.binning``,
+``splitting``, ``measures``, ``attribution``, ``marginals`` or ``sampling``, imported when it is called; the set-up they share stands once, ahead of them.  The fit itself, ``unmix``
 and the engine plumbing are next door in base.py.
 """
 from __future__ import annotations
@@ -317,6 +317,68 @@ class _FitAnalysis:
             warnings.warn(f"assign_counts: {info['invalid']} non-zero entries have no valid modelled rate (not finite, or not above 0): "
                           "their counts are in the first component's image", RuntimeWarning, stacklevel=2)
         return parts
+
+    # ---- line maps and region spectra: weighted sums of X and of the fitted model along one axis ------------------------------------
+    def line_maps(self, lines, X=None):
+        """Elemental line maps next to what the fit says about them (``espm_amd.marginals.line_maps`` on ``G_ @ W_`` and ``H_``):
+        the counts in an energy window around an X-ray line, less a background interpolated between two side windows, with a Poisson
+        error bar - exspy's ``get_lines_intensity``, on the channel windows the reference's own workflow is built on
+        (``select_background_windows``, eds_spim.py:364-384) - and the modelled line with every component's share of it.
+
+        ``lines``: a list of ``(integration, background)`` in half-open ranges of channel indices, ``background`` None or
+        ``((l0, l1), (r0, r1))`` - ``marginals.line_weights`` has the rule.  Sets ``lines_`` (g, n): the weight vectors;
+        ``line_net_`` (g, p): the measured net counts; ``line_net_std_`` (g, p): sqrt(sum u^2 x); ``line_model_`` (g, p):
+        (U G_ W_) H_; ``line_components_`` (g, k, p): component i's share (U G_ W_)_qi H_ij.  Returns them as a dict (``lines``,
+        ``net``, ``net_std``, ``model_net``, ``components``), the maps always (., p) whatever ``hspy_comp``.
+
+        ``X`` as for ``pixel_diagnostics``: the fitted image in counts, (channels, pixels), or (pixels, channels) with ``hspy_comp``;
+        ``X=None`` takes the fit's ``X_`` un-scaled, with the cost and the ``log_shift`` fill described there.  One pass over the
+        lines' channels of X in fp64 on the current device, the model terms on the host: any number of components, every precision
+        mode, ``shard()``ed estimators (every rank computes everything on its own device)."""
+        from espm_amd import marginals
+        check_is_fitted(self, "W_")
+        X, layout = self._image_argument(X, "line_maps")
+        D, H = self._model_counts()
+        out = marginals.line_maps(X, lines, D, H, layout=layout)
+        self.lines_, self.line_net_, self.line_net_std_ = out["weights"], out["net"], out["net_std"]
+        self.line_model_, self.line_components_ = out["model_net"], out["components"]
+        return dict(lines=self.lines_, net=self.line_net_, net_std=self.line_net_std_, model_net=self.line_model_,
+                    components=self.line_components_)
+
+    def region_spectra(self, regions, X=None):
+        """The spectrum of every region of the image - measured, modelled and residual (``espm_amd.marginals.channel_spectra`` on
+        ``G_ @ W_`` and ``H_``): what ``spectral_diagnostics`` gives for the whole image, per phase, where a residual peak that lives
+        in one phase is not diluted by all the other pixels.
+
+        ``regions``: an integer label map of the p pixels (any shape; negative labels belong to no region - e.g.
+        ``H_.argmax(axis=0)``), or floating-point weights (L, p) (e.g. ``H_ / H_.sum(0)``: abundances as soft masks).  Sets
+        ``region_counts_``, ``region_model_`` and ``region_deviance_``, each (n, L): sum_j v_j x, sum_j v_j Y and
+        2 sum_j v_j (x ln(x / Y) - x + Y) with Y = max(G_ W_ H_, log_shift); and ``region_pixels_`` (L,): the sum of every
+        region's weights (its number of pixels).  Returns them as a dict (``counts``, ``model``, ``deviance``, ``pixels``).
+
+        ``X`` as for ``pixel_diagnostics``.  Computed in fp64 whatever the estimator's precision, on the current device (a
+        ``shard()``ed estimator: every rank computes everything on its own device).  More than 8 components raise
+        NotImplementedError, labels or weights that do not match the pixels ValueError - before anything is uploaded."""
+        from espm_amd import marginals
+        check_is_fitted(self, "W_")
+        k, p = int(self.H_.shape[0]), int(self.H_.shape[1])
+        if k > marginals.MAX_K:
+            raise NotImplementedError(f"region_spectra: {k} components (the kernels are built for 1..{marginals.MAX_K})")
+        R = np.asarray(regions)
+        if R.dtype.kind in "iub":
+            if R.size != p:
+                raise ValueError(f"region_spectra: a label map of {R.size} pixels, the fitted H_ has {p}")
+            V = marginals.label_weights(R)
+        else:
+            V = np.asarray(R, dtype=np.float64)
+            if V.ndim != 2 or V.shape[1] != p:
+                raise ValueError(f"region_spectra: weights of shape {V.shape}, the fitted H_ has {p} pixels (weights are (regions, {p}))")
+        X, layout = self._image_argument(X, "region_spectra")
+        D, H = self._model_counts()
+        out = marginals.channel_spectra(X, V, D, H, log_shift=self.log_shift, layout=layout)
+        self.region_counts_, self.region_model_, self.region_deviance_ = out["counts"], out["model"], out["deviance"]
+        self.region_pixels_ = V.sum(axis=1)
+        return dict(counts=self.region_counts_, model=self.region_model_, deviance=self.region_deviance_, pixels=self.region_pixels_)
 
     # ---- draws from the fitted model: a simulated image, a scale for the deviance map, the parametric bootstrap -------------------
     def _sampling_model(self, who):

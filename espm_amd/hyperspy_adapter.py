@@ -28,6 +28,10 @@ What is here:
   (``NMFEstimator.fit_split``).
 * ``SpectrumImage.simulate(est, seed, replicate)`` (``espm_amd.sampling``: a count image drawn from the fitted model),
   ``calibrated_deviance_maps(est)`` and ``bootstrap_maps(est)``: the maps of ``NMFEstimator.calibrate_deviance`` / ``bootstrap``.
+* ``SpectrumImage.line_maps(lines)`` / ``.region_spectra(labels)`` (``espm_amd.marginals``: background-corrected line maps with their
+  Poisson error bars and the sum spectrum of every region of a label map, from the raw cube; windows in channel indices) and
+  ``line_maps(est)`` / ``region_spectra(est)``: the results of ``NMFEstimator.line_maps`` / ``region_spectra`` in the navigation
+  and the signal shape.
 * ``hyperspy_extension.yaml`` (next to this file) and the ``hyperspy.extensions`` entry point in ``pyproject.toml`` declare
   the signal type ``EDS_espm_amd`` -> ``EDSespmAMD`` below, defined only when hyperspy imports.
 """
@@ -119,6 +123,25 @@ class SpectrumImage:
             parts = np.ascontiguousarray(parts.transpose(0, 2, 1))
         return [SpectrumImage(part.reshape(self.data.shape)) for part in parts]
 
+    def line_maps(self, lines):
+        """(net (g, ny, nx), net_std (g, ny, nx)) of the raw cube, no estimator needed: the counts in every line's integration window
+        less the background interpolated between its two side windows, and their Poisson standard deviation sqrt(sum u^2 x)
+        (``espm_amd.marginals.line_maps`` on the device).  ``lines``: a list of ``(integration, background)`` in half-open ranges
+        of CHANNEL INDICES, ``background`` None or ``((l0, l1), (r0, r1))`` - ``marginals.line_weights`` has the rule."""
+        from espm_amd import marginals
+        out = marginals.line_maps(self.unfolded(), lines, layout="pm")
+        ny, nx = self.shape_2d
+        return out["net"].reshape((-1, ny, nx)), out["net_std"].reshape((-1, ny, nx))
+
+    def region_spectra(self, labels):
+        """(L, n): the raw sum spectrum of every region of an integer label map (ny, nx) - negative labels belong to no region
+        (``espm_amd.marginals.channel_spectra`` on the device)."""
+        from espm_amd import marginals
+        labels = np.asarray(labels)
+        if labels.shape != self.shape_2d:
+            raise ValueError(f"labels of shape {labels.shape} for an image of {self.shape_2d}")
+        return marginals.channel_spectra(self.unfolded(), marginals.label_weights(labels), layout="pm")["counts"].T
+
     def decomposition(self, algorithm, output_dimension=None, return_info=False, bin=None, split=None, **kwargs):
         """hyperspy's ``decomposition(algorithm=<object>)`` for a custom estimator: ``fit_transform(data (p, n))`` ->
         loadings (p, k), ``components_`` (k, n) -> factors (n, k); the estimator stays in ``learning_results``.  ``bin=(by, bx)``:
@@ -200,6 +223,26 @@ def component_spectra(est):
     if not hasattr(est, "channel_counts_"):
         raise AttributeError("call est.attribute_counts() first: it sets pixel_counts_ and channel_counts_")
     return np.asarray(est.channel_counts_).T
+
+
+def line_maps(est, shape_2d=None):
+    """``est.line_net_``, ``est.line_net_std_``, ``est.line_model_`` as (g, ny, nx) and ``est.line_components_`` as (g, k, ny, nx) (set by
+    ``est.line_maps()``) in the navigation shape, like the loadings: the measured line next to the modelled one and every component's
+    share of it.  ``shape_2d``: the image grid, by default the estimator's."""
+    if not hasattr(est, "line_net_"):
+        raise AttributeError("call est.line_maps() first: it sets line_net_, line_net_std_, line_model_ and line_components_")
+    ny, nx = (int(v) for v in (shape_2d if shape_2d is not None else est.shape_2d))
+    g, k = np.asarray(est.line_components_).shape[:2]
+    return (np.asarray(est.line_net_).reshape((g, ny, nx)), np.asarray(est.line_net_std_).reshape((g, ny, nx)),
+            np.asarray(est.line_model_).reshape((g, ny, nx)), np.asarray(est.line_components_).reshape((g, k, ny, nx)))
+
+
+def region_spectra(est):
+    """``est.region_counts_``, ``est.region_model_`` and ``est.region_deviance_`` as (L, n) (set by ``est.region_spectra()``) on the
+    signal axis, like the factors: the measured, the modelled and the residual spectrum of every region."""
+    if not hasattr(est, "region_counts_"):
+        raise AttributeError("call est.region_spectra() first: it sets region_counts_, region_model_, region_deviance_ and region_pixels_")
+    return np.asarray(est.region_counts_).T, np.asarray(est.region_model_).T, np.asarray(est.region_deviance_).T
 
 
 def diagnostic_spectra(est):

@@ -53,6 +53,9 @@
  *   espm_attribute_expected, espm_assign_counts <- espm/utils.py:396-414 (get_explained_intensity_W, the modelled intensity behind
  *                            every entry of W) for the MEASURED counts: the responsibilities of the components from a pass over X, and
  *                            (new) the image split into k integer images, one per component, that add up to it
+ *   espm_weighted_marginals <- espm/datasets/eds_spim.py:364-384 (the channel windows of select_background_windows, masked_X = curr_X[mask])
+ *                            as weighted sums of X, of the model and of the deviance term along either axis: line maps with a background
+ *                            correction and a Poisson error bar, and the measured, modelled and residual spectrum of a region
  *   espm_lu_pl            <- espm/estimators/updates.py:179 -> scikit-learn's _initialize_nmf -> _randomized_range_finder: the LU
  *                            normaliser of its power iterations (scipy.linalg.lu(A, permute_l=True)[0]) on tall device matrices
  *
@@ -954,6 +957,46 @@ size_t espm_attribute_expected_scratch(int n, int p, int k);
 int espm_assign_counts(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, int64_t p_total, int64_t j0, const double* d,
                        const double* h, int k, uint64_t seed, void* parts, int64_t part_stride, int64_t out_ld, int64_t* counts,
                        espm_stream_t stream);
+
+/* ---- weighted marginals (csrc/mu_marginals.hip; espm_amd.marginals, NMFEstimator.line_maps / region_spectra) ----
+ * Weighted sums of the image, of its model and of the deviance term along one axis, for g weight vectors at once: weights over the
+ * channels give maps (an energy window, a background-corrected line, a top-hat filter), weights over the pixels give spectra (a phase
+ * mask, a label map, abundances used as soft masks).  Plain device pointers, no espm_mu_state; x, x_dtype (ESPM_DIAG_X_*: u8, u16,
+ * f32, f64), x_layout, ld, d (n, k) row-major, h (k, p) and log_shift exactly as for espm_pixel_diagnostics.
+ *   side ESPM_MARG_PIXELS    wgt (g, n) row-major, one weight per channel; xs, ys, dev (g, p): the sums run over the channels
+ *   side ESPM_MARG_CHANNELS  wgt (g, p) row-major, one weight per pixel;   xs, ys, dev (g, n): the sums run over the pixels
+ * THE RULE (the outputs are defined by it), all in fp64.  Per entry (c, j) with the count x:
+ *   y = 0; y = fma(d[c, i], h[i, j], y) for i ascending; Y = fmax(y, log_shift); r = 1.0 / Y; t = Y - x; if x > 0: t = fma(x, log(x * r), t)
+ *   - the term exactly as the diagnostics form it.  Per group q, with w = wgt[q, the entry's summed index]:
+ *   xs_q = fma(w, x, xs_q); ys_q = fma(w, Y, ys_q); dv_q = fma(w, t, dv_q);        the stored dev is 2 dv.
+ * ORDER.  The pixel side adds the channels in ascending order, from 0, in the pixel's own thread.  The channel side adds the pixels
+ * of a chunk of ESPM_MARG_PCHUNK in ascending order, from 0, and writes the partial sums to `scratch` (device memory,
+ * espm_weighted_marginals_scratch(side, n, p, g) bytes: chunks x 3 x g x n doubles, whatever k is; 0 for the pixel side, whose
+ * `scratch` may be NULL); a second launch adds the chunks in ascending order, from 0.  Nothing is accumulated
+ * atomically: two calls give the same bits, and so do the two layouts of one image.  With all weights 1.0 the outputs are bit-equal
+ * to espm_pixel_diagnostics' dev (pixel side) and to espm_channel_diagnostics' dev, xsum, ysum (channel side).
+ * k == 0: no model.  d, h, ys and dev must be NULL; only xs is formed and an entry with x == 0 costs its read only (the raw line maps).
+ * A summed index whose g weights are all 0 is skipped by the whole workgroup without reading x there: a narrow window costs its own
+ * rows, not the whole image.  (Where x's rows run along the summed axis it is read 64, 32 or 16 consecutive indices at a time - one or
+ * two cache lines of a row - and it is such a piece that is skipped when none of its indices has a weight.)  That changes no bit:
+ * fma(0, v, a) == a for finite v, and x, Y and t are finite for finite x since Y >= log_shift > 0.  Non-finite x or weights are the
+ * caller's to refuse.  The side ESPM_MARG_CHANNELS takes at most 65535 * ESPM_MARG_BLOCK channels.
+ * No espm_mu_state is involved and its layout is untouched: ESPM_MU_ABI_VERSION stays (it versions that layout, not the list of entry
+ * points; a binding finds a missing entry point when it resolves the symbol).
+ * ESPM_EINVAL, before the device is touched and with the offending values in the message, for a null pointer, a side, layout or dtype
+ * that does not exist, g outside 1..ESPM_MARG_MAX_G, k outside 0..ESPM_MARG_MAX_K, n or p below 1, ld below the row length, log_shift
+ * not positive where k > 0, model or output pointers inconsistent with k, scratch_bytes below what the query returns (the message names
+ * both sizes).  Only the narrow build has the kernels; the wide builds return ESPM_EUNSUPPORTED, and their query returns 0. */
+#define ESPM_MARG_MAX_G 8       /* weight vectors per call                                                                       */
+#define ESPM_MARG_MAX_K 8       /* components of the model (ESPM_DIAG_MAX_K); 0: no model                                        */
+#define ESPM_MARG_BLOCK 256     /* threads per workgroup: pixels, or channels                                                    */
+#define ESPM_MARG_PCHUNK 2048   /* pixels per workgroup of the channel side: ESPM_CDIAG_PCHUNK                                   */
+enum { ESPM_MARG_PIXELS = 0,    /* weights (g, n) over channels -> outputs (g, p)                                                */
+       ESPM_MARG_CHANNELS = 1 };/* weights (g, p) over pixels   -> outputs (g, n)                                                */
+int espm_weighted_marginals(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, int side, const double* wgt, int g,
+                            const double* d, const double* h, int k, double log_shift, double* xs, double* ys, double* dev, void* scratch,
+                            size_t scratch_bytes, espm_stream_t stream);
+size_t espm_weighted_marginals_scratch(int side, int n, int p, int g);
 
 #ifdef __cplusplus
 }
