@@ -37,7 +37,9 @@ SAMPLE_BLOCK, SAMPLE_HEAVY, SAMPLE_MAX_RATE, SAMPLE_MAX_K = (_D["ESPM_SAMPLE_" +
 ATTRIB_BLOCK, ATTRIB_PCHUNK, ATTRIB_WALK, ATTRIB_HEAVY, ATTRIB_MAX_K = (_D["ESPM_ATTRIB_" + n] for n in ("BLOCK", "PCHUNK", "WALK", "HEAVY", "MAX_K"))
 MARG_MAX_G, MARG_MAX_K, MARG_BLOCK, MARG_PCHUNK = (_D["ESPM_MARG_" + n] for n in ("MAX_G", "MAX_K", "BLOCK", "PCHUNK"))
 MARG_PIXELS, MARG_CHANNELS = _E["ESPM_MARG_PIXELS"], _E["ESPM_MARG_CHANNELS"]
-SRC_F32, SRC_F64 = _E["ESPM_SRC_F32"], _E["ESPM_SRC_F64"]
+RESID_MAX_G, RESID_MAX_K, RESID_BLOCK, RESID_PCHUNK = (_D["ESPM_RESID_" + n] for n in ("MAX_G", "MAX_K", "BLOCK", "PCHUNK"))
+RESID_PIXELS, RESID_CHANNELS = _E["ESPM_RESID_PIXELS"], _E["ESPM_RESID_CHANNELS"]
+SRC_F32, SRC_F64 =_E["ESPM_SRC_F32"], _E["ESPM_SRC_F64"]
 LAYOUT_CM, LAYOUT_PM = _E["ESPM_LAYOUT_CM"], _E["ESPM_LAYOUT_PM"]
 ABI_VERSION = _D["ESPM_MU_ABI_VERSION"]
 XCHG_HANDLE_BYTES = _D["ESPM_XCHG_HANDLE_BYTES"]

@@ -1,4 +1,4 @@
-// What the passes over a count image share (mu_diag.hip, mu_diag_chan.hip, mu_split.hip, mu_sample.hip, mu_attrib.hip, mu_marginals.hip): the pieces of
+// What the passes over a count image share (mu_diag.hip, mu_diag_chan.hip, mu_split.hip, mu_sample.hip, mu_attrib.hip, mu_marginals.hip, mu_residual.hip): the pieces of
 // the rules of include/espm_mu.h that are defined bit for bit, the walk of "a lane owns one index, a thread walks the other", and the
 // host side's checks and dispatch.  ONE copy of each: a changed Philox constant, a wrong broadcast of e's high word or a tile index off
 // by one still gives plausible counts.  DESIGN.md ("the image-pass header") lists what lives here and what deliberately does not.

@@ -1,7 +1,7 @@
 """What an estimator does with a fit besides fitting (no reference analogue; ``NMFEstimator`` inherits the mixin): the fits around
 ``fit_transform`` - on the binned image, on a thinned image - and the analyses of a fitted model - diagnostics, count attribution,
-line maps and region spectra, draws from the model.  Each method prepares host arrays and hands them to ``espm_amd.binning``,
-``splitting``, ``measures``, ``attribution``, ``marginals`` or ``sampling``, imported when it is called; the set-up they share stands once, ahead of them.  The fit itself, ``unmix``
+line maps and region spectra, residual components, draws from the model.  Each method prepares host arrays and hands them to ``espm_amd.binning``,
+``splitting``, ``measures``, ``attribution``, ``marginals``, ``residuals`` or ``sampling``, imported when it is called; the set-up they share stands once, ahead of them.  The fit itself, ``unmix``
 and the engine plumbing are next door in base.py.
 """
 from __future__ import annotations
@@ -379,6 +379,61 @@ class _FitAnalysis:
         self.region_counts_, self.region_model_, self.region_deviance_ = out["counts"], out["model"], out["deviance"]
         self.region_pixels_ = V.sum(axis=1)
         return dict(counts=self.region_counts_, model=self.region_model_, deviance=self.region_deviance_, pixels=self.region_pixels_)
+
+    # ---- what the fit left in the residual: a missing phase, its spectrum and its map ----------------------------------------------
+    def residual_components(self, n_vectors=4, X=None, n_null=0, seed=0):
+        """Is a phase missing, and what does it look like?  The leading singular triplets of the Pearson residual matrix
+        E = (X - Y) / sqrt(Y), Y = G_ W_ H_ (``espm_amd.residuals.svd``; no reference analogue).  For a correct Poisson model E is
+        unit-variance noise and its top singular value sits near ``residual_edge_`` = sqrt(n) + sqrt(p); a missing phase is a value
+        far above that, its left vector the residual spectrum and its right vector the map of where the phase sits - what
+        ``deviance_`` (where the model fails) and ``bootstrap`` (how uncertain it is given that it is right) do not say.
+
+        Sets ``residual_singular_values_`` (r,), ``residual_spectra_`` (n, r) - each with its largest-magnitude entry positive -,
+        ``residual_maps_`` (r, p), ``residual_explained_`` (r,) = s^2 / ``residual_chi2_``, ``residual_chi2_`` (the total Pearson
+        chi^2), ``residual_chi2_map_`` (p,), ``residual_edge_`` and ``residual_unmodelled_`` (entries with counts whose model is below
+        ``log_shift``: they leave E).  Returns them as a dict (keys without the prefix and the underscore, with ``ritz_residuals``,
+        ``n_iter`` and ``converged``); the maps are always (r, p) whatever ``hspy_comp``.  ``residual_spectra_[:, 0]`` clipped at 0 is
+        a natural extra column of W for a refit with one more component.
+
+        ``n_null >= 1``: the honest scale at EDS doses, where e is heavy-tailed and the analytic edge only a guide -
+        ``residuals.null_singular_values``, the top singular value of ``n_null`` replicates (0 .. n_null - 1 under ``seed``) of the
+        fitted model drawn on the device, each against the fitted model.  Sets ``residual_null_`` (n_null,), ``residual_pvalue_`` =
+        (1 + #{null >= s_1}) / (n_null + 1) and ``residual_n_significant_``: the number of leading values above the largest null
+        value.  The null is FRESH data against the generating model, not refitted to every replicate: the residual of the fitted
+        image is in-sample and a fit takes some of the noise with it, so the top value of a right model sits a little BELOW its null
+        and the calibration is conservative - a component flagged here is flagged with room to spare.
+
+        ``n_vectors``: 1 .. 6.  ``X`` as for ``pixel_diagnostics``; ``X=None`` takes the fit's ``X_`` un-scaled, with the cost and the
+        ``log_shift`` fill described there.  Computed in fp64 whatever the estimator's precision, on the current device; 1 .. 8
+        components (NotImplementedError beyond).  Without a null a ``shard()``ed estimator computes everything on every rank's own
+        device; with one the refusals of ``simulate`` apply (``shard()``: NotImplementedError, ``fit_binned``: ValueError) - all
+        before anything is uploaded."""
+        from espm_amd import residuals, sampling
+        from espm_amd.splitting import _check_seed
+        check_is_fitted(self, "W_")
+        k = int(self.H_.shape[0])
+        if k > residuals.MAX_K:
+            raise NotImplementedError(f"residual_components: {k} components (the kernels are built for 1..{residuals.MAX_K})")
+        n, p = int(self.G_.shape[0]), int(self.H_.shape[1])
+        residuals._check_iteration(n_vectors, 1e-10, 60, n, p)
+        if isinstance(n_null, bool) or int(n_null) != n_null or int(n_null) < 0:
+            raise ValueError(f"n_null must be a non-negative integer, not {n_null!r}")
+        n_null, seed = int(n_null), _check_seed(seed)
+        if n_null:
+            self._sampling_model("residual_components")
+            sampling._check_replicate(0, n_null)
+        X, layout = self._image_argument(X, "residual_components")
+        D, H = self._model_counts()
+        out = residuals.svd(X, D, H, n_vectors=n_vectors, log_shift=self.log_shift, layout=layout)
+        self.residual_singular_values_, self.residual_spectra_, self.residual_maps_ = out["singular_values"], out["spectra"], out["maps"]
+        self.residual_explained_, self.residual_chi2_, self.residual_chi2_map_ = out["explained"], out["chi2_total"], out["chi2_map"]
+        self.residual_edge_, self.residual_unmodelled_ = out["edge"], out["unmodelled"]
+        if n_null:
+            null = residuals.null_singular_values(D, H, n_rep=n_null, seed=seed, log_shift=self.log_shift)
+            cal = residuals.calibrate(out["singular_values"], null)
+            self.residual_null_, self.residual_pvalue_, self.residual_n_significant_ = null, cal["pvalue"], cal["n_significant"]
+            out = dict(out, null=null, pvalue=cal["pvalue"], n_significant=cal["n_significant"])
+        return out
 
     # ---- draws from the fitted model: a simulated image, a scale for the deviance map, the parametric bootstrap -------------------
     def _sampling_model(self, who):

@@ -142,6 +142,16 @@ class SpectrumImage:
             raise ValueError(f"labels of shape {labels.shape} for an image of {self.shape_2d}")
         return marginals.channel_spectra(self.unfolded(), marginals.label_weights(labels), layout="pm")["counts"].T
 
+    def scree(self, n_vectors=6):
+        """The scree plot of the raw cube, no estimator needed: ``espm_amd.residuals.scree`` on the device - the singular values of the
+        Pearson residual against the independence model, whose ``normalised_pca`` are the values hyperspy's Poisson-normalised PCA
+        reports after its trivial first one; k phases show as k - 1 values above the bulk.  Returns that function's dict with the
+        ``maps`` as (r, ny, nx) and the ``chi2_map`` as (ny, nx); the ``spectra`` stay (n, r)."""
+        from espm_amd import residuals
+        out = residuals.scree(self.unfolded(), n_vectors=n_vectors, layout="pm")
+        ny, nx = self.shape_2d
+        return dict(out, maps=out["maps"].reshape((-1, ny, nx)), chi2_map=out["chi2_map"].reshape((ny, nx)))
+
     def decomposition(self, algorithm, output_dimension=None, return_info=False, bin=None, split=None, **kwargs):
         """hyperspy's ``decomposition(algorithm=<object>)`` for a custom estimator: ``fit_transform(data (p, n))`` ->
         loadings (p, k), ``components_`` (k, n) -> factors (n, k); the estimator stays in ``learning_results``.  ``bin=(by, bx)``:
@@ -243,6 +253,16 @@ def region_spectra(est):
     if not hasattr(est, "region_counts_"):
         raise AttributeError("call est.region_spectra() first: it sets region_counts_, region_model_, region_deviance_ and region_pixels_")
     return np.asarray(est.region_counts_).T, np.asarray(est.region_model_).T, np.asarray(est.region_deviance_).T
+
+
+def residual_components(est, shape_2d=None):
+    """``est.residual_maps_`` as (r, ny, nx), in the navigation shape like the loadings, and ``est.residual_spectra_`` as (r, n), on
+    the signal axis like the factors (set by ``est.residual_components()``): where a missing phase sits and what it looks like.
+    ``shape_2d``: the image grid, by default the estimator's."""
+    if not hasattr(est, "residual_maps_"):
+        raise AttributeError("call est.residual_components() first: it sets residual_maps_ and residual_spectra_")
+    ny, nx = (int(v) for v in (shape_2d if shape_2d is not None else est.shape_2d))
+    return np.asarray(est.residual_maps_).reshape((-1, ny, nx)), np.asarray(est.residual_spectra_).T
 
 
 def diagnostic_spectra(est):

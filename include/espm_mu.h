@@ -56,6 +56,9 @@
  *   espm_weighted_marginals <- espm/datasets/eds_spim.py:364-384 (the channel windows of select_background_windows, masked_X = curr_X[mask])
  *                            as weighted sums of X, of the model and of the deviance term along either axis: line maps with a background
  *                            correction and a Poisson error bar, and the measured, modelled and residual spectrum of a region
+ *   espm_residual_products <- (new) the Pearson residual matrix (X - Y) / sqrt(Y) applied to a block of vectors from either side: the
+ *                            pass behind its leading singular triplets (a missing phase) and, against the independence model,
+ *                            hyperspy's Poisson-normalised PCA scree plot; no reference analogue
  *   espm_lu_pl            <- espm/estimators/updates.py:179 -> scikit-learn's _initialize_nmf -> _randomized_range_finder: the LU
  *                            normaliser of its power iterations (scipy.linalg.lu(A, permute_l=True)[0]) on tall device matrices
  *
@@ -997,6 +1000,46 @@ int espm_weighted_marginals(const void* x, int x_dtype, int x_layout, int64_t ld
                             const double* d, const double* h, int k, double log_shift, double* xs, double* ys, double* dev, void* scratch,
                             size_t scratch_bytes, espm_stream_t stream);
 size_t espm_weighted_marginals_scratch(int side, int n, int p, int g);
+
+/* ---- residual products (csrc/mu_residual.hip; espm_amd.residuals, NMFEstimator.residual_components) ----
+ * The Pearson residual matrix E = (X - Y) / sqrt(Y), Y = D H, applied to g dense vectors at once from either side, with the Pearson
+ * chi^2 of every pixel or channel: the pass a subspace iteration for E's leading singular triplets is made of (a missing phase is a
+ * singular value far above sqrt(n) + sqrt(p); against the independence model it is correspondence analysis, hyperspy's
+ * Poisson-normalised PCA).  E is never stored.  Plain device pointers, no espm_mu_state; x, x_dtype (ESPM_DIAG_X_*: u8, u16, f32,
+ * f64), x_layout, ld, d (n, k) row-major and h (k, p) exactly as for espm_weighted_marginals.  A model is required: k = 1..ESPM_RESID_MAX_K.
+ *   side ESPM_RESID_PIXELS    vec (g, n) row-major, one value per channel; out (g, p), out[q, j] = sum_c vec[q, c] e_cj  (E^T U);
+ *                             chi2 (p,) = sum_c e_cj^2
+ *   side ESPM_RESID_CHANNELS  vec (g, p) row-major, one value per pixel;   out (g, n), out[q, c] = sum_j vec[q, j] e_cj  (E V);
+ *                             chi2 (n,) = sum_j e_cj^2
+ * chi2 and unmodelled may each be NULL.
+ * THE RULE (the outputs are defined by it), all in fp64.  Per entry (c, j) with the count x:
+ *   y = 0; y = fma(d[c, i], h[i, j], y) for i ascending; floored = !(y >= log_shift);
+ *   e = floored ? 0.0 : (x - y) / sqrt(y)   - a subtraction, an IEEE square root and an IEEE division, one rounding each (no
+ *   reciprocal square root).  Per vector q, with v = vec[q, the entry's summed index]:  out_q = fma(v, e, out_q);  chi2 = fma(e, e, chi2).
+ * An entry with `floored` and x > 0 adds 1 to *unmodelled (int64, zeroed by the call): counts the model has no rate for
+ * (espm_attribute_expected's unattributed ones).  They leave E: a single one at Y = log_shift would carry e ~ 1e7 and own the whole
+ * decomposition.  The count is a sum of integers - the same in any order - and the call's only atomic.
+ * ORDER, as for the weighted marginals.  The pixel side adds the channels in ascending order, from 0, in the pixel's own thread.  The
+ * channel side adds the pixels of a chunk of ESPM_RESID_PCHUNK in ascending order, from 0, and writes the partial sums to `scratch`
+ * (device memory, espm_residual_products_scratch(side, n, p, g) bytes: chunks x (g + 1) x n doubles; 0 for the pixel side, whose
+ * `scratch` may be NULL); a second launch adds the chunks in ascending order, from 0.  No value is accumulated atomically: two calls
+ * give the same bits, and so do the two layouts of one image.  Non-finite x, vectors or models are the caller's to refuse.
+ * No espm_mu_state is involved: ESPM_MU_ABI_VERSION stays.
+ * ESPM_EINVAL, before the device is touched and with the offending values in the message, for a null pointer, a side, layout or dtype
+ * that does not exist, g outside 1..ESPM_RESID_MAX_G, k outside 1..ESPM_RESID_MAX_K, n or p below 1, ld below the row length, log_shift
+ * not positive, scratch_bytes below what the query returns (the message names both sizes), more than 65535 * ESPM_RESID_BLOCK channels
+ * on the side ESPM_RESID_CHANNELS.  Only the narrow build has the kernels; the wide builds return ESPM_EUNSUPPORTED, and their query
+ * returns 0. */
+#define ESPM_RESID_MAX_G 8       /* vectors per call                                                                              */
+#define ESPM_RESID_MAX_K 8       /* components of the model (ESPM_DIAG_MAX_K)                                                     */
+#define ESPM_RESID_BLOCK 256     /* threads per workgroup: pixels, or channels                                                    */
+#define ESPM_RESID_PCHUNK 2048   /* pixels per workgroup of the channel side: ESPM_MARG_PCHUNK                                    */
+enum { ESPM_RESID_PIXELS = 0,    /* vectors (g, n) over channels -> out (g, p), chi2 (p,)                                         */
+       ESPM_RESID_CHANNELS = 1 };/* vectors (g, p) over pixels   -> out (g, n), chi2 (n,)                                         */
+int espm_residual_products(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, int side, const double* vec, int g,
+                           const double* d, const double* h, int k, double log_shift, double* out, double* chi2, int64_t* unmodelled,
+                           void* scratch, size_t scratch_bytes, espm_stream_t stream);
+size_t espm_residual_products_scratch(int side, int n, int p, int g);
 
 #ifdef __cplusplus
 }
