@@ -39,6 +39,8 @@ MARG_MAX_G, MARG_MAX_K, MARG_BLOCK, MARG_PCHUNK = (_D["ESPM_MARG_" + n] for n in
 MARG_PIXELS, MARG_CHANNELS = _E["ESPM_MARG_PIXELS"], _E["ESPM_MARG_CHANNELS"]
 RESID_MAX_G, RESID_MAX_K, RESID_BLOCK, RESID_PCHUNK = (_D["ESPM_RESID_" + n] for n in ("MAX_G", "MAX_K", "BLOCK", "PCHUNK"))
 RESID_PIXELS, RESID_CHANNELS = _E["ESPM_RESID_PIXELS"], _E["ESPM_RESID_CHANNELS"]
+PML_MAX_K = _D["ESPM_PML_MAX_K"]
+PML_NOT_DONE, PML_UNMODELLED, PML_NONFINITE, PML_COUNTERS = (_E["ESPM_PML_" + n] for n in ("NOT_DONE", "UNMODELLED", "NONFINITE", "COUNTERS"))
 SRC_F32, SRC_F64 =_E["ESPM_SRC_F32"], _E["ESPM_SRC_F64"]
 LAYOUT_CM, LAYOUT_PM = _E["ESPM_LAYOUT_CM"], _E["ESPM_LAYOUT_PM"]
 ABI_VERSION = _D["ESPM_MU_ABI_VERSION"]

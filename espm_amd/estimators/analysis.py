@@ -435,6 +435,48 @@ class _FitAnalysis:
             out = dict(out, null=null, pvalue=cal["pvalue"], n_significant=cal["n_significant"])
         return out
 
+    # ---- is phase j in this pixel at all: per-pixel ML abundances and nested likelihood-ratio tests ---------------------------------
+    def presence_maps(self, X=None, tol=1e-3, max_pass=None):
+        """Is phase j present in this pixel?  ``espm_amd.presence.presence`` on the fitted spectra ``G_ @ W_``, started at ``H_``: the
+        Poisson maximum-likelihood abundances of every pixel given the spectra, and for every component the likelihood ratio between
+        that fit and the pixel's best fit WITHOUT the component - the honest statistic where an abundance sits at or near zero and
+        the Wald bar ``H_std_`` (which ignores active floors) means nothing.  No reference analogue.
+
+        Sets ``H_ml_`` (k, p), oriented as ``H_``; ``deviance_ml_`` (p,); ``presence_lr_`` (k, p) = max(deviance without j -
+        deviance_ml, 0), certified to within ``tol`` on either side; ``presence_pvalue_`` (k, p) = 1/2 erfc(sqrt(lr / 2)), the tail of
+        the boundary mixture 1/2 chi2_0 + 1/2 chi2_1 - asymptotic, a guide at a few tens of counts per pixel -, 1 where lr = 0; and
+        ``ml_converged_`` (bool), ``ml_gap_``, ``ml_n_pass_``, each (k + 1, p): row 0 the full fit, row 1 + j the fit without
+        component j.  Returns dict(H_ml, deviance_ml, lr, pvalue, converged, gap, n_pass, unmodelled, nonfinite); with ``hspy_comp``
+        the returned ``H_ml`` is (p, k), as ``fit_transform`` returns ``H_.T``; the maps stay (k, p).
+
+        The ML is over h >= 0 alone: the regularisers of the fit (``mu``, ``lambda_L``) and ``simplex_H`` are NOT imposed.  A fit
+        without ``simplex_H`` therefore has ``deviance_ml_ <= deviance_`` (+ tol) in every pixel.  Under ``simplex_H`` the per-pixel ML
+        frees the pixel's scale: the fit's model is a sub-model of it, and ``H_ml_.sum(0)`` is a map of the per-pixel dose or thickness
+        that the simplex model cannot express (a simplex-constrained ML is not provided).
+
+        ``tol``: the certified gap, in deviance units, at which a pixel stops; ``max_pass``: the cap of a pixel's EM passes (None:
+        ``presence.MAX_PASS``) - EM takes hundreds of passes, with tails of thousands, and pixels still running at the cap are False in
+        ``ml_converged_``.  ``X`` as for ``pixel_diagnostics``; ``X=None`` takes the fit's ``X_`` un-scaled, with the cost and the
+        ``log_shift`` fill described there (refused after ``fit_binned``).  Computed in fp64 whatever the estimator's precision, on the
+        current device (a ``shard()``ed estimator: every rank computes all pixels on its own device); 1 .. 8 components
+        (NotImplementedError beyond), all before anything is uploaded."""
+        from espm_amd import presence
+        check_is_fitted(self, "W_")
+        k = int(self.H_.shape[0])
+        if k > presence.MAX_K:
+            raise NotImplementedError(f"presence_maps: {k} components (the kernels are built for 1..{presence.MAX_K})")
+        X, layout = self._image_argument(X, "presence_maps")
+        G, W, H = self._model_factors()
+        D = W if G is None else G @ W
+        out = presence.presence(X, D, H, tol=tol, max_pass=presence.MAX_PASS if max_pass is None else max_pass,
+                                log_shift=self.log_shift, layout=layout)
+        self.H_ml_, self.deviance_ml_ = out["H_ml"], out["deviance_ml"]
+        self.presence_lr_, self.presence_pvalue_ = out["lr"], out["pvalue"]
+        self.ml_converged_, self.ml_gap_, self.ml_n_pass_ = out["converged"], out["gap"], out["n_pass"]
+        if self.hspy_comp:
+            out = dict(out, H_ml=out["H_ml"].T)
+        return out
+
     # ---- draws from the fitted model: a simulated image, a scale for the deviance map, the parametric bootstrap -------------------
     def _sampling_model(self, who):
         """(D, H): the fitted model ``G_ @ W_`` (n, k) and ``H_`` (k, p) in counts, in fp64, after the refusals of ``simulate``,

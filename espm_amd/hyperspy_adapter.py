@@ -202,6 +202,16 @@ def diagnostic_maps(est, shape_2d=None):
     return np.asarray(est.deviance_).reshape((ny, nx)), np.asarray(est.H_std_).reshape((-1, ny, nx))
 
 
+def presence_maps(est, shape_2d=None):
+    """``est.H_ml_``, ``est.presence_lr_`` and ``est.presence_pvalue_`` (set by ``est.presence_maps()``) in the navigation shape, like
+    the loadings: (k, ny, nx) each - the per-pixel ML abundances, the likelihood-ratio statistic of every phase's presence and its
+    asymptotic p-value."""
+    if not hasattr(est, "presence_lr_"):
+        raise AttributeError("call est.presence_maps() first: it sets H_ml_, presence_lr_ and presence_pvalue_")
+    ny, nx = (int(v) for v in (shape_2d if shape_2d is not None else est.shape_2d))
+    return tuple(np.asarray(a).reshape((-1, ny, nx)) for a in (est.H_ml_, est.presence_lr_, est.presence_pvalue_))
+
+
 def calibrated_deviance_maps(est, shape_2d=None):
     """``est.deviance_z_`` and ``est.deviance_pvalue_`` (set by ``est.calibrate_deviance()``) in the navigation shape: (ny, nx) each."""
     if not hasattr(est, "deviance_z_"):

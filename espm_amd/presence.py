@@ -1,0 +1,252 @@
+"""Presence maps on the device (csrc/mu_pixel_ml.hip): is phase j in this pixel at all?
+
+At EDS doses of a few tens of counts per pixel most abundances of most phases sit at or near zero, where a Cramer-Rao bar around
+h ~ 0 (``measures.pixel_diagnostics``' ``H_std``, which ignores active floors) means nothing.  The honest statistic at a boundary is
+a likelihood ratio between nested models: the pixel's best Poisson fit with all k spectra against its best fit with spectrum j left
+out.  Both are per-pixel maximum-likelihood problems given the spectra D:
+
+* ``ml_unmix``: the ML abundances of every pixel over a set of components, by EM (the entry point espm_pixel_ml; the rule is in
+  include/espm_mu.h, "pixel ML") - every pixel with a stop of its own and an optimality CERTIFICATE: ``gap`` bounds how far the
+  pixel's deviance is above the minimum over {h >= 0, support in the set}, wherever no entry with counts sits under the floor;
+* ``presence``: the k + 1 nested fits, the likelihood-ratio statistic ``lr`` of every (component, pixel) - certified to within
+  ``tol`` on either side - and its asymptotic p-value under the boundary mixture 1/2 chi2_0 + 1/2 chi2_1.
+
+The ML abundances are also what ``H_std`` is formally a bound for, and with a ``simplex_H`` fit their column sums map the per-pixel
+dose or thickness that the simplex model cannot express.  EM is slow (hundreds of passes, tails of thousands) and cannot fail; the
+kernel runs a bounded number of passes per launch and the loop here reads one integer, the pixels not yet done, between launches.
+fp64 throughout, no float atomics: two calls, both layouts, every dtype that holds the counts and every ``chunk`` give the same bits.
+Everything but the argument checks needs the GPU (there is no CPU path)."""
+from __future__ import annotations
+
+import numpy as np
+
+from espm_amd._image_args import check_layout, image_dims, layout_code
+
+MAX_K = 8            # ESPM_PML_MAX_K: components of the model
+MAX_PASS = 20000     # the default cap of the passes of a pixel
+CHUNK = 64           # passes per launch
+
+
+def _on_device(X):
+    """(Xd, dtype code, device): X on the GPU in a dtype the kernel reads (the marginals' rule)."""
+    from espm_amd import marginals
+    return marginals._on_device(X)
+
+
+def _positive_int(v, name):
+    if isinstance(v, bool) or int(v) != v or int(v) < 1:
+        raise ValueError(f"{name} must be a positive integer, not {v!r}")
+    return int(v)
+
+
+def _components(components, k):
+    """The sorted component set and its bitmask."""
+    if components is None:
+        comp = list(range(k))
+    else:
+        comp = sorted({int(j) for j in components})
+        if len(comp) != len(list(components)) or any(isinstance(j, bool) or int(j) != j for j in components):
+            raise ValueError(f"components must be distinct integers, not {components!r}")
+        if not comp or comp[0] < 0 or comp[-1] >= k:
+            raise ValueError(f"components must be a non-empty subset of 0 .. {k - 1}, not {components!r}")
+    return comp, sum(1 << j for j in comp)
+
+
+class _Solver:
+    """X and the spectra, checked on the host and then uploaded ONCE: every ``run`` is a nested fit on the resident image."""
+
+    def __init__(self, X, D, tol, max_pass, chunk, log_shift, layout, who):
+        from espm_amd import marginals
+        check_layout(layout)
+        if getattr(X, "ndim", None) != 2:
+            X = np.asarray(X)
+        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+            raise ValueError("X must be a non-empty 2-D array or tensor")
+        D = np.ascontiguousarray(D, dtype=np.float64)
+        if D.ndim != 2 or D.size == 0:
+            raise ValueError("D must be (channels, components), not empty")
+        self.n, self.p = image_dims(X.shape, layout)
+        self.k = int(D.shape[1])
+        if D.shape[0] != self.n:
+            raise ValueError(f"X has {self.n} channels, D has {D.shape[0]}")
+        if self.k > MAX_K:
+            raise NotImplementedError(f"{who}: {self.k} components (the kernels are built for 1..{MAX_K})")
+        if not log_shift > 0:
+            raise ValueError("log_shift must be positive")
+        if not tol > 0:
+            raise ValueError("tol must be positive")
+        self.max_pass, self.chunk = _positive_int(max_pass, "max_pass"), _positive_int(chunk, "chunk")
+        if not np.isfinite(D).all() or (D < 0).any():
+            raise ValueError(f"{who}: D must be finite and not negative")
+        self.who, self.layout, self.log_shift, self.tol = who, layout, float(log_shift), float(tol)
+        self.D, self.s = D, np.ascontiguousarray(D.sum(axis=0))
+        self._host = marginals._image(X, who)
+        self.Xd = None
+
+    def check_start(self, H0):
+        if H0 is None:
+            return None
+        H0 = np.ascontiguousarray(H0, dtype=np.float64)
+        if H0.shape != (self.k, self.p):
+            raise ValueError(f"{self.who}: H0 of shape {H0.shape} for {self.k} components and {self.p} pixels")
+        if not np.isfinite(H0).all():
+            raise ValueError(f"{self.who}: H0 holds values that are not finite")
+        return H0
+
+    def check_components(self, components):
+        comp, mask = _components(components, self.k)
+        empty = [j for j in comp if not self.s[j] > 0]
+        if empty:
+            raise ValueError(f"{self.who}: the spectrum of component {empty[0]} is all zero: leave it out of `components`")
+        return comp, mask
+
+    def upload(self):
+        if self.Xd is not None:
+            return
+        import torch
+        self.Xd, self.code, self.dev = _on_device(self._host)
+        self._host = None
+        with torch.cuda.device(self.dev):
+            self.Dd = torch.from_numpy(self.D).to(self.dev)
+
+    def counts(self):
+        """N (p,) on the device: the counts of every pixel (the marginals' pass under all-ones weights: exact for integers)."""
+        import torch
+
+        from espm_amd import marginals
+        N = marginals.pixel_maps(self.Xd, np.ones((1, self.n)), layout=self.layout)["counts"][0]
+        return torch.from_numpy(np.ascontiguousarray(N)).to(self.dev)
+
+    def run(self, start, comp, mask):
+        """One fit over the component set: dict of DEVICE tensors H (k, p), deviance, gap (p,), n_pass (p,) int32, done (p,) uint8 and the
+        ints unmodelled, nonfinite.  ``start``: a device (k, p) float64 tensor (consumed), a checked host array, or None: N / sum_M s."""
+        import ctypes as C
+
+        import torch
+
+        from espm_amd import _lib
+        from espm_amd.engine import _ptr, _stream
+        self.upload()
+        k, p = self.k, self.p
+        with torch.cuda.device(self.dev):
+            if start is None:
+                Hd = torch.zeros((k, p), dtype=torch.float64, device=self.dev)
+                Hd[comp] = (self.counts() / float(self.s[comp].sum()))[None, :]
+            elif isinstance(start, torch.Tensor):
+                Hd = start.contiguous()
+            else:
+                Hd = torch.from_numpy(start).to(self.dev)
+            dv, gp = torch.zeros(p, dtype=torch.float64, device=self.dev), torch.zeros(p, dtype=torch.float64, device=self.dev)
+            passes = torch.zeros(p, dtype=torch.int32, device=self.dev)
+            done = torch.zeros(p, dtype=torch.uint8, device=self.dev)
+            counters = torch.zeros(3, dtype=torch.int64, device=self.dev)
+            s_ptr = self.s.ctypes.data_as(C.c_void_p)
+            issued = 0
+            while issued < self.max_pass:   # bounded launches: no launch's duration depends on the slowest pixel of the image
+                step = min(self.chunk, self.max_pass - issued)
+                _lib.check(_lib.lib.espm_pixel_ml(_ptr(self.Xd), self.code, layout_code(self.layout), int(self.Xd.stride(0)), self.n, p,
+                                                  _ptr(self.Dd), s_ptr, k, mask, self.log_shift, self.tol, step, _ptr(Hd), _ptr(dv), _ptr(gp),
+                                                  _ptr(passes), _ptr(done), _ptr(counters), _stream()))
+                issued += step
+                if int(counters[_lib.PML_NOT_DONE].item()) == 0:   # the one integer read between the chunks
+                    break
+            cnt = counters.cpu().numpy()
+        return dict(H=Hd, deviance=dv, gap=gp, n_pass=passes, done=done, unmodelled=int(cnt[_lib.PML_UNMODELLED]),
+                    nonfinite=int(cnt[_lib.PML_NONFINITE]))
+
+
+def _to_host(r):
+    done = r["done"].cpu().numpy()
+    return dict(H=r["H"].cpu().numpy(), deviance=r["deviance"].cpu().numpy(), gap=r["gap"].cpu().numpy(),
+                n_pass=r["n_pass"].cpu().numpy().astype(np.int64), converged=done == 1, unmodelled=r["unmodelled"], nonfinite=r["nonfinite"])
+
+
+def ml_unmix(X, D, H0=None, components=None, tol=1e-3, max_pass=MAX_PASS, chunk=CHUNK, log_shift=1e-14, layout="cm"):
+    """The Poisson maximum-likelihood abundances of every pixel given the spectra D, over the component set ``components`` (None: all),
+    by EM with a per-pixel stop.  Returns dict(
+
+    * ``H`` (k, p) float64: the ML abundances, rows outside the set exactly 0, scaled so that sum_j s_j h_j = N (s: the column sums of
+      D, N: the pixel's counts); a pixel without a count has h = 0;
+    * ``deviance`` (p,): 2 sum_c (x ln(x / y) - x + y) at ``H``, y = max(D h, log_shift) - ``pixel_diagnostics``' expression;
+    * ``gap`` (p,): the certificate 2 N (max_j (D^T (x / y))_j / s_j - 1): ``deviance`` is above its minimum over {h >= 0, support in
+      the set} by at most ``gap`` (convexity; it needs no entry with counts under the floor - see ``unmodelled``);
+    * ``n_pass`` (p,) int: the EM steps the pixel took; ``converged`` (p,) bool: gap <= tol.  A pixel that is not converged after
+      ``max_pass`` passes reports the deviance and gap of its last pass and the h the next pass would start from;
+    * ``unmodelled``: the entries with counts whose model is below ``log_shift`` (over the converged pixels); ``nonfinite``: the pixels
+      stopped at a value that is not finite (they are not converged)).
+
+    X: the image as measured, (channels, pixels) for ``layout="cm"`` or (pixels, channels) for "pm", a host array or a device tensor,
+    checked and uploaded ONCE by the marginals' rules.  D (n, k): 1 .. 8 components (NotImplementedError beyond), finite, not negative;
+    a component of the set needs a spectrum that is not all zero.  ``H0`` (k, p): the start; an entry of the set that is not > 0 is
+    replaced by N / (|set| s_j) * 1e-3; None: N / sum_set s.  ``chunk``: the passes per launch (the results do not depend on it).
+    ValueError for shapes that do not match, ``tol`` or ``log_shift`` not positive and X, D or H0 not finite - before anything is
+    uploaded."""
+    sv = _Solver(X, D, tol, max_pass, chunk, log_shift, layout, "ml_unmix")
+    start = sv.check_start(H0)
+    comp, mask = sv.check_components(components)
+    return _to_host(sv.run(start, comp, mask))
+
+
+def _empty_model_deviance(X, layout, log_shift):
+    """The deviance of the model with no component at all, by the floor rule: y = log_shift in every channel; 0 for a pixel without a
+    count.  Host numpy, one pass."""
+    try:
+        import torch
+        if isinstance(X, torch.Tensor):
+            X = X.cpu().numpy()
+    except ImportError:
+        pass
+    x = np.asarray(X, dtype=np.float64)
+    x = x if layout == "cm" else x.T
+    t = log_shift - x
+    pos = x > 0
+    t[pos] += x[pos] * np.log(x[pos] * (1.0 / log_shift))
+    return np.where(x.sum(axis=0) == 0, 0.0, 2.0 * t.sum(axis=0))
+
+
+def pvalue(lr):
+    """1/2 erfc(sqrt(lr / 2)): the tail of the boundary mixture 1/2 chi2_0 + 1/2 chi2_1 at ``lr``; 1 where lr == 0."""
+    from scipy.special import erfc
+    lr = np.asarray(lr, dtype=np.float64)
+    return np.where(lr > 0, 0.5 * erfc(np.sqrt(lr / 2.0)), 1.0)
+
+
+def presence(X, D, H0=None, tol=1e-3, max_pass=MAX_PASS, chunk=CHUNK, log_shift=1e-14, layout="cm"):
+    """Is component j present in pixel q?  The likelihood ratio between the pixel's ML fit with all k spectra and its ML fit with
+    spectrum j left out (``ml_unmix`` k + 1 times on the resident image, each reduced fit started at the full solution with row j
+    zeroed).  Returns dict(
+
+    * ``H_ml`` (k, p), ``deviance_ml`` (p,): the full fit;
+    * ``lr`` (k, p) = max(deviance without j - deviance_ml, 0): each of the two deviances is within ``gap`` <= tol of its minimum, so
+      every entry is certified to within ``tol`` on either side;
+    * ``pvalue`` (k, p) = 1/2 erfc(sqrt(lr / 2)), 1 where lr = 0: the tail of 1/2 chi2_0 + 1/2 chi2_1, the law of the statistic when
+      the true abundance sits ON the boundary h_j = 0.  It is ASYMPTOTIC: at a few tens of counts per pixel, and where other abundances
+      sit on their boundaries too, it is a guide and no calibration (``sampling`` draws the replicates a calibration needs);
+    * ``converged``, ``gap``, ``n_pass`` (k + 1, p): row 0 the full fit, row 1 + j the fit without j;
+    * ``unmodelled``, ``nonfinite``: of the full fit).
+
+    With one component the reduced model is empty: its deviance is the floor rule's, y = log_shift in every channel, formed on the
+    host without a launch.  Arguments and refusals as for ``ml_unmix``; every component needs a spectrum that is not all zero."""
+    sv = _Solver(X, D, tol, max_pass, chunk, log_shift, layout, "presence")
+    start = sv.check_start(H0)
+    comp, mask = sv.check_components(None)
+    k, p = sv.k, sv.p
+    held = sv._host if k == 1 else None
+    full = sv.run(start, comp, mask)
+    without = np.empty((k, p))
+    rows = [_to_host(full)]
+    for j in range(k):
+        if k == 1:
+            without[j] = _empty_model_deviance(held, layout, sv.log_shift)
+            rows.append(dict(converged=np.ones(p, dtype=bool), gap=np.zeros(p), n_pass=np.zeros(p, dtype=np.int64)))
+            continue
+        Hs = full["H"].clone()
+        Hs[j] = 0.0
+        rest = [i for i in comp if i != j]
+        red = _to_host(sv.run(Hs, rest, mask & ~(1 << j)))
+        without[j] = red["deviance"]
+        rows.append(red)
+    lr = np.maximum(without - rows[0]["deviance"][None, :], 0.0)
+    return dict(H_ml=rows[0]["H"], deviance_ml=rows[0]["deviance"], lr=lr, pvalue=pvalue(lr),
+                converged=np.stack([r["converged"] for r in rows]), gap=np.stack([r["gap"] for r in rows]),
+                n_pass=np.stack([r["n_pass"] for r in rows]), unmodelled=rows[0]["unmodelled"], nonfinite=rows[0]["nonfinite"])

@@ -59,6 +59,9 @@
  *   espm_residual_products <- (new) the Pearson residual matrix (X - Y) / sqrt(Y) applied to a block of vectors from either side: the
  *                            pass behind its leading singular triplets (a missing phase) and, against the independence model,
  *                            hyperspy's Poisson-normalised PCA scree plot; no reference analogue
+ *   espm_pixel_ml         <- (new) per-pixel Poisson maximum-likelihood abundances given the spectra over a subset of the components,
+ *                            EM with an optimality certificate and a per-pixel stop: the nested fits behind a likelihood-ratio
+ *                            presence test; no reference analogue
  *   espm_lu_pl            <- espm/estimators/updates.py:179 -> scikit-learn's _initialize_nmf -> _randomized_range_finder: the LU
  *                            normaliser of its power iterations (scipy.linalg.lu(A, permute_l=True)[0]) on tall device matrices
  *
@@ -1040,6 +1043,52 @@ int espm_residual_products(const void* x, int x_dtype, int x_layout, int64_t ld,
                            const double* d, const double* h, int k, double log_shift, double* out, double* chi2, int64_t* unmodelled,
                            void* scratch, size_t scratch_bytes, espm_stream_t stream);
 size_t espm_residual_products_scratch(int side, int n, int p, int g);
+
+/* ---- pixel ML (csrc/mu_pixel_ml.hip; espm_amd.presence, NMFEstimator.presence_maps) ----
+ * The maximum-likelihood abundances of every pixel given the spectra, over a subset of the components, by EM with an optimality
+ * certificate and a stop of the pixel's own: the two nested fits a likelihood-ratio test of "is component j in this pixel" compares.
+ * An ITERATING image pass: the image is walked once per EM pass, the pixel's state stays in its thread.  Plain device pointers, no
+ * espm_mu_state; x, x_dtype (ESPM_DIAG_X_*: u8, u16, f32, f64), x_layout, ld and d (n, k) row-major exactly as for
+ * espm_pixel_diagnostics.  mask: the component set M, bit j for component j.  s: a HOST array of k doubles, s[j] = sum_c d[c, j]
+ * (read during the call, passed to the kernel by value); s[j] > 0 is required for every j in M.
+ * THE RULE (the outputs are defined by it), all in fp64, for the pixel with the counts x:
+ *   N = 0; N = N + x_c for c ascending.  N == 0: the pixel is done at once with h = 0, dev = 0, gap = 0 and 0 passes.
+ *   start (passes == 0 on entry): h_j = 0 for j not in M; for j in M an h_j that is not > 0 becomes N / (|M| s_j) * 1e-3.
+ *   one pass:
+ *     1  S = 0; S = fma(s_j, h_j, S) for j in M ascending; f = N / S; h_j = h_j * f            (the scale of least deviance on the ray)
+ *     2  per channel c ascending: y = 0; y = fma(d[c, j], h_j, y) for j = 0 .. k - 1; floored = !(y >= log_shift);
+ *        y = floored ? log_shift : y; i = 1 / y; w = x_c * i; t = y - x_c; if x_c > 0: t = fma(x_c, log(w), t); dev = dev + t;
+ *        q_j = fma(d[c, j], w, q_j)                                  (espm_pixel_diagnostics' expression and floor; dev ends as 2 dev)
+ *     3  r_j = q_j / s_j for j in M
+ *     4  gap = 2 N (max_{j in M} r_j - 1): the pixel's deviance is above its minimum over {h >= 0, support in M} by at most gap
+ *        wherever no entry with counts is floored (convexity, and sum_j s_j h_j = N at h and at the optimum)
+ *     5  gap <= tol: the pixel is DONE - h (as scaled in 1), dev, gap and passes are stored and never touched again, done = 1, and
+ *        its floored entries with x_c > 0 add to counters[ESPM_PML_UNMODELLED].  Otherwise h_j = h_j r_j (the EM step: the deviance
+ *        never rises) and passes goes up by one.
+ *     S, dev or gap not finite, or S not > 0: the pixel stops with done = 2 and h as the pass found it (dev, gap as computed), and adds
+ *     to counters[ESPM_PML_NONFINITE].
+ * A call runs AT MOST n_pass passes for every pixel with done == 0 and is RESUMABLE: the state of a pixel is h_inout (k, p), passes (p,)
+ * int32 and done (p,) uint8, which the caller zeroes (passes, done) and fills (h_inout: the start) before the first call; two calls
+ * with n_pass = a and b leave bit for bit what one call with a + b leaves.  A pixel still not done after the call holds the h the
+ * next pass starts from, and in dev and gap the values of its last pass (of the h before that pass's EM step).  dev, gap (p,) fp64.
+ * counters: 3 uint64 on the device.  counters[ESPM_PML_NOT_DONE] is zeroed by the call and receives the number of pixels with
+ * done == 0 after it - the one integer a host loop reads between calls; the other two are ADDED to as pixels stop (the caller zeroes
+ * them before the first call), so their totals do not depend on how the passes were split into calls.
+ * One pixel per thread, ESPM_DIAG_BLOCK pixels per workgroup, d staged through LDS ESPM_DIAG_CHUNK channels at a time; a workgroup
+ * leaves the pass loop when all its pixels are done.  No value is accumulated atomically but the three integer counts: a pixel's
+ * results do not depend on its neighbours, on the layout, on the dtype that holds its counts, or on the split into calls or slabs.
+ * ESPM_EINVAL, before the device is touched, for a null pointer, a layout or dtype that does not exist, n or p below 1, ld below the
+ * row length, log_shift or tol not positive, n_pass below 1, a mask that is empty or has bits at or above k, and s[j] not > 0 (or not
+ * finite) for a j in the mask; ESPM_EUNSUPPORTED for k outside 1..ESPM_PML_MAX_K.  Only the narrow build has the kernels; the wide
+ * builds return ESPM_EUNSUPPORTED.  No espm_mu_state is involved: ESPM_MU_ABI_VERSION stays. */
+#define ESPM_PML_MAX_K 8         /* components of the model (ESPM_DIAG_MAX_K)                                                     */
+enum { ESPM_PML_NOT_DONE = 0,    /* pixels with done == 0 after the call (zeroed by the call)                                     */
+       ESPM_PML_UNMODELLED = 1,  /* entries with counts whose model is below log_shift, of the pixels that became done (added to)   */
+       ESPM_PML_NONFINITE = 2,   /* pixels stopped at a value that is not finite (added to)                                       */
+       ESPM_PML_COUNTERS = 3 };
+int espm_pixel_ml(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, const double* d, const double* s, int k, uint32_t mask,
+                  double log_shift, double tol, int n_pass, double* h_inout, double* dev, double* gap, int32_t* passes, uint8_t* done,
+                  uint64_t* counters, espm_stream_t stream);
 
 #ifdef __cplusplus
 }

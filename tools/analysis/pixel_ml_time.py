@@ -1,0 +1,112 @@
+"""Time of espm_pixel_ml (csrc/mu_pixel_ml.hip) at the headline image (2048 channels x 512^2 pixels, k = 5, 8-bit X): the time of one
+EM pass over the image, the passes the pixels need at tol = 1e-3, and the whole of ``presence.presence`` (k + 1 nested fits) -
+against ONE espm_pixel_diagnostics pass over the same image in the same process, the yardstick: a pixel ML pass does strictly less
+arithmetic per entry (2 k FMAs, one division, one logarithm against that plus k (k + 1) / 2 FMAs).
+
+    python tools/analysis/pixel_ml_time.py [--size n,nx,ny] [--k 5] [--counts 500] [--runs 3] [--max-pass 20000] [--no-presence] [--out FILE]
+
+X is device-resident (synthetic Poisson counts drawn on the device from ``pixel_diagnostics_time.model``).  The time per pass is the
+difference of two calls from the same fresh state, with 4 and with 12 passes, over the 8 passes between them (no pixel stops that
+early: the count of pixels not done is checked) - the first call's walk for N and the launch are in both and cancel.  Every number
+is min - max over --runs after a warm-up, HIP events around the calls."""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import pixel_diagnostics_time as pdt  # noqa: E402
+from espm_amd import _lib, presence  # noqa: E402
+from espm_amd.conf import log_shift  # noqa: E402
+from espm_amd.engine import _ptr, _stream, require_gpu  # noqa: E402
+
+
+def passes_call(X, D, s, H, state, n_pass, tol):
+    dv, gp, passes, done, counters = state
+    n, p = X.shape
+    _lib.check(_lib.lib.espm_pixel_ml(_ptr(X), pdt.CODES[X.dtype], _lib.LAYOUT_CM, int(X.stride(0)), n, p, _ptr(D), s.ctypes.data, D.shape[1],
+                                      (1 << D.shape[1]) - 1, float(log_shift), tol, n_pass, _ptr(H), _ptr(dv), _ptr(gp), _ptr(passes), _ptr(done),
+                                      _ptr(counters), _stream()))
+
+
+def fresh(p, k, H0):
+    return H0.clone(), (torch.zeros(p, dtype=torch.float64, device="cuda"), torch.zeros(p, dtype=torch.float64, device="cuda"),
+                        torch.zeros(p, dtype=torch.int32, device="cuda"), torch.zeros(p, dtype=torch.uint8, device="cuda"),
+                        torch.zeros(3, dtype=torch.int64, device="cuda"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", default="2048,512,512")
+    ap.add_argument("--k", type=int, default=5)
+    ap.add_argument("--counts", type=float, default=500.0)
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--max-pass", type=int, default=presence.MAX_PASS)
+    ap.add_argument("--no-presence", action="store_true")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    require_gpu()
+    n, nx, ny = (int(v) for v in args.size.split(","))
+    p, k, tol = nx * ny, args.k, 1e-3
+
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        open(args.out, "w").close()
+
+    def say(text):
+        print(text, flush=True)
+        if args.out:   # (line by line: the nested fits take a while)
+            with open(args.out, "a") as f:
+                f.write(text + "\n")
+
+    pdt.COUNTS = args.counts
+    g = torch.Generator(device="cuda").manual_seed(k)
+    D, Ht = pdt.model(n, p, k, g)
+    X = pdt.draw(D, Ht, g)
+    say(f"pixel ML, {n} channels x {nx} x {ny} pixels, k = {k}, {args.counts:.0f} counts per pixel, uint8 channel-major, tol = {tol:g}, "
+        f"{torch.cuda.get_device_name(0)}")
+    # the yardstick: one pixel diagnostics pass
+    out = (torch.empty(p, dtype=torch.float64, device="cuda"), torch.empty((k, p), dtype=torch.float64, device="cuda"),
+           torch.zeros(1, dtype=torch.int32, device="cuda"))
+    lo, hi = pdt.timed(lambda: pdt.kernel(X, "cm", D, Ht, False, out), args.runs)
+    say(f"  espm_pixel_diagnostics, one pass: {lo:8.3f} - {hi:8.3f} ms")
+    diag = (lo, hi)
+    # one EM pass
+    s = np.ascontiguousarray(D.sum(dim=0).cpu().numpy())
+    H0 = (X.sum(dim=0, dtype=torch.float64) / float(s.sum()))[None, :].repeat(k, 1).contiguous()
+    t = {}
+    for n_pass in (4, 12):
+        def run():
+            H, state = fresh(p, k, H0)
+            passes_call(X, D, s, H, state, n_pass, tol)
+            run.left = state[4]
+        # (the allocation and the clone of the fresh state are inside the events of both calls and cancel in the difference)
+        t[n_pass] = pdt.timed(run, args.runs)
+        left = int(run.left[_lib.PML_NOT_DONE])
+        say(f"  espm_pixel_ml, {n_pass:2d} passes from a fresh state: {t[n_pass][0]:8.3f} - {t[n_pass][1]:8.3f} ms, {left} of {p} pixels not done")
+    per = ((t[12][0] - t[4][0]) / 8.0, (t[12][1] - t[4][1]) / 8.0)
+    say(f"  time per pass: {min(per):8.3f} - {max(per):8.3f} ms = {min(per) / diag[0]:.2f} of a pixel diagnostics pass")
+    if not args.no_presence:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = presence.presence(X, D.cpu().numpy(), tol=tol, max_pass=args.max_pass)
+        torch.cuda.synchronize()
+        total = time.perf_counter() - t0
+        npass = res["n_pass"]
+        q = np.percentile(npass[0], [50, 99, 100])
+        say(f"  full fit: passes to the 50th / 99th / last percentile of the pixels: {q[0]:.0f} / {q[1]:.0f} / {q[2]:.0f}; "
+            f"{res['converged'][0].mean():.6f} converged (max_pass {args.max_pass})")
+        for j in range(k):
+            qj = np.percentile(npass[1 + j], [50, 99, 100])
+            say(f"  without component {j}: {qj[0]:.0f} / {qj[1]:.0f} / {qj[2]:.0f} passes; {res['converged'][1 + j].mean():.6f} converged")
+        say(f"  presence, {k + 1} nested fits, read-backs included: {total:.2f} s; median lr per component {np.median(res['lr'], axis=1)}")
+
+
+if __name__ == "__main__":
+    main()
