@@ -40,6 +40,7 @@ MARG_PIXELS, MARG_CHANNELS = _E["ESPM_MARG_PIXELS"], _E["ESPM_MARG_CHANNELS"]
 RESID_MAX_G, RESID_MAX_K, RESID_BLOCK, RESID_PCHUNK = (_D["ESPM_RESID_" + n] for n in ("MAX_G", "MAX_K", "BLOCK", "PCHUNK"))
 RESID_PIXELS, RESID_CHANNELS = _E["ESPM_RESID_PIXELS"], _E["ESPM_RESID_CHANNELS"]
 PML_MAX_K = _D["ESPM_PML_MAX_K"]
+PMLN_STATE_EXTRA = _D["ESPM_PMLN_STATE_EXTRA"]   # espm_pixel_ml_newton's state: (k + PMLN_STATE_EXTRA, p) doubles
 PML_NOT_DONE, PML_UNMODELLED, PML_NONFINITE, PML_COUNTERS = (_E["ESPM_PML_" + n] for n in ("NOT_DONE", "UNMODELLED", "NONFINITE", "COUNTERS"))
 SRC_F32, SRC_F64 =_E["ESPM_SRC_F32"], _E["ESPM_SRC_F64"]
 LAYOUT_CM, LAYOUT_PM = _E["ESPM_LAYOUT_CM"], _E["ESPM_LAYOUT_PM"]

@@ -25,51 +25,9 @@ namespace espm {
 
 #if ESPM_KP == 8
 #include "mu_image_pass.hpp"
+#include "mu_pixel_ml.hpp"   // the geometry, the walk and the argument checks, shared with mu_pixel_ml_newton.hip
 
 namespace pmlk {
-
-constexpr int B = ESPM_DIAG_BLOCK;
-constexpr int CH = ESPM_DIAG_CHUNK;
-constexpr int TP = B + 1;   // pixel stride of the pixel-major tile
-static_assert(B % 64 == 0 && ESPM_PML_COUNTERS <= B, "whole waves; a thread per counter");
-
-template <int K>
-struct Sums {   // s, by value: uniform over the launch
-  double v[K];
-};
-
-// The channels of the workgroup's pixels, ascending: f(x, row of D in LDS) for every entry of an `active` thread.  WITH_D: the rows of
-// D are staged (and `restage` says whether ds still holds the one chunk there is); every thread of the workgroup comes here.
-template <int K, typename XT, bool PM, bool WITH_D, typename F>
-__device__ __forceinline__ void walk(const XT* __restrict__ x, int64_t ld, int n, int p, int q0, const double* __restrict__ d, double* ds,
-                                     XT* tile, bool restage, bool active, F f) {
-  const int q = q0 + threadIdx.x;
-  for (int c0 = 0; c0 < n; c0 += CH) {
-    const int cn = min(CH, n - c0);
-    if (WITH_D && restage) {   // (workgroup-uniform)
-      __syncthreads();   // (the readers of the round before)
-      for (int i = threadIdx.x; i < cn * K; i += B) ds[i] = d[(size_t)c0 * K + i];
-      __syncthreads();
-    }
-    if constexpr (!PM) {
-      if (active) {
-        const XT* xp = x + (size_t)c0 * ld + q;
-#pragma unroll 4
-        for (int c = 0; c < cn; ++c) f((double)xp[(size_t)c * ld], ds + c * K);
-      }
-    } else {
-      constexpr int TS = tile_rows<XT>();
-      for (int t0 = 0; t0 < cn; t0 += TS) {
-        const int tn = min(TS, cn - t0);
-        __syncthreads();   // (the tile's readers of the round before)
-        fill_tile<XT, B>(tile, x, ld, q0, p, c0 + t0, tn);
-        __syncthreads();
-        if (active)
-          for (int c = 0; c < tn; ++c) f((double)tile[c * TP + threadIdx.x], ds + (t0 + c) * K);
-      }
-    }
-  }
-}
 
 template <int K, typename XT, bool PM>
 __global__ __launch_bounds__(B) void pixel_ml_kernel(const XT* __restrict__ x, int64_t ld, int n, int p, const double* __restrict__ d,
@@ -221,17 +179,8 @@ extern "C" int espm_pixel_ml(const void* x, int x_dtype, int x_layout, int64_t l
 #else
   const char* who = "pixel ML";
   if (k < 1 || k > ESPM_PML_MAX_K) return set_error(ESPM_EUNSUPPORTED, "%s: k=%d (1..%d components)", who, k, ESPM_PML_MAX_K);
-  ESPM_REQUIRE(x && d && s && h_inout && dev && gap && passes && done && counters,
-               "%s: bad arguments (x %p, d %p, s %p, h %p, dev %p, gap %p, passes %p, done %p, counters %p)", who, x, (const void*)d,
-               (const void*)s, (void*)h_inout, (void*)dev, (void*)gap, (void*)passes, (void*)done, (void*)counters);
-  if (int rc = check_image(who, x, x_dtype, ESPM_DIAG_X_F64, x_layout, ld, n, p)) return rc;
-  ESPM_REQUIRE(log_shift > 0, "%s: log_shift=%g must be positive", who, log_shift);
-  ESPM_REQUIRE(tol > 0, "%s: tol=%g must be positive", who, tol);
-  ESPM_REQUIRE(n_pass >= 1, "%s: n_pass=%d (at least one pass)", who, n_pass);
-  ESPM_REQUIRE(mask != 0 && (mask >> k) == 0,"%s: mask 0x%x over %d components (empty, or bits beyond them)", who, mask, k);
-  for (int j = 0; j < k; ++j)
-    if ((mask >> j) & 1u)
-      ESPM_REQUIRE(s[j] > 0 && std::isfinite(s[j]), "%s: component %d is in the mask and its spectrum sums to %g", who, j, s[j]);
+  if (int rc = pmlk::check_args(who, x, x_dtype, x_layout, ld, n, p, d, s, k, mask, log_shift, tol, n_pass, h_inout, dev, gap, passes, done, counters))
+    return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counters);
   if (int rc = check_hip(hipMemsetAsync(cnt + ESPM_PML_NOT_DONE, 0, sizeof(unsigned long long), st), "pixel ML: zeroing the counter")) return rc;

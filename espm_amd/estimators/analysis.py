@@ -436,7 +436,7 @@ class _FitAnalysis:
         return out
 
     # ---- is phase j in this pixel at all: per-pixel ML abundances and nested likelihood-ratio tests ---------------------------------
-    def presence_maps(self, X=None, tol=1e-3, max_pass=None):
+    def presence_maps(self, X=None, tol=1e-3, max_pass=None, method="em"):
         """Is phase j present in this pixel?  ``espm_amd.presence.presence`` on the fitted spectra ``G_ @ W_``, started at ``H_``: the
         Poisson maximum-likelihood abundances of every pixel given the spectra, and for every component the likelihood ratio between
         that fit and the pixel's best fit WITHOUT the component - the honest statistic where an abundance sits at or near zero and
@@ -446,7 +446,7 @@ class _FitAnalysis:
         deviance_ml, 0), certified to within ``tol`` on either side; ``presence_pvalue_`` (k, p) = 1/2 erfc(sqrt(lr / 2)), the tail of
         the boundary mixture 1/2 chi2_0 + 1/2 chi2_1 - asymptotic, a guide at a few tens of counts per pixel -, 1 where lr = 0; and
         ``ml_converged_`` (bool), ``ml_gap_``, ``ml_n_pass_``, each (k + 1, p): row 0 the full fit, row 1 + j the fit without
-        component j.  Returns dict(H_ml, deviance_ml, lr, pvalue, converged, gap, n_pass, unmodelled, nonfinite); with ``hspy_comp``
+        component j; and ``ml_method_``, the ``method`` of this call.  Returns dict(H_ml, deviance_ml, lr, pvalue, converged, gap, n_pass, unmodelled, nonfinite); with ``hspy_comp``
         the returned ``H_ml`` is (p, k), as ``fit_transform`` returns ``H_.T``; the maps stay (k, p).
 
         The ML is over h >= 0 alone: the regularisers of the fit (``mu``, ``lambda_L``) and ``simplex_H`` are NOT imposed.  A fit
@@ -456,12 +456,15 @@ class _FitAnalysis:
 
         ``tol``: the certified gap, in deviance units, at which a pixel stops; ``max_pass``: the cap of a pixel's EM passes (None:
         ``presence.MAX_PASS``) - EM takes hundreds of passes, with tails of thousands, and pixels still running at the cap are False in
-        ``ml_converged_``.  ``X`` as for ``pixel_diagnostics``; ``X=None`` takes the fit's ``X_`` un-scaled, with the cost and the
+        ``ml_converged_``.  ``method``: "em" (the default: the rule defined bit for bit) or "newton" (the safeguarded Newton step of
+        ``presence.ml_unmix``: the same certified statistic within ``tol``, tens of passes per pixel), the one method for all k + 1
+        fits; anything else is a ValueError.  ``X`` as for ``pixel_diagnostics``; ``X=None`` takes the fit's ``X_`` un-scaled, with the cost and the
         ``log_shift`` fill described there (refused after ``fit_binned``).  Computed in fp64 whatever the estimator's precision, on the
         current device (a ``shard()``ed estimator: every rank computes all pixels on its own device); 1 .. 8 components
         (NotImplementedError beyond), all before anything is uploaded."""
         from espm_amd import presence
         check_is_fitted(self, "W_")
+        presence._check_method(method)
         k = int(self.H_.shape[0])
         if k > presence.MAX_K:
             raise NotImplementedError(f"presence_maps: {k} components (the kernels are built for 1..{presence.MAX_K})")
@@ -469,7 +472,8 @@ class _FitAnalysis:
         G, W, H = self._model_factors()
         D = W if G is None else G @ W
         out = presence.presence(X, D, H, tol=tol, max_pass=presence.MAX_PASS if max_pass is None else max_pass,
-                                log_shift=self.log_shift, layout=layout)
+                                log_shift=self.log_shift, layout=layout, method=method)
+        self.ml_method_ = method
         self.H_ml_, self.deviance_ml_ = out["H_ml"], out["deviance_ml"]
         self.presence_lr_, self.presence_pvalue_ = out["lr"], out["pvalue"]
         self.ml_converged_, self.ml_gap_, self.ml_n_pass_ = out["converged"], out["gap"], out["n_pass"]

@@ -202,10 +202,13 @@ def diagnostic_maps(est, shape_2d=None):
     return np.asarray(est.deviance_).reshape((ny, nx)), np.asarray(est.H_std_).reshape((-1, ny, nx))
 
 
-def presence_maps(est, shape_2d=None):
+def presence_maps(est, shape_2d=None, method=None):
     """``est.H_ml_``, ``est.presence_lr_`` and ``est.presence_pvalue_`` (set by ``est.presence_maps()``) in the navigation shape, like
     the loadings: (k, ny, nx) each - the per-pixel ML abundances, the likelihood-ratio statistic of every phase's presence and its
-    asymptotic p-value."""
+    asymptotic p-value.  ``method``: None takes the maps as the last ``est.presence_maps()`` left them; "em" or "newton" runs
+    ``est.presence_maps(method=method)`` on the fit's own image first."""
+    if method is not None:
+        est.presence_maps(method=method)
     if not hasattr(est, "presence_lr_"):
         raise AttributeError("call est.presence_maps() first: it sets H_ml_, presence_lr_ and presence_pvalue_")
     ny, nx = (int(v) for v in (shape_2d if shape_2d is not None else est.shape_2d))

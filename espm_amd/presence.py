@@ -6,13 +6,15 @@ a likelihood ratio between nested models: the pixel's best Poisson fit with all 
 out.  Both are per-pixel maximum-likelihood problems given the spectra D:
 
 * ``ml_unmix``: the ML abundances of every pixel over a set of components, by EM (the entry point espm_pixel_ml; the rule is in
-  include/espm_mu.h, "pixel ML") - every pixel with a stop of its own and an optimality CERTIFICATE: ``gap`` bounds how far the
+  include/espm_mu.h, "pixel ML") or by a safeguarded Newton step (``method="newton"``: espm_pixel_ml_newton, csrc/mu_pixel_ml_newton.hip,
+  "pixel ML, Newton") - every pixel with a stop of its own and an optimality CERTIFICATE: ``gap`` bounds how far the
   pixel's deviance is above the minimum over {h >= 0, support in the set}, wherever no entry with counts sits under the floor;
 * ``presence``: the k + 1 nested fits, the likelihood-ratio statistic ``lr`` of every (component, pixel) - certified to within
   ``tol`` on either side - and its asymptotic p-value under the boundary mixture 1/2 chi2_0 + 1/2 chi2_1.
 
 The ML abundances are also what ``H_std`` is formally a bound for, and with a ``simplex_H`` fit their column sums map the per-pixel
-dose or thickness that the simplex model cannot express.  EM is slow (hundreds of passes, tails of thousands) and cannot fail; the
+dose or thickness that the simplex model cannot express.  EM is slow (hundreds of passes, tails of thousands) and cannot fail, and
+it is the default; the Newton rule reaches the same certified points in tens of passes.  The
 kernel runs a bounded number of passes per launch and the loop here reads one integer, the pixels not yet done, between launches.
 fp64 throughout, no float atomics: two calls, both layouts, every dtype that holds the counts and every ``chunk`` give the same bits.
 Everything but the argument checks needs the GPU (there is no CPU path)."""
@@ -25,6 +27,13 @@ from espm_amd._image_args import check_layout, image_dims, layout_code
 MAX_K = 8            # ESPM_PML_MAX_K: components of the model
 MAX_PASS = 20000     # the default cap of the passes of a pixel
 CHUNK = 64           # passes per launch
+METHODS = ("em", "newton")   # espm_pixel_ml, espm_pixel_ml_newton
+
+
+def _check_method(method):
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}, not {method!r}")
+    return method
 
 
 def _on_device(X):
@@ -55,9 +64,10 @@ def _components(components, k):
 class _Solver:
     """X and the spectra, checked on the host and then uploaded ONCE: every ``run`` is a nested fit on the resident image."""
 
-    def __init__(self, X, D, tol, max_pass, chunk, log_shift, layout, who):
+    def __init__(self, X, D, tol, max_pass, chunk, log_shift, layout, who, method="em"):
         from espm_amd import marginals
         check_layout(layout)
+        self.method = _check_method(method)
         if getattr(X, "ndim", None) != 2:
             X = np.asarray(X)
         if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
@@ -141,12 +151,18 @@ class _Solver:
             done = torch.zeros(p, dtype=torch.uint8, device=self.dev)
             counters = torch.zeros(3, dtype=torch.int64, device=self.dev)
             s_ptr = self.s.ctypes.data_as(C.c_void_p)
+            args = (_ptr(self.Xd), self.code, layout_code(self.layout), int(self.Xd.stride(0)), self.n, p, _ptr(self.Dd), s_ptr, k, mask,
+                    self.log_shift, self.tol)
+            state = (_ptr(Hd), _ptr(dv), _ptr(gp), _ptr(passes), _ptr(done), _ptr(counters))
+            if self.method == "newton":   # the rule's own scratch (e, dev_acc, tau, trial per pixel): the kernel initialises it
+                extra = torch.empty((k + _lib.PMLN_STATE_EXTRA, p), dtype=torch.float64, device=self.dev)
+                entry, state = _lib.lib.espm_pixel_ml_newton, state + (_ptr(extra), extra.numel() * extra.element_size())
+            else:
+                entry = _lib.lib.espm_pixel_ml
             issued = 0
             while issued < self.max_pass:   # bounded launches: no launch's duration depends on the slowest pixel of the image
                 step = min(self.chunk, self.max_pass - issued)
-                _lib.check(_lib.lib.espm_pixel_ml(_ptr(self.Xd), self.code, layout_code(self.layout), int(self.Xd.stride(0)), self.n, p,
-                                                  _ptr(self.Dd), s_ptr, k, mask, self.log_shift, self.tol, step, _ptr(Hd), _ptr(dv), _ptr(gp),
-                                                  _ptr(passes), _ptr(done), _ptr(counters), _stream()))
+                _lib.check(entry(*args, step, *state, _stream()))
                 issued += step
                 if int(counters[_lib.PML_NOT_DONE].item()) == 0:   # the one integer read between the chunks
                     break
@@ -161,17 +177,20 @@ def _to_host(r):
                 n_pass=r["n_pass"].cpu().numpy().astype(np.int64), converged=done == 1, unmodelled=r["unmodelled"], nonfinite=r["nonfinite"])
 
 
-def ml_unmix(X, D, H0=None, components=None, tol=1e-3, max_pass=MAX_PASS, chunk=CHUNK, log_shift=1e-14, layout="cm"):
+def ml_unmix(X, D, H0=None, components=None, tol=1e-3, max_pass=MAX_PASS, chunk=CHUNK, log_shift=1e-14, layout="cm", method="em"):
     """The Poisson maximum-likelihood abundances of every pixel given the spectra D, over the component set ``components`` (None: all),
-    by EM with a per-pixel stop.  Returns dict(
+    by EM (``method="em"``, the default and the rule that is defined bit for bit) or by the safeguarded Newton step of
+    include/espm_mu.h, "pixel ML, Newton" (``method="newton"``: the same certificate and stop, tens of passes where EM takes hundreds
+    to thousands), with a per-pixel stop.  Returns dict(
 
     * ``H`` (k, p) float64: the ML abundances, rows outside the set exactly 0, scaled so that sum_j s_j h_j = N (s: the column sums of
       D, N: the pixel's counts); a pixel without a count has h = 0;
     * ``deviance`` (p,): 2 sum_c (x ln(x / y) - x + y) at ``H``, y = max(D h, log_shift) - ``pixel_diagnostics``' expression;
     * ``gap`` (p,): the certificate 2 N (max_j (D^T (x / y))_j / s_j - 1): ``deviance`` is above its minimum over {h >= 0, support in
       the set} by at most ``gap`` (convexity; it needs no entry with counts under the floor - see ``unmodelled``);
-    * ``n_pass`` (p,) int: the EM steps the pixel took; ``converged`` (p,) bool: gap <= tol.  A pixel that is not converged after
-      ``max_pass`` passes reports the deviance and gap of its last pass and the h the next pass would start from;
+    * ``n_pass`` (p,) int: the steps the pixel took (under "newton": trials, rejected ones included); ``converged`` (p,) bool:
+      gap <= tol.  A pixel that is not converged after ``max_pass`` passes reports the deviance and gap of its last pass (under
+      "newton": of its last accepted point) and the h the next pass would start from;
     * ``unmodelled``: the entries with counts whose model is below ``log_shift`` (over the converged pixels); ``nonfinite``: the pixels
       stopped at a value that is not finite (they are not converged)).
 
@@ -179,9 +198,9 @@ def ml_unmix(X, D, H0=None, components=None, tol=1e-3, max_pass=MAX_PASS, chunk=
     checked and uploaded ONCE by the marginals' rules.  D (n, k): 1 .. 8 components (NotImplementedError beyond), finite, not negative;
     a component of the set needs a spectrum that is not all zero.  ``H0`` (k, p): the start; an entry of the set that is not > 0 is
     replaced by N / (|set| s_j) * 1e-3; None: N / sum_set s.  ``chunk``: the passes per launch (the results do not depend on it).
-    ValueError for shapes that do not match, ``tol`` or ``log_shift`` not positive and X, D or H0 not finite - before anything is
-    uploaded."""
-    sv = _Solver(X, D, tol, max_pass, chunk, log_shift, layout, "ml_unmix")
+    ValueError for shapes that do not match, ``tol`` or ``log_shift`` not positive, X, D or H0 not finite and a ``method`` that does
+    not exist - before anything is uploaded."""
+    sv = _Solver(X, D, tol, max_pass, chunk, log_shift, layout, "ml_unmix", method)
     start = sv.check_start(H0)
     comp, mask = sv.check_components(components)
     return _to_host(sv.run(start, comp, mask))
@@ -211,10 +230,10 @@ def pvalue(lr):
     return np.where(lr > 0, 0.5 * erfc(np.sqrt(lr / 2.0)), 1.0)
 
 
-def presence(X, D, H0=None, tol=1e-3, max_pass=MAX_PASS, chunk=CHUNK, log_shift=1e-14, layout="cm"):
+def presence(X, D, H0=None, tol=1e-3, max_pass=MAX_PASS, chunk=CHUNK, log_shift=1e-14, layout="cm", method="em"):
     """Is component j present in pixel q?  The likelihood ratio between the pixel's ML fit with all k spectra and its ML fit with
     spectrum j left out (``ml_unmix`` k + 1 times on the resident image, each reduced fit started at the full solution with row j
-    zeroed).  Returns dict(
+    zeroed).  ``method``: as for ``ml_unmix``, the one method for all k + 1 fits.  Returns dict(
 
     * ``H_ml`` (k, p), ``deviance_ml`` (p,): the full fit;
     * ``lr`` (k, p) = max(deviance without j - deviance_ml, 0): each of the two deviances is within ``gap`` <= tol of its minimum, so
@@ -227,7 +246,7 @@ def presence(X, D, H0=None, tol=1e-3, max_pass=MAX_PASS, chunk=CHUNK, log_shift=
 
     With one component the reduced model is empty: its deviance is the floor rule's, y = log_shift in every channel, formed on the
     host without a launch.  Arguments and refusals as for ``ml_unmix``; every component needs a spectrum that is not all zero."""
-    sv = _Solver(X, D, tol, max_pass, chunk, log_shift, layout, "presence")
+    sv = _Solver(X, D, tol, max_pass, chunk, log_shift, layout, "presence", method)
     start = sv.check_start(H0)
     comp, mask = sv.check_components(None)
     k, p = sv.k, sv.p

@@ -62,7 +62,10 @@
  *   espm_pixel_ml         <- (new) per-pixel Poisson maximum-likelihood abundances given the spectra over a subset of the components,
  *                            EM with an optimality certificate and a per-pixel stop: the nested fits behind a likelihood-ratio
  *                            presence test; no reference analogue
- *   espm_lu_pl            <- espm/estimators/updates.py:179 -> scikit-learn's _initialize_nmf -> _randomized_range_finder: the LU
+ *   espm_pixel_ml_newton  <- (new) the same problem, certificate and stop by a safeguarded Newton step (EM's diagonal metric blended
+ *                            into the Hessian, a fraction-to-boundary clamp, the EM successor after a rejected trial): tens of
+ *                            passes where EM takes hundreds to thousands; no reference analogue
+ *   espm_lu_pl           <- espm/estimators/updates.py:179 -> scikit-learn's _initialize_nmf -> _randomized_range_finder: the LU
  *                            normaliser of its power iterations (scipy.linalg.lu(A, permute_l=True)[0]) on tall device matrices
  *
  * Conventions
@@ -1089,6 +1092,42 @@ enum { ESPM_PML_NOT_DONE = 0,    /* pixels with done == 0 after the call (zeroed
 int espm_pixel_ml(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, const double* d, const double* s, int k, uint32_t mask,
                   double log_shift, double tol, int n_pass, double* h_inout, double* dev, double* gap, int32_t* passes, uint8_t* done,
                   uint64_t* counters, espm_stream_t stream);
+
+/* ---- pixel ML, Newton (csrc/mu_pixel_ml_newton.hip; espm_amd.presence with method="newton") ----
+ * The problem, the certificate, the stop and every output of espm_pixel_ml, reached by a safeguarded Newton step: the EM rule above
+ * stays the defined default, this one is for the images whose tails EM walks for thousands of passes.  The certificate is a property
+ * of the point and not of the path that reached it, so it stays the stop rule: every pixel that is done is certified to tol exactly
+ * as under EM.  Arguments as for espm_pixel_ml, plus state: caller-owned DEVICE scratch of ESPM_PMLN_STATE_BYTES(k, p) bytes
+ * (state_bytes: what the caller allocated), (k + ESPM_PMLN_STATE_EXTRA, p) doubles - rows 0 .. k - 1: e, the EM successor of the last
+ * accepted point; row k: dev_acc, its deviance; row k + 1: tau, the blend; row k + 2: trial (0 or 1).  The kernel initialises the
+ * state of a pixel that enters with passes == 0 (e = 0, dev_acc = +inf, tau = 1e-2, trial = 0); the caller never fills it, and keeps
+ * it, with h_inout, passes and done, from call to call.
+ * THE RULE, for the pixel with the counts x; N, the start and steps 1 - 4 are espm_pixel_ml's, and in the walk of step 2, per
+ * channel c ascending: v = w * i (x_c / y^2); for a = 0 .. k - 1: t = d[c, a] * v; A_ab = fma(t, d[c, b], A_ab) for b = 0 .. a.
+ *     5  S, dev or gap not finite, or S not > 0: the stop of espm_pixel_ml (done = 2, h as the pass found it, dev and gap as computed).
+ *        REJECT, if trial and not dev <= dev_acc: h = e, trial = 0, tau = min(10 tau, 1); passes goes up by one; the reported dev and
+ *        gap stay those of the accepted point.
+ *        ACCEPT, otherwise: dev_acc = dev; dev and gap are reported.  gap <= tol: the pixel is DONE exactly as in espm_pixel_ml (h as
+ *        scaled in 1).  Otherwise, in this order: if trial, tau = max(tau / 10, 1e-8); e_j = h_j r_j (the EM successor);
+ *        g_j = s_j - q_j; B = A over M with B_jj = fma(tau, s_j / h_j, A_jj); B = L diag(p) L^T by the root-free Cholesky of
+ *        espm_pixel_diagnostics, components outside M as rows of the identity; L z = -g, z = z / p, L^T delta = z;
+ *        h_j = max(h_j + delta_j, 0.01 h_j, 1e-30 N / s_j) for j in M and trial = 1 - or, if a pivot p_j is not > 0 or not finite,
+ *        h = e and trial = 0.  passes goes up by one.
+ * Why each piece: a step clamped at exactly 0 is rejected for ever on a pixel with several abundances at the boundary (the clamp at
+ * 0.01 h is a fraction-to-boundary rule: a coordinate reaches the boundary geometrically, and can leave it again); A alone is singular
+ * where a pixel has fewer counts than components (s_j / h_j is the metric in which the EM step is a gradient step: blended in, B is
+ * positive definite, and tau grows after a rejection and shrinks after a success); and after a rejected trial the stored EM
+ * successor is a step that cannot raise the deviance.  The accepted deviances of a pixel never increase.
+ * RESUMABLE as espm_pixel_ml is, state included: two calls with n_pass = a and b leave bit for bit what one call with a + b leaves.
+ * A pixel still not done after the call holds the h its next pass starts from (a trial, or an EM successor), and in dev and gap the
+ * values of its last ACCEPTED point.  Counters, geometry, independence of neighbours, layout, dtype and slabs, and the refusals are
+ * espm_pixel_ml's; ESPM_EINVAL also for a null state or state_bytes below ESPM_PMLN_STATE_BYTES(k, p).  Only the narrow build has the
+ * kernels; the wide builds return ESPM_EUNSUPPORTED.  No espm_mu_state is involved: ESPM_MU_ABI_VERSION stays. */
+#define ESPM_PMLN_STATE_EXTRA 3  /* rows of state beyond the k of e: dev_acc, tau, trial                                          */
+#define ESPM_PMLN_STATE_BYTES(k, p) ((size_t)((k) + ESPM_PMLN_STATE_EXTRA) * (size_t)(p) * sizeof(double))
+int espm_pixel_ml_newton(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, const double* d, const double* s, int k,
+                         uint32_t mask, double log_shift, double tol, int n_pass, double* h_inout, double* dev, double* gap, int32_t* passes,
+                         uint8_t* done, uint64_t* counters, void* state, size_t state_bytes, espm_stream_t stream);
 
 #ifdef __cplusplus
 }

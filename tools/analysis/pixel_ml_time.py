@@ -1,13 +1,16 @@
-"""Time of espm_pixel_ml (csrc/mu_pixel_ml.hip) at the headline image (2048 channels x 512^2 pixels, k = 5, 8-bit X): the time of one
-EM pass over the image, the passes the pixels need at tol = 1e-3, and the whole of ``presence.presence`` (k + 1 nested fits) -
-against ONE espm_pixel_diagnostics pass over the same image in the same process, the yardstick: a pixel ML pass does strictly less
-arithmetic per entry (2 k FMAs, one division, one logarithm against that plus k (k + 1) / 2 FMAs).
+"""Time of espm_pixel_ml (csrc/mu_pixel_ml.hip) and espm_pixel_ml_newton (csrc/mu_pixel_ml_newton.hip) at the headline image (2048
+channels x 512^2 pixels, k = 5, 8-bit X): the time of one pass over the image, the passes the pixels need at tol = 1e-3, and the whole
+of ``presence.presence`` (k + 1 nested fits) - against ONE espm_pixel_diagnostics pass over the same image in the same process, the
+yardstick: an EM pass does strictly less arithmetic per entry (2 k FMAs, one division, one logarithm against that plus
+k (k + 1) / 2 FMAs), a Newton pass the two together.
 
-    python tools/analysis/pixel_ml_time.py [--size n,nx,ny] [--k 5] [--counts 500] [--runs 3] [--max-pass 20000] [--no-presence] [--out FILE]
+    python tools/analysis/pixel_ml_time.py [--size n,nx,ny] [--k 5] [--counts 500] [--runs 3] [--max-pass 20000] [--method em|newton|both]
+                                           [--no-presence] [--out FILE]
 
 X is device-resident (synthetic Poisson counts drawn on the device from ``pixel_diagnostics_time.model``).  The time per pass is the
-difference of two calls from the same fresh state, with 4 and with 12 passes, over the 8 passes between them (no pixel stops that
-early: the count of pixels not done is checked) - the first call's walk for N and the launch are in both and cancel.  Every number
+difference of two calls from the same fresh state, with 4 and with 12 passes (EM) or with 1 and with 3 (Newton, whose pixels stop
+within a handful), over the passes between them (the count of pixels not done is printed with both: a pixel that stopped in between
+takes no further pass) - the first call's walk for N and the launch are in both and cancel.  Every number
 is min - max over --runs after a warm-up, HIP events around the calls."""
 import argparse
 import os
@@ -27,12 +30,16 @@ from espm_amd.conf import log_shift  # noqa: E402
 from espm_amd.engine import _ptr, _stream, require_gpu  # noqa: E402
 
 
-def passes_call(X, D, s, H, state, n_pass, tol):
+def passes_call(X, D, s, H, state, n_pass, tol, method="em"):
     dv, gp, passes, done, counters = state
     n, p = X.shape
-    _lib.check(_lib.lib.espm_pixel_ml(_ptr(X), pdt.CODES[X.dtype], _lib.LAYOUT_CM, int(X.stride(0)), n, p, _ptr(D), s.ctypes.data, D.shape[1],
-                                      (1 << D.shape[1]) - 1, float(log_shift), tol, n_pass, _ptr(H), _ptr(dv), _ptr(gp), _ptr(passes), _ptr(done),
-                                      _ptr(counters), _stream()))
+    args = (_ptr(X), pdt.CODES[X.dtype], _lib.LAYOUT_CM, int(X.stride(0)), n, p, _ptr(D), s.ctypes.data, D.shape[1], (1 << D.shape[1]) - 1,
+            float(log_shift), tol, n_pass, _ptr(H), _ptr(dv), _ptr(gp), _ptr(passes), _ptr(done), _ptr(counters))
+    if method == "newton":
+        extra = torch.empty((D.shape[1] + _lib.PMLN_STATE_EXTRA, p), dtype=torch.float64, device="cuda")
+        _lib.check(_lib.lib.espm_pixel_ml_newton(*args, _ptr(extra), extra.numel() * 8, _stream()))
+    else:
+        _lib.check(_lib.lib.espm_pixel_ml(*args, _stream()))
 
 
 def fresh(p, k, H0):
@@ -48,6 +55,7 @@ def main():
     ap.add_argument("--counts", type=float, default=500.0)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--max-pass", type=int, default=presence.MAX_PASS)
+    ap.add_argument("--method", choices=("em", "newton", "both"), default="em")
     ap.add_argument("--no-presence", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -77,35 +85,37 @@ def main():
     lo, hi = pdt.timed(lambda: pdt.kernel(X, "cm", D, Ht, False, out), args.runs)
     say(f"  espm_pixel_diagnostics, one pass: {lo:8.3f} - {hi:8.3f} ms")
     diag = (lo, hi)
-    # one EM pass
     s = np.ascontiguousarray(D.sum(dim=0).cpu().numpy())
     H0 = (X.sum(dim=0, dtype=torch.float64) / float(s.sum()))[None, :].repeat(k, 1).contiguous()
-    t = {}
-    for n_pass in (4, 12):
-        def run():
-            H, state = fresh(p, k, H0)
-            passes_call(X, D, s, H, state, n_pass, tol)
-            run.left = state[4]
-        # (the allocation and the clone of the fresh state are inside the events of both calls and cancel in the difference)
-        t[n_pass] = pdt.timed(run, args.runs)
-        left = int(run.left[_lib.PML_NOT_DONE])
-        say(f"  espm_pixel_ml, {n_pass:2d} passes from a fresh state: {t[n_pass][0]:8.3f} - {t[n_pass][1]:8.3f} ms, {left} of {p} pixels not done")
-    per = ((t[12][0] - t[4][0]) / 8.0, (t[12][1] - t[4][1]) / 8.0)
-    say(f"  time per pass: {min(per):8.3f} - {max(per):8.3f} ms = {min(per) / diag[0]:.2f} of a pixel diagnostics pass")
-    if not args.no_presence:
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        res = presence.presence(X, D.cpu().numpy(), tol=tol, max_pass=args.max_pass)
-        torch.cuda.synchronize()
-        total = time.perf_counter() - t0
-        npass = res["n_pass"]
-        q = np.percentile(npass[0], [50, 99, 100])
-        say(f"  full fit: passes to the 50th / 99th / last percentile of the pixels: {q[0]:.0f} / {q[1]:.0f} / {q[2]:.0f}; "
-            f"{res['converged'][0].mean():.6f} converged (max_pass {args.max_pass})")
-        for j in range(k):
-            qj = np.percentile(npass[1 + j], [50, 99, 100])
-            say(f"  without component {j}: {qj[0]:.0f} / {qj[1]:.0f} / {qj[2]:.0f} passes; {res['converged'][1 + j].mean():.6f} converged")
-        say(f"  presence, {k + 1} nested fits, read-backs included: {total:.2f} s; median lr per component {np.median(res['lr'], axis=1)}")
+    for method in (("em", "newton") if args.method == "both" else (args.method,)):
+        entry = "espm_pixel_ml" if method == "em" else "espm_pixel_ml_newton"
+        # one pass
+        t, (few, many) = {}, ((4, 12) if method == "em" else (1, 3))
+        for n_pass in (few, many):
+            def run():
+                H, state = fresh(p, k, H0)
+                passes_call(X, D, s, H, state, n_pass, tol, method)
+                run.left = state[4]
+            # (the allocation and the clone of the fresh state are inside the events of both calls and cancel in the difference)
+            t[n_pass] = pdt.timed(run, args.runs)
+            left = int(run.left[_lib.PML_NOT_DONE])
+            say(f"  {entry}, {n_pass:2d} passes from a fresh state: {t[n_pass][0]:8.3f} - {t[n_pass][1]:8.3f} ms, {left} of {p} pixels not done")
+        per = ((t[many][0] - t[few][0]) / (many - few), (t[many][1] - t[few][1]) / (many - few))
+        say(f"  {method}: time per pass: {min(per):8.3f} - {max(per):8.3f} ms = {min(per) / diag[0]:.2f} of a pixel diagnostics pass")
+        if not args.no_presence:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = presence.presence(X, D.cpu().numpy(), tol=tol, max_pass=args.max_pass, method=method)
+            torch.cuda.synchronize()
+            total = time.perf_counter() - t0
+            npass = res["n_pass"]
+            q = np.percentile(npass[0], [50, 99, 100])
+            say(f"  {method}: full fit: passes to the 50th / 99th / last percentile of the pixels: {q[0]:.0f} / {q[1]:.0f} / {q[2]:.0f}; "
+                f"{res['converged'][0].mean():.6f} converged (max_pass {args.max_pass})")
+            for j in range(k):
+                qj = np.percentile(npass[1 + j], [50, 99, 100])
+                say(f"  {method}: without component {j}: {qj[0]:.0f} / {qj[1]:.0f} / {qj[2]:.0f} passes; {res['converged'][1 + j].mean():.6f} converged")
+            say(f"  {method}: presence, {k + 1} nested fits, read-backs included: {total:.2f} s; median lr per component {np.median(res['lr'], axis=1)}")
 
 
 if __name__ == "__main__":
