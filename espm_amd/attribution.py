@@ -18,15 +18,10 @@ from __future__ import annotations
 
 import numpy as np
 
-from espm_amd._image_args import check_model, layout_code
+from espm_amd import _image
+from espm_amd._image_args import check_image, check_log_shift, check_model, check_seed, counts_image
 
 MAX_K = 32   # ESPM_ATTRIB_MAX_K
-
-
-def _on_device(X):
-    """(Xd, dtype code, device): X on the GPU in a dtype the kernels read."""
-    from espm_amd import binning
-    return binning._on_device(X)
 
 
 def expected(X, D, H, log_shift=1e-14, layout="cm"):
@@ -40,28 +35,26 @@ def expected(X, D, H, log_shift=1e-14, layout="cm"):
     * ``unattributed`` (p,): counts - sum_j pixel_counts, non-zero only where the model fell below ``log_shift``).
 
     X: the image as measured, non-negative, (channels, pixels) for ``layout="cm"`` or (pixels, channels) for "pm" - a host array or
-    a device tensor in any dtype ``measures.pixel_diagnostics`` reads.  1 .. 32 components.  Everything in fp64, sums in a fixed
-    order, no atomics: two calls, and both layouts, give the same bits."""
-    if getattr(X, "ndim", None) != 2:
-        X = np.asarray(X)
+    a device tensor in any dtype the as-measured rule reads (``_image_args.measured_dtype``).  1 .. 32 components.  Everything in
+    fp64, sums in a fixed order, no atomics: two calls, and both layouts, give the same bits."""
+    X = check_image(X)
     n, p, k, D, H = check_model(D, H, "expected", MAX_K, tuple(X.shape), layout)
-    if not log_shift > 0:
-        raise ValueError("log_shift must be positive")
+    check_log_shift(log_shift)
     import torch
 
     from espm_amd import _lib
     from espm_amd.engine import _ptr, _stream
-    Xd, code, dev = _on_device(X)
-    with torch.cuda.device(dev):
-        Dd, Hd = torch.from_numpy(D).to(dev), torch.from_numpy(H).to(dev)
+    img = _image.Resident(X, layout).upload()
+    code, dev = img.code, img.dev
+    with img.scope():
+        Dd, Hd = img.model(D, H)
         num = torch.empty((k, p), dtype=torch.float64, device=dev)
         ratio = torch.empty((n, k), dtype=torch.float64, device=dev)
         cnt = torch.empty(p, dtype=torch.int64 if code in (_lib.DIAG_X_U8, _lib.DIAG_X_U16) else torch.float64, device=dev)
         need = int(_lib.lib.espm_attribute_expected_scratch(n, p, k))
         scratch = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
-        _lib.check(_lib.lib.espm_attribute_expected(_ptr(Xd), code, layout_code(layout), int(Xd.stride(0)), n, p,
-                                                    _ptr(Dd), _ptr(Hd), k, float(log_shift), _ptr(num), _ptr(ratio), _ptr(cnt), _ptr(scratch),
-                                                    need, _stream()))
+        _lib.check(_lib.lib.espm_attribute_expected(*img.abi(), _ptr(Dd), _ptr(Hd), k, float(log_shift), _ptr(num), _ptr(ratio), _ptr(cnt),
+                                                    _ptr(scratch), need, _stream()))
         pixel_counts, ratio_sums, counts = num.cpu().numpy(), ratio.cpu().numpy(), cnt.cpu().numpy()
     return dict(pixel_counts=pixel_counts, ratio_sums=ratio_sums, channel_counts=D * ratio_sums, counts=counts,
                 unattributed=counts - pixel_counts.sum(axis=0))
@@ -77,22 +70,21 @@ def assign(X, D, H, seed=0, layout="cm", device=False):
     X as for ``splitting.thin``: integer counts 0 .. 65535, a host array or a device tensor; TypeError for floating-point X,
     ValueError for values out of range, a bad seed or shapes that do not match, NotImplementedError for more than 32 components -
     all before anything is uploaded.  One HIP kernel: the result is a function of (X, D, H, seed) alone, bit for bit."""
-    from espm_amd import splitting
-    seed = splitting._check_seed(seed)
-    X, n, p = splitting._counts(X, layout)
+    seed = check_seed(seed)
+    X, n, p = counts_image(X, layout)
     n, p, k, D, H = check_model(D, H, "assign", MAX_K, tuple(X.shape), layout)
     import torch
 
     from espm_amd import _lib
     from espm_amd.engine import _ptr, _stream
-    Xd, code, dev = _on_device(X)
-    with torch.cuda.device(dev):
-        Dd, Hd = torch.from_numpy(D).to(dev), torch.from_numpy(H).to(dev)
+    img = _image.Resident(X, layout).upload()
+    Xd, dev = img.Xd, img.dev
+    with img.scope():
+        Dd, Hd = img.model(D, H)
         parts = torch.empty((k,) + tuple(Xd.shape), dtype=Xd.dtype, device=dev)
         cnt = torch.empty(1, dtype=torch.int64, device=dev)
-        _lib.check(_lib.lib.espm_assign_counts(_ptr(Xd), code, layout_code(layout), int(Xd.stride(0)), n, p, p, 0,
-                                               _ptr(Dd), _ptr(Hd), k, seed, _ptr(parts), int(parts.stride(0)), int(parts.stride(1)), _ptr(cnt),
-                                               _stream()))
+        _lib.check(_lib.lib.espm_assign_counts(*img.abi(), p, 0, _ptr(Dd), _ptr(Hd), k, seed, _ptr(parts), int(parts.stride(0)),
+                                               int(parts.stride(1)), _ptr(cnt), _stream()))
         invalid = int(cnt.item())
     return (parts if device else parts.cpu().numpy()), dict(invalid=invalid)
 

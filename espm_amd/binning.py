@@ -23,23 +23,23 @@ from __future__ import annotations
 
 import numpy as np
 
-from espm_amd._image_args import check_layout, image_dims, layout_code
+from espm_amd import _image
+from espm_amd._image_args import check_image, check_layout, image_dims
 
 
 def _check(X, shape_2d, layout):
-    """(n, ny, nx) before anything is uploaded."""
+    """(X, n, ny, nx) before anything is uploaded."""
     check_layout(layout)
-    if getattr(X, "ndim", None) != 2:
-        raise ValueError("X must be a 2-D array or tensor")
+    X = check_image(X)
     if shape_2d is None or len(shape_2d) != 2:
         raise ValueError("shape_2d must be (rows, columns) of the image")
     ny, nx = int(shape_2d[0]), int(shape_2d[1])
     n, p = image_dims(X.shape, layout)
-    if ny < 1 or nx < 1 or n < 1:
-        raise ValueError("X and shape_2d must not be empty")
+    if ny < 1 or nx < 1:
+        raise ValueError("shape_2d must not be empty")
     if ny * nx != p:
         raise ValueError(f"shape_2d {(ny, nx)} does not match the {p} pixels of X")
-    return n, ny, nx
+    return X, n, ny, nx
 
 
 def _check_bin(bin):
@@ -63,21 +63,6 @@ def default_bins(shape_2d):
     return [(b, b) for b in range(1, max(1, min(int(shape_2d[0]), int(shape_2d[1])) // 2) + 1)]
 
 
-def _on_device(X):
-    """(Xd, dtype code, device) of X on the GPU in a dtype the kernels read."""
-    import torch
-
-    from espm_amd import _lib
-    from espm_amd.engine import require_gpu
-    from espm_amd.measures import _diag_upload
-    is_dev = isinstance(X, torch.Tensor) and X.is_cuda
-    dev = require_gpu(X.device if is_dev else None)
-    with torch.cuda.device(dev):
-        Xd = _diag_upload(X, dev)
-    code = {torch.uint8: _lib.DIAG_X_U8, torch.uint16: _lib.DIAG_X_U16, torch.float32: _lib.DIAG_X_F32, torch.float64: _lib.DIAG_X_F64}[Xd.dtype]
-    return Xd, code, dev
-
-
 def _is_integer(X):
     import torch
     if isinstance(X, torch.Tensor):
@@ -92,15 +77,16 @@ def rebin(X, shape_2d, bin, layout="cm"):
     float32 when every bin sum is exactly representable in it - integer input with max(X) by bx < 2^24 - or when X is float32;
     float64 otherwise.  Integer input is summed exactly, floating-point input in fp64, and rounded once.  X: a host array or a
     device tensor; ``bin=(1, 1)`` returns the values unchanged.  One HIP kernel; two calls give the same bits."""
-    n, ny, nx = _check(X, shape_2d, layout)
+    X, n, ny, nx = _check(X, shape_2d, layout)
     by, bx = _check_bin(bin)
     import torch
 
     from espm_amd import _lib
     from espm_amd.engine import _ptr, _stream
     integer = _is_integer(X)
-    Xd, code, dev = _on_device(X)
-    with torch.cuda.device(dev):
+    img = _image.Resident(X, layout).upload()
+    Xd, dev = img.Xd, img.dev
+    with img.scope():
         if integer:   # (torch has no reductions on 16-bit unsigned tensors: those go through a wider copy)
             top = np.asarray(X).max() if not isinstance(X, torch.Tensor) else (Xd.to(torch.int32) if Xd.dtype == torch.uint16 else Xd).max().item()
             f32 = int(top) * min(by, ny) * min(bx, nx) < (1 << 24)
@@ -108,8 +94,8 @@ def rebin(X, shape_2d, bin, layout="cm"):
             f32 = Xd.dtype == torch.float32
         gny, gnx = binned_shape((ny, nx), (by, bx))
         out = torch.empty((n, gny * gnx) if layout == "cm" else (gny * gnx, n), dtype=torch.float32 if f32 else torch.float64, device=dev)
-        _lib.check(_lib.lib.espm_rebin_pixels(_ptr(Xd), code, layout_code(layout), int(Xd.stride(0)), n, ny, nx,
-                                              by, bx, _ptr(out), _lib.DIAG_X_F32 if f32 else _lib.DIAG_X_F64, int(out.stride(0)), _stream()))
+        _lib.check(_lib.lib.espm_rebin_pixels(*img.abi()[:5], ny, nx, by, bx, _ptr(out), _lib.DIAG_X_F32 if f32 else _lib.DIAG_X_F64,
+                                              int(out.stride(0)), _stream()))
         return out.cpu().numpy()
 
 
@@ -117,7 +103,7 @@ def binning_sums(X, shape_2d, bins, layout="cm"):
     """(T1, T2, A, C): sum x and sum x^2 over the cube, and per candidate of ``bins`` A = sum_gc S_gc^2 / n_g and
     C = sum_gc S_gc / n_g (float64 arrays of len(bins)).  One pass over X for the totals and one per candidate, fp64, without atomics:
     two calls give the same bits."""
-    n, ny, nx = _check(X, shape_2d, layout)
+    X, n, ny, nx = _check(X, shape_2d, layout)
     bins = [_check_bin(b) for b in bins]
     if not bins:
         raise ValueError("bins must hold at least one (by, bx)")
@@ -125,15 +111,15 @@ def binning_sums(X, shape_2d, bins, layout="cm"):
 
     from espm_amd import _lib
     from espm_amd.engine import _ptr, _stream
-    Xd, code, dev = _on_device(X)
+    img = _image.Resident(X, layout).upload()
+    dev = img.dev
     nb = len(bins)
     host_bins = np.ascontiguousarray(np.asarray(bins, dtype=np.int32).reshape(nb, 2))
-    with torch.cuda.device(dev):
+    with img.scope():
         out = torch.empty(2 + 2 * nb, dtype=torch.float64, device=dev)
         nbytes = int(_lib.lib.espm_binning_sums_scratch(n, ny, nx, nb))
         scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        _lib.check(_lib.lib.espm_binning_sums(_ptr(Xd), code, layout_code(layout), int(Xd.stride(0)), n, ny, nx,
-                                              host_bins.ctypes.data, nb, _ptr(out), _ptr(scratch), nbytes, _stream()))
+        _lib.check(_lib.lib.espm_binning_sums(*img.abi()[:5], ny, nx, host_bins.ctypes.data, nb, _ptr(out), _ptr(scratch), nbytes, _stream()))
         host = out.cpu().numpy()
     return float(host[0]), float(host[1]), host[2::2].copy(), host[3::2].copy()
 
@@ -150,7 +136,7 @@ def risk_from_sums(T1, T2, A, C, n, ny, nx):
 def binning_risk(X, shape_2d, bins=None, layout="cm"):
     """(bins, var, bias, risk): the reference's variance and squared-bias estimates and their combination for every candidate;
     ``bins=None``: ``default_bins(shape_2d)``."""
-    n, ny, nx = _check(X, shape_2d, layout)
+    X, n, ny, nx = _check(X, shape_2d, layout)
     bins = default_bins((ny, nx)) if bins is None else [_check_bin(b) for b in bins]
     T1, T2, A, C = binning_sums(X, (ny, nx), bins, layout=layout)
     var, bias, risk = risk_from_sums(T1, T2, A, C, n, ny, nx)

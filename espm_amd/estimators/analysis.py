@@ -157,11 +157,11 @@ class _FitAnalysis:
         X: integer counts 0 .. 65535 - a host array or a device tensor, (channels, pixels), or (pixels, channels) with ``hspy_comp``;
         TypeError for floating-point X, ValueError for values out of range, before anything is uploaded.  Every solver, G kind and
         precision mode, 1 .. 32 components; ``shard()``ed estimators raise NotImplementedError before anything is uploaded."""
-        from espm_amd import splitting
+        from espm_amd import _image, splitting
         self._split_refusal()
         layout = self._layout()
         Xd = splitting._resident(X, q, seed, layout)   # (one upload for the split and the score: 1 or 2 bytes per entry stay on the device)
-        Xa = splitting._to_host(splitting._thin(Xd, q, seed, layout, False)[0])
+        Xa = _image.to_host(splitting._thin(Xd, q, seed, layout, False)[0])
         return self._fit_split_stages(Xd, Xa, q, seed, layout, W=W, H=H)
 
     def _fit_split_stages(self, X, Xa, q, seed, layout, W=None, H=None):
@@ -409,7 +409,7 @@ class _FitAnalysis:
         device; with one the refusals of ``simulate`` apply (``shard()``: NotImplementedError, ``fit_binned``: ValueError) - all
         before anything is uploaded."""
         from espm_amd import residuals, sampling
-        from espm_amd.splitting import _check_seed
+        from espm_amd._image_args import check_seed
         check_is_fitted(self, "W_")
         k = int(self.H_.shape[0])
         if k > residuals.MAX_K:
@@ -418,7 +418,7 @@ class _FitAnalysis:
         residuals._check_iteration(n_vectors, 1e-10, 60, n, p)
         if isinstance(n_null, bool) or int(n_null) != n_null or int(n_null) < 0:
             raise ValueError(f"n_null must be a non-negative integer, not {n_null!r}")
-        n_null, seed = int(n_null), _check_seed(seed)
+        n_null, seed = int(n_null), check_seed(seed)
         if n_null:
             self._sampling_model("residual_components")
             sampling._check_replicate(0, n_null)
@@ -531,12 +531,12 @@ class _FitAnalysis:
         ``X`` as for ``pixel_diagnostics``; 1 .. 8 components, the diagnostics' limit; at least 2 replicates.  Refusals as for
         ``simulate``, before anything is uploaded."""
         from espm_amd import sampling
-        from espm_amd.splitting import _check_seed
+        from espm_amd._image_args import check_seed
         D, H = self._sampling_model("calibrate_deviance")
         n_rep = sampling._check_n_rep(n_rep)
         if n_rep < 2:
             raise ValueError("calibrate_deviance needs at least two replicates (the null standard deviation has ddof = 1)")
-        _check_seed(seed)
+        check_seed(seed)
         self.pixel_diagnostics(X)
         null = sampling.null_deviance(D, H, n_rep=n_rep, seed=seed, replicate0=0, log_shift=self.log_shift)
         cal = sampling.calibrate(self.deviance_, null)
@@ -578,9 +578,9 @@ class _FitAnalysis:
         with ``return_samples=True`` the dict also holds ``W_samples`` (n_boot, ...) and ``H_samples`` (n_boot, k, p) for
         percentile intervals.  At least 2 replicates; refusals as for ``simulate``, before anything is uploaded."""
         from espm_amd import sampling
-        from espm_amd.splitting import _check_seed
+        from espm_amd._image_args import check_seed
         D, H = self._sampling_model("bootstrap")
-        n_boot, seed = sampling._check_n_rep(n_boot), _check_seed(seed)
+        n_boot, seed = sampling._check_n_rep(n_boot), check_seed(seed)
         if n_boot < 2:
             raise ValueError("bootstrap needs at least two replicates (the standard deviations have ddof = 1)")
         sampling._check_replicate(0, n_boot)

@@ -18,7 +18,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from espm_amd._image_args import check_layout, check_model, image_dims, layout_code
+from espm_amd import _image
+from espm_amd._image_args import check_image, check_layout, check_log_shift, check_model, image_dims, narrowed_image
 
 MAX_G = 8    # ESPM_MARG_MAX_G: weight vectors per launch (any number is accepted, in batches)
 MAX_K = 8    # ESPM_MARG_MAX_K: components of a model on the device
@@ -113,42 +114,6 @@ def label_weights(labels, n_regions=None):
 
 
 # ---- the sums ----------------------------------------------------------------------------------------------------------------------
-def _on_device(X):
-    """(Xd, dtype code, device): X on the GPU in a dtype the kernels read."""
-    from espm_amd import binning
-    return binning._on_device(X)
-
-
-def _image(X, who):
-    """X as it goes to the device: 8- and 16-bit counts, float32 and float64 as they are; other integer dtypes narrowed to uint8 or
-    uint16 where the values allow (else as ``measures.pixel_diagnostics`` converts them); ValueError for negative integers and for
-    values that are not finite - a NaN under a zero weight would be skipped and elsewhere poison its sums.  Host arrays are checked
-    on the host, before anything is uploaded; device tensors where they are."""
-    try:
-        import torch
-        tensor = isinstance(X, torch.Tensor)
-    except ImportError:   # (the builders and checks work without torch)
-        tensor = False
-    if tensor:
-        if X.dtype.is_floating_point:
-            if not bool(torch.isfinite(X).all()):
-                raise ValueError(f"{who}: X holds values that are not finite")
-        return X
-    X = np.asarray(X)
-    if X.dtype.kind == "f":
-        if not np.isfinite(X).all():
-            raise ValueError(f"{who}: X holds values that are not finite")
-    elif X.dtype.kind in "iu" and X.dtype not in (np.uint8, np.uint16):
-        lo, hi = int(X.min()), int(X.max())
-        if lo < 0:
-            raise ValueError(f"{who}: X holds values from {lo} to {hi}: counts are not negative")
-        if hi <= 65535:
-            X = X.astype(np.uint8 if hi <= 255 else np.uint16)
-    elif X.dtype.kind not in "iub":
-        raise TypeError(f"{who}: X of dtype {X.dtype} is not an image of counts")
-    return X
-
-
 def _weights(W, m, axis, who):
     W = np.asarray(W, dtype=np.float64)
     if W.ndim == 1:
@@ -163,40 +128,36 @@ def _weights(W, m, axis, who):
 def _sums(X, weights, D, H, log_shift, layout, pixel_side, who):
     """(xs, ys, dev), each (g, p) for the pixel side and (g, n) for the channel side; ys and dev None without a model."""
     check_layout(layout)
-    if getattr(X, "ndim", None) != 2:
-        X = np.asarray(X)
-    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
-        raise ValueError("X must be a non-empty 2-D array or tensor")
+    X = check_image(X)
     if (D is None) != (H is None):
         raise ValueError(f"{who}: a model is D and H together")
     if D is not None:
         n, p, k, D, H = check_model(D, H, who, MAX_K, tuple(X.shape), layout)
-        if not log_shift > 0:
-            raise ValueError("log_shift must be positive")
+        check_log_shift(log_shift)
     else:
         (n, p), k = image_dims(X.shape, layout), 0
     W = _weights(weights, n if pixel_side else p, "channels" if pixel_side else "pixels", who)
-    X = _image(X, who)
+    X = narrowed_image(X, who)
     import torch
 
     from espm_amd import _lib
     from espm_amd.engine import _ptr, _stream
-    Xd, code, dev = _on_device(X)
+    img = _image.Resident(X, layout).upload()
+    dev = img.dev
     side = _lib.MARG_PIXELS if pixel_side else _lib.MARG_CHANNELS
     g, m = W.shape[0], (p if pixel_side else n)
     xs = np.empty((g, m))
     ys, dv = (np.empty((g, m)), np.empty((g, m))) if k else (None, None)
-    with torch.cuda.device(dev):
-        Dd, Hd = (torch.from_numpy(D).to(dev), torch.from_numpy(H).to(dev)) if k else (None, None)
+    with img.scope():
+        Dd, Hd = img.model(D, H)
         need = int(_lib.lib.espm_weighted_marginals_scratch(side, n, p, min(g, MAX_G)))
         scratch = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
         for b in range(0, g, MAX_G):
             Wd = torch.from_numpy(W[b:b + MAX_G]).to(dev)
             gb = int(Wd.shape[0])
             out = [torch.empty((gb, m), dtype=torch.float64, device=dev) for _ in range(3 if k else 1)] + [None, None]
-            _lib.check(_lib.lib.espm_weighted_marginals(_ptr(Xd), code, layout_code(layout), int(Xd.stride(0)), n, p, side, _ptr(Wd), gb,
-                                                        _ptr(Dd), _ptr(Hd), k, float(log_shift), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
-                                                        _ptr(scratch), need, _stream()))
+            _lib.check(_lib.lib.espm_weighted_marginals(*img.abi(), side, _ptr(Wd), gb, _ptr(Dd), _ptr(Hd), k, float(log_shift), _ptr(out[0]),
+                                                        _ptr(out[1]), _ptr(out[2]), _ptr(scratch), need, _stream()))
             xs[b:b + gb] = out[0].cpu().numpy()
             if k:
                 ys[b:b + gb], dv[b:b + gb] = out[1].cpu().numpy(), out[2].cpu().numpy()
@@ -251,10 +212,7 @@ def line_maps(X, lines, D=None, H=None, layout="cm"):
     The model terms are linear in the UNFLOORED model D H and are small host products in fp64 - no pass over X - so any k up to 32
     works here.  X, ``layout`` and the refusals as for ``pixel_maps``."""
     check_layout(layout)
-    if getattr(X, "ndim", None) != 2:
-        X = np.asarray(X)
-    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
-        raise ValueError("X must be a non-empty 2-D array or tensor")
+    X = check_image(X)
     if (D is None) != (H is None):
         raise ValueError("line_maps: a model is D and H together")
     n, p = image_dims(X.shape, layout)

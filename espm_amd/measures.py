@@ -5,7 +5,8 @@ import ctypes as C
 
 import numpy as np
 
-from espm_amd._image_args import check_layout, image_dims, layout_code
+from espm_amd import _image
+from espm_amd._image_args import check_image, check_log_shift, check_model
 from espm_amd.conf import log_shift
 
 
@@ -250,71 +251,6 @@ def Frobenius_loss(X, W, H, average=False):
 
 
 # ---- per-pixel diagnostics of a fitted model (csrc/mu_diag.hip) ------------------------------------------------------------------
-_DIAG_UPLOAD_ENTRIES = 16 << 20   # entries of a host X per upload step
-
-
-def _diag_host_dtype(dt):
-    """The dtype a host X of dtype ``dt`` goes to the device in: u8, u16, f32 and f64 as they are, the others as f32 or f64,
-    whichever holds every value exactly (64-bit integers: f64, exact up to 2^53)."""
-    dt = np.dtype(dt)
-    if dt in (np.uint8, np.uint16, np.float32, np.float64):
-        return dt
-    if dt == np.bool_:
-        return np.dtype(np.uint8)
-    if dt in (np.int8, np.int16, np.float16):
-        return np.dtype(np.float32)
-    if dt.kind in "iu" or dt.kind == "f":
-        return np.dtype(np.float64)
-    raise TypeError(f"pixel_diagnostics: X of dtype {dt} is not an image of counts")
-
-
-def _diag_check(X, D, H, layout, log_shift):
-    """Shapes and arguments of pixel_diagnostics, before any device is touched: (n, p, k, D, H) with D, H as C-contiguous fp64."""
-    check_layout(layout)
-    if getattr(X, "ndim", None) != 2:
-        raise ValueError("X must be a 2-D array or tensor")
-    D = np.ascontiguousarray(D, dtype=np.float64)
-    H = np.ascontiguousarray(H, dtype=np.float64)
-    if D.ndim != 2 or H.ndim != 2 or D.shape[1] != H.shape[0]:
-        raise ValueError(f"D must be (channels, k) and H (k, pixels): got {D.shape} and {H.shape}")
-    n, p = image_dims(X.shape, layout)
-    k = int(D.shape[1])
-    if D.shape[0] != n:
-        raise ValueError(f"X has {n} channels, D has {D.shape[0]}")
-    if H.shape[1] != p:
-        raise ValueError(f"X has {p} pixels, H has {H.shape[1]}")
-    if n < 1 or p < 1 or k < 1:
-        raise ValueError("X, D and H must not be empty")
-    if not log_shift > 0:
-        raise ValueError("log_shift must be positive")
-    from espm_amd import _lib
-    if k > _lib.DIAG_MAX_K:
-        raise NotImplementedError(f"pixel_diagnostics: {k} components (the kernel is built for 1..{_lib.DIAG_MAX_K})")
-    return n, p, k, D, H
-
-
-def _diag_upload(X, dev):
-    """X on ``dev`` in a dtype the kernel reads, with its row stride: a device tensor stays where it is (converted there only when
-    its dtype needs it); a host array goes up in row chunks in its own dtype - no fp64 copy of the image, on either side."""
-    import torch
-
-    if isinstance(X, torch.Tensor):
-        Xd = X.to(dev)
-        if Xd.dtype not in (torch.uint8, torch.uint16, torch.float32, torch.float64):
-            exact32 = Xd.dtype in (torch.int8, torch.int16, torch.float16, torch.bool)
-            Xd = Xd.to(torch.uint8 if Xd.dtype == torch.bool else torch.float32 if exact32 else torch.float64)
-        if Xd.stride(1) != 1 or Xd.stride(0) < Xd.shape[1]:
-            Xd = Xd.contiguous()
-        return Xd
-    X = np.asarray(X)
-    dt = _diag_host_dtype(X.dtype)
-    Xd = torch.empty(X.shape, dtype=getattr(torch, dt.name), device=dev)
-    step = max(1, _DIAG_UPLOAD_ENTRIES // max(1, X.shape[1]))
-    for a in range(0, X.shape[0], step):
-        Xd[a:a + step].copy_(torch.from_numpy(np.ascontiguousarray(X[a:a + step], dtype=dt)))
-    return Xd
-
-
 def pixel_diagnostics(X, D, H, *, simplex_H=False, log_shift=log_shift, layout="cm", device=None):
     """Where the model D H fails and how well every abundance is known: per pixel j, with Y = max(D H, log_shift),
 
@@ -333,25 +269,23 @@ def pixel_diagnostics(X, D, H, *, simplex_H=False, log_shift=log_shift, layout="
     are read as they are; other integer dtypes and float16 are converted to f32 or f64, whichever holds them exactly.  D (n, k) is
     G W in counts, H (k, p); 1..8 components.  Everything is computed in fp64 by one HIP kernel; there is no CPU path.  Returns a
     dict of float64 numpy arrays and the int ``n_singular``."""
-    n, p, k, D, H = _diag_check(X, D, H, layout, log_shift)
+    from espm_amd import _lib
+    X = check_image(X)
+    n, p, k, D, H = check_model(D, H, "pixel_diagnostics", _lib.DIAG_MAX_K, tuple(X.shape), layout)
+    check_log_shift(log_shift)
     import torch
 
-    from espm_amd import _lib
-    from espm_amd.engine import _ptr, _stream, require_gpu
+    from espm_amd.engine import _ptr, _stream
 
-    is_dev = isinstance(X, torch.Tensor) and X.is_cuda
-    dev = require_gpu(device if device is not None else (X.device if is_dev else None))
-    with torch.cuda.device(dev):
-        Xd = _diag_upload(X, dev)
-        code = {torch.uint8: _lib.DIAG_X_U8, torch.uint16: _lib.DIAG_X_U16, torch.float32: _lib.DIAG_X_F32,
-                torch.float64: _lib.DIAG_X_F64}[Xd.dtype]
-        Dd, Hd = torch.from_numpy(D).to(dev), torch.from_numpy(H).to(dev)
+    img = _image.Resident(X, layout, device).upload()
+    dev = img.dev
+    with img.scope():
+        Dd, Hd = img.model(D, H)
         dv = torch.empty(p, dtype=torch.float64, device=dev)
         hs = torch.empty((k, p), dtype=torch.float64, device=dev)
         ns = torch.zeros(1, dtype=torch.int32, device=dev)
-        _lib.check(_lib.lib.espm_pixel_diagnostics(_ptr(Xd), code, layout_code(layout), int(Xd.stride(0)),
-                                                   n, p, _ptr(Dd), _ptr(Hd), k, float(log_shift), int(bool(simplex_H)), _ptr(dv), _ptr(hs),
-                                                   _ptr(ns), _stream()))
+        _lib.check(_lib.lib.espm_pixel_diagnostics(*img.abi(), _ptr(Dd), _ptr(Hd), k, float(log_shift), int(bool(simplex_H)), _ptr(dv),
+                                                   _ptr(hs), _ptr(ns), _stream()))
         return dict(deviance=dv.cpu().numpy(), H_std=hs.cpu().numpy(), n_singular=int(ns.item()))
 
 
@@ -513,25 +447,23 @@ def spectral_diagnostics(X, D_or_W, H, *, G=None, simplex_rows=None, log_shift=l
         D = G @ W
     else:
         D = W
-    n, p, k, D, H = _diag_check(X, D, H, layout, log_shift)
+    X = check_image(X)
+    n, p, k, D, H = check_model(D, H, "spectral_diagnostics", _lib.DIAG_MAX_K, tuple(X.shape), layout)
+    check_log_shift(log_shift)
     _simplex_rows(simplex_rows, W.shape[0])   # (an index out of range: before the upload)
     import torch
 
-    from espm_amd.engine import _ptr, _stream, require_gpu
+    from espm_amd.engine import _ptr, _stream
 
-    is_dev = isinstance(X, torch.Tensor) and X.is_cuda
-    dev = require_gpu(device if device is not None else (X.device if is_dev else None))
+    img = _image.Resident(X, layout, device).upload()
+    dev = img.dev
     nt = k * (k + 1) // 2
-    with torch.cuda.device(dev):
-        Xd = _diag_upload(X, dev)
-        code = {torch.uint8: _lib.DIAG_X_U8, torch.uint16: _lib.DIAG_X_U16, torch.float32: _lib.DIAG_X_F32,
-                torch.float64: _lib.DIAG_X_F64}[Xd.dtype]
-        Dd, Hd = torch.from_numpy(D).to(dev), torch.from_numpy(H).to(dev)
+    with img.scope():
+        Dd, Hd = img.model(D, H)
         out = torch.empty((3 + nt) * n, dtype=torch.float64, device=dev)   # dev, xsum, ysum, then m_tri (n, nt)
         nbytes = int(_lib.lib.espm_channel_diagnostics_scratch(n, p, k))
         scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        _lib.check(_lib.lib.espm_channel_diagnostics(_ptr(Xd), code, layout_code(layout),
-                                                     int(Xd.stride(0)), n, p, _ptr(Dd), _ptr(Hd), k, float(log_shift), _ptr(out[:n]),
+        _lib.check(_lib.lib.espm_channel_diagnostics(*img.abi(), _ptr(Dd), _ptr(Hd), k, float(log_shift), _ptr(out[:n]),
                                                      _ptr(out[n:2 * n]), _ptr(out[2 * n:3 * n]), _ptr(out[3 * n:]), _ptr(scratch),
                                                      nbytes, _stream()))
         host = out.cpu().numpy()

@@ -22,7 +22,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from espm_amd._image_args import check_layout, image_dims, layout_code
+from espm_amd import _image
+from espm_amd._image_args import check_image, check_layout, check_log_shift, image_dims, narrowed_image
 
 MAX_K = 8            # ESPM_PML_MAX_K: components of the model
 MAX_PASS = 20000     # the default cap of the passes of a pixel
@@ -34,12 +35,6 @@ def _check_method(method):
     if method not in METHODS:
         raise ValueError(f"method must be one of {METHODS}, not {method!r}")
     return method
-
-
-def _on_device(X):
-    """(Xd, dtype code, device): X on the GPU in a dtype the kernel reads (the marginals' rule)."""
-    from espm_amd import marginals
-    return marginals._on_device(X)
 
 
 def _positive_int(v, name):
@@ -62,16 +57,13 @@ def _components(components, k):
 
 
 class _Solver:
-    """X and the spectra, checked on the host and then uploaded ONCE: every ``run`` is a nested fit on the resident image."""
+    """X and the spectra, checked on the host and then uploaded ONCE (``image``, by the narrowing rule): every ``run`` is a nested
+    fit on the resident image.  The component sets, the start and the solver's state are its own."""
 
     def __init__(self, X, D, tol, max_pass, chunk, log_shift, layout, who, method="em"):
-        from espm_amd import marginals
         check_layout(layout)
         self.method = _check_method(method)
-        if getattr(X, "ndim", None) != 2:
-            X = np.asarray(X)
-        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
-            raise ValueError("X must be a non-empty 2-D array or tensor")
+        X = check_image(X)
         D = np.ascontiguousarray(D, dtype=np.float64)
         if D.ndim != 2 or D.size == 0:
             raise ValueError("D must be (channels, components), not empty")
@@ -81,8 +73,7 @@ class _Solver:
             raise ValueError(f"X has {self.n} channels, D has {D.shape[0]}")
         if self.k > MAX_K:
             raise NotImplementedError(f"{who}: {self.k} components (the kernels are built for 1..{MAX_K})")
-        if not log_shift > 0:
-            raise ValueError("log_shift must be positive")
+        check_log_shift(log_shift)
         if not tol > 0:
             raise ValueError("tol must be positive")
         self.max_pass, self.chunk = _positive_int(max_pass, "max_pass"), _positive_int(chunk, "chunk")
@@ -90,8 +81,7 @@ class _Solver:
             raise ValueError(f"{who}: D must be finite and not negative")
         self.who, self.layout, self.log_shift, self.tol = who, layout, float(log_shift), float(tol)
         self.D, self.s = D, np.ascontiguousarray(D.sum(axis=0))
-        self._host = marginals._image(X, who)
-        self.Xd = None
+        self.image, self.Dd = _image.Resident(narrowed_image(X, who), layout), None
 
     def check_start(self, H0):
         if H0 is None:
@@ -111,20 +101,16 @@ class _Solver:
         return comp, mask
 
     def upload(self):
-        if self.Xd is not None:
-            return
-        import torch
-        self.Xd, self.code, self.dev = _on_device(self._host)
-        self._host = None
-        with torch.cuda.device(self.dev):
-            self.Dd = torch.from_numpy(self.D).to(self.dev)
+        if self.Dd is None:
+            self.dev = self.image.upload().dev
+            self.Dd, = self.image.model(self.D)
 
     def counts(self):
         """N (p,) on the device: the counts of every pixel (the marginals' pass under all-ones weights: exact for integers)."""
         import torch
 
         from espm_amd import marginals
-        N = marginals.pixel_maps(self.Xd, np.ones((1, self.n)), layout=self.layout)["counts"][0]
+        N = marginals.pixel_maps(self.image.Xd, np.ones((1, self.n)), layout=self.layout)["counts"][0]
         return torch.from_numpy(np.ascontiguousarray(N)).to(self.dev)
 
     def run(self, start, comp, mask):
@@ -138,7 +124,7 @@ class _Solver:
         from espm_amd.engine import _ptr, _stream
         self.upload()
         k, p = self.k, self.p
-        with torch.cuda.device(self.dev):
+        with self.image.scope():
             if start is None:
                 Hd = torch.zeros((k, p), dtype=torch.float64, device=self.dev)
                 Hd[comp] = (self.counts() / float(self.s[comp].sum()))[None, :]
@@ -151,8 +137,7 @@ class _Solver:
             done = torch.zeros(p, dtype=torch.uint8, device=self.dev)
             counters = torch.zeros(3, dtype=torch.int64, device=self.dev)
             s_ptr = self.s.ctypes.data_as(C.c_void_p)
-            args = (_ptr(self.Xd), self.code, layout_code(self.layout), int(self.Xd.stride(0)), self.n, p, _ptr(self.Dd), s_ptr, k, mask,
-                    self.log_shift, self.tol)
+            args = (*self.image.abi(), _ptr(self.Dd), s_ptr, k, mask, self.log_shift, self.tol)
             state = (_ptr(Hd), _ptr(dv), _ptr(gp), _ptr(passes), _ptr(done), _ptr(counters))
             if self.method == "newton":   # the rule's own scratch (e, dev_acc, tau, trial per pixel): the kernel initialises it
                 extra = torch.empty((k + _lib.PMLN_STATE_EXTRA, p), dtype=torch.float64, device=self.dev)
@@ -171,10 +156,11 @@ class _Solver:
                     nonfinite=int(cnt[_lib.PML_NONFINITE]))
 
 
-def _to_host(r):
-    done = r["done"].cpu().numpy()
-    return dict(H=r["H"].cpu().numpy(), deviance=r["deviance"].cpu().numpy(), gap=r["gap"].cpu().numpy(),
-                n_pass=r["n_pass"].cpu().numpy().astype(np.int64), converged=done == 1, unmodelled=r["unmodelled"], nonfinite=r["nonfinite"])
+def _result(r):
+    """A ``run``'s dict on the host, as ``ml_unmix`` returns it."""
+    t = _image.to_host
+    return dict(H=t(r["H"]), deviance=t(r["deviance"]), gap=t(r["gap"]), n_pass=t(r["n_pass"]).astype(np.int64),
+                converged=t(r["done"]) == 1, unmodelled=r["unmodelled"], nonfinite=r["nonfinite"])
 
 
 def ml_unmix(X, D, H0=None, components=None, tol=1e-3, max_pass=MAX_PASS, chunk=CHUNK, log_shift=1e-14, layout="cm", method="em"):
@@ -195,15 +181,15 @@ def ml_unmix(X, D, H0=None, components=None, tol=1e-3, max_pass=MAX_PASS, chunk=
       stopped at a value that is not finite (they are not converged)).
 
     X: the image as measured, (channels, pixels) for ``layout="cm"`` or (pixels, channels) for "pm", a host array or a device tensor,
-    checked and uploaded ONCE by the marginals' rules.  D (n, k): 1 .. 8 components (NotImplementedError beyond), finite, not negative;
-    a component of the set needs a spectrum that is not all zero.  ``H0`` (k, p): the start; an entry of the set that is not > 0 is
+    checked and uploaded ONCE by the narrowing rule (``_image_args.narrowed_image``).  D (n, k): 1 .. 8 components
+    (NotImplementedError beyond), finite, not negative; a component of the set needs a spectrum that is not all zero.  ``H0`` (k, p): the start; an entry of the set that is not > 0 is
     replaced by N / (|set| s_j) * 1e-3; None: N / sum_set s.  ``chunk``: the passes per launch (the results do not depend on it).
     ValueError for shapes that do not match, ``tol`` or ``log_shift`` not positive, X, D or H0 not finite and a ``method`` that does
     not exist - before anything is uploaded."""
     sv = _Solver(X, D, tol, max_pass, chunk, log_shift, layout, "ml_unmix", method)
     start = sv.check_start(H0)
     comp, mask = sv.check_components(components)
-    return _to_host(sv.run(start, comp, mask))
+    return _result(sv.run(start, comp, mask))
 
 
 def _empty_model_deviance(X, layout, log_shift):
@@ -250,10 +236,10 @@ def presence(X, D, H0=None, tol=1e-3, max_pass=MAX_PASS, chunk=CHUNK, log_shift=
     start = sv.check_start(H0)
     comp, mask = sv.check_components(None)
     k, p = sv.k, sv.p
-    held = sv._host if k == 1 else None
+    held = sv.image.host if k == 1 else None
     full = sv.run(start, comp, mask)
     without = np.empty((k, p))
-    rows = [_to_host(full)]
+    rows = [_result(full)]
     for j in range(k):
         if k == 1:
             without[j] = _empty_model_deviance(held, layout, sv.log_shift)
@@ -262,7 +248,7 @@ def presence(X, D, H0=None, tol=1e-3, max_pass=MAX_PASS, chunk=CHUNK, log_shift=
         Hs = full["H"].clone()
         Hs[j] = 0.0
         rest = [i for i in comp if i != j]
-        red = _to_host(sv.run(Hs, rest, mask & ~(1 << j)))
+        red = _result(sv.run(Hs, rest, mask & ~(1 << j)))
         without[j] = red["deviance"]
         rows.append(red)
     lr = np.maximum(without - rows[0]["deviance"][None, :], 0.0)

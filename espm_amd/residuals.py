@@ -25,7 +25,9 @@ from __future__ import annotations
 
 import numpy as np
 
-from espm_amd._image_args import check_layout, check_model, layout_code
+from espm_amd import _image
+from espm_amd._image_args import (check_image, check_layout, check_log_shift, check_model, check_seed, image_dims, is_tensor,
+                                  narrowed_image)
 
 MAX_G = 8        # ESPM_RESID_MAX_G: vectors per launch (any number is accepted, in batches)
 MAX_K = 8        # ESPM_RESID_MAX_K: components of the model
@@ -33,24 +35,10 @@ BLOCK = 8        # the block of the subspace iteration: the vectors asked for an
 MAX_VECTORS = 6  # singular triplets svd returns at most
 
 
-def _on_device(X):
-    """(Xd, dtype code, device): X on the GPU in a dtype the kernels read (the marginals' rule)."""
-    from espm_amd import marginals
-    return marginals._on_device(X)
-
-
 def _side(side):
     if side not in ("pixels", "channels"):
         raise ValueError(f"side must be 'pixels' (E^T U, a value per pixel) or 'channels' (E V, a value per channel), not {side!r}")
     return side == "pixels"
-
-
-def _is_tensor(v):
-    try:
-        import torch
-    except ImportError:
-        return False
-    return isinstance(v, torch.Tensor)
 
 
 def _host_vectors(V, m, axis, who):
@@ -65,31 +53,25 @@ def _host_vectors(V, m, axis, who):
 
 
 class _Pass:
-    """X and a model, checked on the host and then uploaded ONCE: every ``run`` is a pass over the resident image."""
+    """X and a model, checked on the host and then uploaded ONCE (``image``, by the narrowing rule): every ``run`` is a pass over
+    the resident image.  The vectors and the scratch are its own."""
 
     def __init__(self, X, D, H, log_shift, layout, who):
-        from espm_amd import marginals
         check_layout(layout)
-        if getattr(X, "ndim", None) != 2:
-            X = np.asarray(X)
-        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
-            raise ValueError("X must be a non-empty 2-D array or tensor")
+        X = check_image(X)
         if D is None or H is None:
             raise ValueError(f"{who}: a model D (channels, components), H (components, pixels) is required")
         self.n, self.p, self.k, D, H = check_model(D, H, who, MAX_K, tuple(X.shape), layout)
-        if not log_shift > 0:
-            raise ValueError("log_shift must be positive")
+        self.who, self.log_shift = who, check_log_shift(log_shift)
         for name, A in (("D", D), ("H", H)):
             if not np.isfinite(A).all():
                 raise ValueError(f"{who}: {name} holds values that are not finite")
-        self.who, self.layout, self.log_shift = who, layout, float(log_shift)
-        self._host = (marginals._image(X, who), D, H)
-        self.Xd = None
+        self.image, self._model, self.scratch = _image.Resident(narrowed_image(X, who), layout), (D, H), None
 
     def check_vectors(self, vectors, pixel_side):
         """The vectors as they go to the device: a checked host array, or a device tensor checked where it is."""
         m, axis = (self.n, "channels") if pixel_side else (self.p, "pixels")
-        if not _is_tensor(vectors):
+        if not is_tensor(vectors):
             return _host_vectors(vectors, m, axis, self.who)
         import torch
         V = vectors if vectors.ndim == 2 else vectors[None, :]
@@ -102,18 +84,17 @@ class _Pass:
         return V
 
     def upload(self):
-        if self.Xd is not None:
+        if self.scratch is not None:
             return
         import torch
 
         from espm_amd import _lib
-        X, D, H = self._host
-        self.Xd, self.code, self.dev = _on_device(X)
-        with torch.cuda.device(self.dev):
-            self.Dd, self.Hd = torch.from_numpy(D).to(self.dev), torch.from_numpy(H).to(self.dev)
+        self.dev = self.image.upload().dev
+        with self.image.scope():
+            self.Dd, self.Hd = self.image.model(*self._model)
             self.need = int(_lib.lib.espm_residual_products_scratch(_lib.RESID_CHANNELS, self.n, self.p, MAX_G))
             self.scratch = torch.empty(max(self.need, 8), dtype=torch.uint8, device=self.dev)
-        self._host = None
+        self._model = None
 
     def run(self, vectors, pixel_side, chi2=False, device=False):
         """dict(out (g, p) or (g, n), chi2 or None, unmodelled) for checked ``vectors``; ``device``: out and chi2 stay on the GPU."""
@@ -124,16 +105,15 @@ class _Pass:
         self.upload()
         side = _lib.RESID_PIXELS if pixel_side else _lib.RESID_CHANNELS
         m = self.p if pixel_side else self.n
-        with torch.cuda.device(self.dev):
-            V = vectors.to(self.dev).contiguous() if _is_tensor(vectors) else torch.from_numpy(vectors).to(self.dev)
+        with self.image.scope():
+            V = vectors.to(self.dev).contiguous() if is_tensor(vectors) else torch.from_numpy(vectors).to(self.dev)
             g = int(V.shape[0])
             out = torch.empty((g, m), dtype=torch.float64, device=self.dev)
             c2 = torch.empty(m, dtype=torch.float64, device=self.dev) if chi2 else None
             un = torch.zeros(1, dtype=torch.int64, device=self.dev)
             for b in range(0, g, MAX_G):   # (chi2 and the count belong to E, not to the vectors: the first batch forms them)
                 gb = min(MAX_G, g - b)
-                _lib.check(_lib.lib.espm_residual_products(_ptr(self.Xd), self.code, layout_code(self.layout), int(self.Xd.stride(0)), self.n,
-                                                           self.p, side, _ptr(V[b:b + gb]), gb, _ptr(self.Dd), _ptr(self.Hd), self.k,
+                _lib.check(_lib.lib.espm_residual_products(*self.image.abi(), side, _ptr(V[b:b + gb]), gb, _ptr(self.Dd), _ptr(self.Hd), self.k,
                                                            self.log_shift, _ptr(out[b:b + gb]), _ptr(c2 if b == 0 else None),
                                                            _ptr(un if b == 0 else None), _ptr(self.scratch), self.need, _stream()))
             unmodelled = int(un.cpu().numpy()[0])
@@ -156,8 +136,8 @@ def products(X, vectors, D, H, side="pixels", log_shift=1e-14, layout="cm", chi2
     * ``unmodelled``: the entries with counts whose model is below ``log_shift``; they and every other entry below it have e = 0).
 
     X: the image as measured, (channels, pixels) for ``layout="cm"`` or (pixels, channels) for "pm", a host array or a device
-    tensor, checked and uploaded once by the marginals' rules.  D (n, k), H (k, p): 1 .. 8 components (NotImplementedError
-    beyond).  ``vectors``: a host array or a device float64 tensor, any number of them (8 per launch).  ``device=True`` leaves
+    tensor, checked and uploaded once by the narrowing rule (``_image_args.narrowed_image``).  D (n, k), H (k, p): 1 .. 8 components
+    (NotImplementedError beyond).  ``vectors``: a host array or a device float64 tensor, any number of them (8 per launch).  ``device=True`` leaves
     ``out`` and ``chi2`` on the GPU.  ValueError for shapes that do not match and for X, vectors or a model that are not finite -
     all before anything is uploaded.  Sums in fp64 in a fixed order without atomics: two calls and both layouts give the same bits."""
     pixel_side = _side(side)
@@ -173,21 +153,17 @@ def start_block(n, seed, block=BLOCK):
 
 def _orthonormal_rows(V):
     """The rows of V (b, p) orthonormalised, where V lives."""
-    if _is_tensor(V):
+    if is_tensor(V):
         from espm_amd.init_device import _qr_tall
         return _qr_tall(V.T.contiguous()).T.contiguous()
     return np.ascontiguousarray(np.linalg.qr(V.T)[0].T)
 
 
 def _rotate(M, V):
-    if _is_tensor(V):
+    if is_tensor(V):
         import torch
         return torch.from_numpy(np.ascontiguousarray(M)).to(V.device) @ V
     return M @ V
-
-
-def _to_host(V):
-    return V.cpu().numpy() if _is_tensor(V) else np.asarray(V)
 
 
 def _check_iteration(n_vectors, tol, max_iter, n, p):
@@ -217,7 +193,7 @@ def _subspace_iteration(products, n, p, n_vectors=4, tol=1e-10, max_iter=60, see
     ritz, n_iter, converged = None, 0, False
     while n_iter < max_iter and not converged:
         V = _orthonormal_rows(products("pixels", np.ascontiguousarray(U.T))["out"])
-        Z = _to_host(products("channels", V)["out"])
+        Z = _image.to_host(products("channels", V)["out"])
         U, R = np.linalg.qr(Z.T)
         s = np.linalg.svd(R, compute_uv=False)
         n_iter += 1
@@ -229,11 +205,11 @@ def _subspace_iteration(products, n, p, n_vectors=4, tol=1e-10, max_iter=60, see
     spectra = (U @ A)[:, :r]
     maps = _rotate(Bt[:r], V)
     last = products("pixels", np.ascontiguousarray(spectra.T), chi2=True)
-    maps, back = _to_host(maps), _to_host(last["out"])
+    maps, back = _image.to_host(maps), _image.to_host(last["out"])
     sv = s[:r]
     rho = np.linalg.norm(back - sv[:, None] * maps, axis=1)
     sign = np.where(spectra[np.abs(spectra).argmax(axis=0), np.arange(r)] < 0, -1.0, 1.0)
-    chi2_map = _to_host(last["chi2"])
+    chi2_map = _image.to_host(last["chi2"])
     total = float(chi2_map.sum())
     with np.errstate(divide="ignore", invalid="ignore"):
         explained = sv * sv / total
@@ -272,11 +248,8 @@ def independence_model(X, layout="cm"):
     all-ones weights without a model: exact for integer X.  ValueError for an image without a count."""
     from espm_amd import marginals
     check_layout(layout)
-    if getattr(X, "ndim", None) != 2:
-        X = np.asarray(X)
-    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
-        raise ValueError("X must be a non-empty 2-D array or tensor")
-    n, p = (int(X.shape[0]), int(X.shape[1])) if layout == "cm" else (int(X.shape[1]), int(X.shape[0]))
+    X = check_image(X)
+    n, p = image_dims(X.shape, layout)
     c = marginals.pixel_maps(X, np.ones((1, n)), layout=layout)["counts"][0]
     r = marginals.channel_spectra(X, np.ones((1, p)), layout=layout)["counts"][:, 0]
     T = float(c.sum())
@@ -290,17 +263,11 @@ def scree(X, n_vectors=6, tol=1e-10, max_iter=60, seed=0, log_shift=1e-14, layou
     map holds before anything is fitted - k phases show as k - 1 values above the bulk near ``edge``.  Returns ``svd``'s dict with
     ``normalised_pca`` (r,) = singular_values / sqrt(T), the values hyperspy's Poisson-normalised PCA reports beyond its trivial first
     one (which is 1), and ``total_counts`` = T.  X is uploaded once; arguments and refusals as for ``svd``."""
-    from espm_amd import marginals
     check_layout(layout)
-    if getattr(X, "ndim", None) != 2:
-        X = np.asarray(X)
-    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
-        raise ValueError("X must be a non-empty 2-D array or tensor")
-    n, p = (int(X.shape[0]), int(X.shape[1])) if layout == "cm" else (int(X.shape[1]), int(X.shape[0]))
-    _check_iteration(n_vectors, tol, max_iter, n, p)
-    if not log_shift > 0:
-        raise ValueError("log_shift must be positive")
-    Xd = _on_device(marginals._image(X, "scree"))[0]
+    X = check_image(X)
+    _check_iteration(n_vectors, tol, max_iter, *image_dims(X.shape, layout))
+    check_log_shift(log_shift)
+    Xd = _image.Resident(narrowed_image(X, "scree"), layout).upload().Xd
     D, H = independence_model(Xd, layout=layout)
     out = _svd_of(_Pass(Xd, D, H, log_shift, layout, "scree"), n_vectors, tol, max_iter, seed)
     T = float(H.sum())
@@ -317,11 +284,9 @@ def null_singular_values(D, H, n_rep=10, seed=0, replicate0=0, log_shift=1e-14, 
     checks them, 1 .. 8 components; ValueError if a replicate has saturated entries or entries without a valid rate, as ``simulate``
     raises."""
     from espm_amd import sampling
-    from espm_amd.splitting import _check_seed
-    seed, n_rep = _check_seed(seed), sampling._check_n_rep(n_rep)
+    seed, n_rep = check_seed(seed), sampling._check_n_rep(n_rep)
     replicate0 = sampling._check_replicate(replicate0, n_rep)
-    if not log_shift > 0:
-        raise ValueError("log_shift must be positive")
+    check_log_shift(log_shift)
     n, p, _, D, H = check_model(D, H, "null_singular_values", MAX_K)
     _check_iteration(1, tol, max_iter, n, p)
     D, H = sampling._model(D, H)

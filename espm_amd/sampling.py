@@ -16,7 +16,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from espm_amd._image_args import check_layout, check_model, layout_code
+from espm_amd import _image
+from espm_amd._image_args import check_layout, check_log_shift, check_model, check_seed, layout_code
 
 # T_i = floor(2^32 sum_{j <= i} e^-1 / j!): a 32-bit word w is the Poisson(1) draw #{i : w >= UNIT_CDF[i]}
 UNIT_CDF = (0x5e2d58d8, 0xbc5ab1b1, 0xeb715e1d, 0xfb239797, 0xff1025f5, 0xffd90f3b, 0xfffa8b71, 0xffff540c, 0xffffed1f, 0xfffffe21,
@@ -51,12 +52,9 @@ def _model(D, H):
 
 def _upload(D, H):
     """(Dd, Hd, device): the model on the GPU."""
-    import torch
-
     from espm_amd.engine import require_gpu
     dev = require_gpu(None)
-    with torch.cuda.device(dev):
-        return torch.tensor(D, device=dev), torch.tensor(H, device=dev), dev   # (a copy: D and H may be read-only arrays)
+    return (*_image.model_on_device(dev, D, H), dev)   # (D and H may be read-only arrays: those are copied)
 
 
 def _draw(Dd, Hd, dev, seed, replicate, dtype, layout):
@@ -78,8 +76,7 @@ def _draw(Dd, Hd, dev, seed, replicate, dtype, layout):
 
 
 def _check_sample_args(seed, replicate, dtype, layout):
-    from espm_amd.splitting import _check_seed
-    seed, replicate = _check_seed(seed), _check_replicate(replicate)
+    seed, replicate = check_seed(seed), _check_replicate(replicate)
     dtype = np.dtype(dtype)
     if dtype not in (np.dtype(np.uint8), np.dtype(np.uint16)):
         raise ValueError(f"dtype must be uint8 or uint16 (counts), not {dtype}")
@@ -109,11 +106,9 @@ def null_deviance(D, H, n_rep=100, seed=0, replicate0=0, log_shift=1e-14):
     ``replicate0 .. replicate0 + n_rep - 1`` of the model against the model itself - the distribution a pixel's deviance has when the
     model is right.  Row r is the deviance of ``sample(D, H, seed, replicate0 + r)``; the replicates are never stored.  Checks as for
     ``sample``.  One HIP kernel, sums in channel order in the pixel's own thread: two calls give the same bits."""
-    from espm_amd.splitting import _check_seed
-    seed, n_rep = _check_seed(seed), _check_n_rep(n_rep)
+    seed, n_rep = check_seed(seed), _check_n_rep(n_rep)
     replicate0 = _check_replicate(replicate0, n_rep)
-    if not log_shift > 0:
-        raise ValueError("log_shift must be positive")
+    check_log_shift(log_shift)
     D, H = _model(D, H)
     Dd, Hd, dev = _upload(D, H)
     import torch

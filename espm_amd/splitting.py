@@ -19,9 +19,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from espm_amd._image_args import check_layout, check_model, image_dims, layout_code
-
-MAX_COUNT = 65535
+from espm_amd import _image
+from espm_amd._image_args import check_log_shift, check_model, check_seed, counts_image
 
 
 def threshold(q):
@@ -37,73 +36,32 @@ def threshold(q):
     return thr, thr / 2.0 ** 32
 
 
-def _check_seed(seed):
-    if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
-        raise ValueError(f"seed must be an integer in 0 .. 2^64 - 1, not {seed!r}")
-    return int(seed)
-
-
-def _counts(X, layout):
-    """X as the kernels read it - a host array or a device tensor of uint8 / uint16 - and (n, p): TypeError for an X that is no image of
-    counts, ValueError for values outside 0 .. 65535.  Nothing is uploaded here."""
-    import torch
-    check_layout(layout)
-    is_t = isinstance(X, torch.Tensor)
-    if not is_t:
-        X = np.asarray(X)
-    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
-        raise ValueError("X must be a non-empty 2-D array or tensor")
-    integer = (not (X.dtype.is_floating_point or X.dtype.is_complex)) if is_t else X.dtype.kind in "iub"
-    if not integer:
-        raise TypeError(f"thinning is defined for counts: X has dtype {X.dtype} (an integer dtype with values 0 .. {MAX_COUNT})")
-    n, p = image_dims(X.shape, layout)
-    if X.dtype in ((torch.uint8, torch.uint16) if is_t else (np.uint8, np.uint16)):
-        return X, n, p
-    if is_t:
-        wide = X.to(torch.int64) if X.dtype != torch.bool else X.to(torch.uint8)
-        lo, hi = int(wide.min().item()), int(wide.max().item())
-    else:
-        lo, hi = int(X.min()), int(X.max())
-    if lo < 0 or hi > MAX_COUNT:
-        raise ValueError(f"X holds values from {lo} to {hi}: counts are 0 .. {MAX_COUNT}")
-    if is_t:
-        return X.to(torch.uint8 if hi <= 255 else torch.uint16), n, p
-    return X.astype(np.uint8 if hi <= 255 else np.uint16), n, p
-
-
-def _on_device(X):
-    """(Xd, dtype code, device): the 8- or 16-bit X on the GPU."""
-    from espm_amd import binning
-    return binning._on_device(X)
+def _checked(X, q, seed, layout):
+    """(image, thr, q_eff, seed) after every check of (X, q, seed, layout): the image by the counts-only rule, not yet uploaded."""
+    thr, q_eff = threshold(q)
+    seed = check_seed(seed)
+    return _image.Resident(counts_image(X, layout)[0], layout), thr, q_eff, seed
 
 
 def _resident(X, q, seed, layout):
     """X on the device as the kernels read it, after every check of (X, q, seed, layout): for callers that split and score the same
     image (one upload for both; a device tensor of 8- or 16-bit counts is returned as it is)."""
-    threshold(q)
-    _check_seed(seed)
-    return _on_device(_counts(X, layout)[0])[0]
+    return _checked(X, q, seed, layout)[0].upload().Xd
 
 
 def _thin(X, q, seed, layout, want_b):
-    thr, q_eff = threshold(q)
-    seed = _check_seed(seed)
-    X, n, p = _counts(X, layout)
+    img, thr, q_eff, seed = _checked(X, q, seed, layout)
     import torch
 
     from espm_amd import _lib
     from espm_amd.engine import _ptr, _stream
-    Xd, code, dev = _on_device(X)
-    with torch.cuda.device(dev):
+    Xd, dev = img.upload().Xd, img.dev
+    with img.scope():
         Xa = torch.empty(Xd.shape, dtype=Xd.dtype, device=dev)
         Xb = torch.empty(Xd.shape, dtype=Xd.dtype, device=dev) if want_b else None
-        _lib.check(_lib.lib.espm_thin_counts(_ptr(Xd), code, layout_code(layout), int(Xd.stride(0)), n, p, p, 0,
-                                             thr, seed, _ptr(Xa), _ptr(Xb) if want_b else None, int(Xa.stride(0)), _stream()))
+        _lib.check(_lib.lib.espm_thin_counts(*img.abi(), img.p, 0, thr, seed, _ptr(Xa), _ptr(Xb) if want_b else None, int(Xa.stride(0)),
+                                             _stream()))
     return Xa, Xb, q_eff
-
-
-def _to_host(T):
-    return T.cpu().numpy()
 
 
 def thin(X, q=0.5, seed=0, layout="cm", device=False):
@@ -117,7 +75,7 @@ def thin(X, q=0.5, seed=0, layout="cm", device=False):
     values above 65535 ValueError, a q outside (0, 1) or a seed outside 0 .. 2^64 - 1 ValueError - all before anything is uploaded.
     One HIP kernel, no atomics: the result is a function of (X, q, seed) alone, bit for bit, in both layouts."""
     Xa, Xb, _ = _thin(X, q, seed, layout, True)
-    return (Xa, Xb) if device else (_to_host(Xa), _to_host(Xb))
+    return (Xa, Xb) if device else (_image.to_host(Xa), _image.to_host(Xb))
 
 
 def split_deviance(X, D, H, q=0.5, seed=0, log_shift=1e-14, layout="cm"):
@@ -133,24 +91,21 @@ def split_deviance(X, D, H, q=0.5, seed=0, log_shift=1e-14, layout="cm"):
 
     X as for ``thin``; 1 .. 32 components; everything in fp64, sums in channel order: two calls, and both layouts, give the same
     bits."""
-    thr, q_eff = threshold(q)
-    seed = _check_seed(seed)
-    X, n, p = _counts(X, layout)
+    img, thr, q_eff, seed = _checked(X, q, seed, layout)
     from espm_amd import _lib
-    n, p, k, D, H = check_model(D, H, "split_deviance", _lib.SPLIT_MAX_K, tuple(X.shape), layout)
-    if not log_shift > 0:
-        raise ValueError("log_shift must be positive")
+    n, p, k, D, H = check_model(D, H, "split_deviance", _lib.SPLIT_MAX_K, tuple(img.host.shape), layout)
+    check_log_shift(log_shift)
     import torch
 
     from espm_amd.engine import _ptr, _stream
-    Xd, code, dev = _on_device(X)
-    with torch.cuda.device(dev):
-        Dd, Hd = torch.from_numpy(D).to(dev), torch.from_numpy(H).to(dev)
+    dev = img.upload().dev
+    with img.scope():
+        Dd, Hd = img.model(D, H)
         da = torch.empty(p, dtype=torch.float64, device=dev)
         db = torch.empty(p, dtype=torch.float64, device=dev)
         cb = torch.empty(p, dtype=torch.int64, device=dev)
-        _lib.check(_lib.lib.espm_split_deviance(_ptr(Xd), code, layout_code(layout), int(Xd.stride(0)), n, p, p, 0,
-                                                thr, seed, _ptr(Dd), _ptr(Hd), k, float(log_shift), _ptr(da), _ptr(db), _ptr(cb), _stream()))
+        _lib.check(_lib.lib.espm_split_deviance(*img.abi(), p, 0, thr, seed, _ptr(Dd), _ptr(Hd), k, float(log_shift), _ptr(da), _ptr(db),
+                                                _ptr(cb), _stream()))
         train_map, heldout_map, counts = da.cpu().numpy(), db.cpu().numpy(), cb.cpu().numpy()
     return dict(train_map=train_map, heldout_map=heldout_map, train=_ordered_sum(train_map), heldout=_ordered_sum(heldout_map),
                 heldout_counts=counts, q_eff=q_eff)
@@ -167,7 +122,7 @@ def scan(X, estimators, q=0.8, seeds=(0,)):
     ``fit_transform`` on X_a and is scored with ``split_deviance`` - the stages of ``NMFEstimator.fit_split``, whose attributes every
     estimator carries afterwards, from the last seed.  Returns dict(``heldout`` and ``train`` (len(estimators), len(seeds)), ``best``:
     the index of the estimator with the least mean held-out deviance, ``q_eff``)."""
-    estimators, seeds = list(estimators), [_check_seed(s) for s in seeds]
+    estimators, seeds = list(estimators), [check_seed(s) for s in seeds]
     if not estimators or not seeds:
         raise ValueError("scan needs at least one estimator and one seed")
     thr, q_eff = threshold(q)
@@ -182,7 +137,7 @@ def scan(X, estimators, q=0.8, seeds=(0,)):
             if layout not in resident:
                 resident[layout] = _resident(X, q, seed, layout)
             if layout not in parts:
-                parts[layout] = _to_host(_thin(resident[layout], q, seed, layout, False)[0])
+                parts[layout] = _image.to_host(_thin(resident[layout], q, seed, layout, False)[0])
             est._fit_split_stages(resident[layout], parts[layout], q, seed, layout)
             held[i, s], train[i, s] = est.heldout_deviance_, est.train_deviance_
     return dict(heldout=held, train=train, best=int(np.argmin(held.mean(axis=1))), q_eff=q_eff)

@@ -267,7 +267,8 @@ def test_module_raises_before_upload(lib, monkeypatch):
     import torch
 
     from espm_amd import attribution
-    monkeypatch.setattr(attribution, "_on_device", lambda *a, **k: pytest.fail("the upload was reached"))
+    from espm_amd import _image
+    monkeypatch.setattr(_image, "on_device", lambda *a, **k: pytest.fail("the upload was reached"))
     X = np.zeros((6, 20), np.uint8)
     D, H = np.ones((6, 2)), np.ones((2, 20))
     with pytest.raises(TypeError, match="defined for counts"):
@@ -335,7 +336,8 @@ def test_estimator_refuses_before_any_upload(lib, monkeypatch):
 
     from espm_amd import attribution
     from espm_amd.estimators import SmoothNMF
-    monkeypatch.setattr(attribution, "_on_device", lambda *a, **k: pytest.fail("the upload was reached"))
+    from espm_amd import _image
+    monkeypatch.setattr(_image, "on_device", lambda *a, **k: pytest.fail("the upload was reached"))
     X = np.ones((6, 20), np.uint8)
     with pytest.raises(NotFittedError):
         SmoothNMF(n_components=3, verbose=0).attribute_counts(X)

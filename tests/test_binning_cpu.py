@@ -147,7 +147,8 @@ def test_the_wide_builds_export_stubs(lib):
 # ---- the Python module, before the device ------------------------------------------------------------------------------------------------
 def test_module_checks_come_before_the_device(lib, monkeypatch):
     from espm_amd import binning
-    monkeypatch.setattr(binning, "_on_device", lambda *a, **k: pytest.fail("the upload was reached"))
+    from espm_amd import _image
+    monkeypatch.setattr(_image, "on_device", lambda *a, **k: pytest.fail("the upload was reached"))
     X = np.zeros((6, 20), np.uint8)
     with pytest.raises(ValueError, match="layout"):
         binning.rebin(X, (4, 5), (2, 2), layout="rows")
@@ -193,7 +194,8 @@ def _est(**kw):
 
 def test_fit_binned_refuses_before_any_upload(lib, monkeypatch):
     from espm_amd import binning
-    monkeypatch.setattr(binning, "_on_device", lambda *a, **k: pytest.fail("the upload was reached"))
+    from espm_amd import _image
+    monkeypatch.setattr(_image, "on_device", lambda *a, **k: pytest.fail("the upload was reached"))
     X = np.ones((10, 96), np.float32)
     with pytest.raises(ValueError, match=r"does not divide.*crop it to \(6, 10\)"):
         _est().fit_binned(X, (3, 5))

@@ -198,7 +198,8 @@ def test_estimator_refusals(measures, monkeypatch):
         SmoothNMF(n_components=K).pixel_diagnostics(X)
     est = SmoothNMF(n_components=9, max_iter=3, tol=0.0, verbose=0, random_state=0)
     quiet(est.fit, X)
-    monkeypatch.setattr(measures, "_diag_upload", lambda *a, **k: pytest.fail("the upload was reached"))
+    from espm_amd import _image
+    monkeypatch.setattr(_image, "on_device", lambda *a, **k: pytest.fail("the upload was reached"))
     with pytest.raises(NotImplementedError, match="9 components"):
         est.pixel_diagnostics(X)
     with pytest.raises(NotImplementedError, match="9 components"):

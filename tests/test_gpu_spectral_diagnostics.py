@@ -197,7 +197,8 @@ def test_estimator_refusals(measures, monkeypatch):
     fixed[5, 1] = 0.7
     held = SmoothNMF(n_components=K, max_iter=3, tol=0.0, verbose=0, random_state=0, fixed_W=fixed, simplex_W=False, simplex_H=True)
     quiet(held.fit, X)
-    monkeypatch.setattr(measures, "_diag_upload", lambda *a, **k: pytest.fail("the upload was reached"))
+    from espm_amd import _image
+    monkeypatch.setattr(_image, "on_device", lambda *a, **k: pytest.fail("the upload was reached"))
     for est, what in ((nine, "9 components"), (held, "fixed_W")):
         with pytest.raises(NotImplementedError, match=what):
             est.spectral_diagnostics(X)

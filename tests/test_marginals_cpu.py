@@ -216,7 +216,8 @@ def test_the_wide_builds_export_stubs(lib):
 
 # ---- the Python module, the estimator and the adapter, before the device ---------------------------------------------------------------------
 def test_module_raises_before_upload(lib, marginals, monkeypatch):
-    monkeypatch.setattr(marginals, "_on_device", lambda *a, **k: pytest.fail("the upload was reached"))
+    from espm_amd import _image
+    monkeypatch.setattr(_image, "on_device", lambda *a, **k: pytest.fail("the upload was reached"))
     X = np.zeros((6, 20), np.uint8)
     D, H = np.ones((6, 2)), np.ones((2, 20))
     Wn, Wp = np.ones((2, 6)), np.ones((2, 20))
@@ -286,7 +287,8 @@ def test_estimator_refuses_before_any_upload(lib, marginals, monkeypatch):
     from sklearn.exceptions import NotFittedError
 
     from espm_amd.estimators import SmoothNMF
-    monkeypatch.setattr(marginals, "_on_device", lambda *a, **k: pytest.fail("the upload was reached"))
+    from espm_amd import _image
+    monkeypatch.setattr(_image, "on_device", lambda *a, **k: pytest.fail("the upload was reached"))
     X = np.ones((6, 20), np.uint8)
     lines = [((2, 4), ((0, 2), (4, 6)))]
     labels = np.arange(20) % 3

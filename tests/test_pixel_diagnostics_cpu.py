@@ -45,7 +45,8 @@ def test_host_side_argument_errors_need_no_device(lib):
 
 def test_shape_checks_come_before_the_device(lib, monkeypatch):
     from espm_amd import measures
-    monkeypatch.setattr(measures, "_diag_upload", lambda *a, **k: pytest.fail("the upload was reached"))
+    from espm_amd import _image
+    monkeypatch.setattr(_image, "on_device", lambda *a, **k: pytest.fail("the upload was reached"))
     X, D, H = np.zeros((6, 10), np.float32), np.ones((6, 2)), np.ones((2, 10))
     with pytest.raises(ValueError, match="layout"):
         measures.pixel_diagnostics(X, D, H, layout="rows")
@@ -66,14 +67,14 @@ def test_shape_checks_come_before_the_device(lib, monkeypatch):
 
 
 def test_host_dtypes_go_up_exactly(lib):
-    from espm_amd import measures
+    from espm_amd._image_args import measured_dtype
     same = (np.uint8, np.uint16, np.float32, np.float64)
-    assert all(measures._diag_host_dtype(d) == np.dtype(d) for d in same)
-    assert measures._diag_host_dtype(np.bool_) == np.uint8
-    assert all(measures._diag_host_dtype(d) == np.float32 for d in (np.int8, np.int16, np.float16))
-    assert all(measures._diag_host_dtype(d) == np.float64 for d in (np.int32, np.uint32, np.int64, np.uint64))
+    assert all(measured_dtype(d) == np.dtype(d) for d in same)
+    assert measured_dtype(np.bool_) == np.uint8
+    assert all(measured_dtype(d) == np.float32 for d in (np.int8, np.int16, np.float16))
+    assert all(measured_dtype(d) == np.float64 for d in (np.int32, np.uint32, np.int64, np.uint64))
     with pytest.raises(TypeError):
-        measures._diag_host_dtype(np.complex64)
+        measured_dtype(np.complex64)
 
 
 def test_no_cpu_fallback(lib, monkeypatch):

@@ -149,7 +149,8 @@ def test_host_side_argument_errors_need_no_device(lib):
 
 def test_a_method_that_does_not_exist_is_refused_before_the_upload(lib, monkeypatch):
     from espm_amd import presence
-    monkeypatch.setattr(presence, "_on_device", lambda *a, **k: pytest.fail("the upload was reached"))
+    from espm_amd import _image
+    monkeypatch.setattr(_image, "on_device", lambda *a, **k: pytest.fail("the upload was reached"))
     X, D = np.zeros((6, 10), np.float32), np.ones((6, 2))
     for f in (presence.ml_unmix, presence.presence):
         with pytest.raises(ValueError, match="method"):

@@ -220,10 +220,9 @@ def test_the_wide_builds_export_stubs(lib):
 
 # ---- the Python module, the estimator and the adapter, before the device ---------------------------------------------------------------------
 def test_module_raises_before_upload(lib, residuals, monkeypatch):
-    from espm_amd import marginals, sampling
-    monkeypatch.setattr(residuals, "_on_device", lambda *a, **k: pytest.fail("the upload was reached"))
-    monkeypatch.setattr(marginals, "_on_device", lambda *a, **k: pytest.fail("the upload was reached"))
-    monkeypatch.setattr(sampling, "_upload", lambda *a, **k: pytest.fail("the upload was reached"))
+    from espm_amd import _image
+    monkeypatch.setattr(_image, "on_device", lambda *a, **k: pytest.fail("the upload was reached"))
+    monkeypatch.setattr(_image, "model_on_device", lambda *a, **k: pytest.fail("the upload was reached"))
     X = np.zeros((6, 20), np.uint8)
     D, H = np.ones((6, 2)), np.ones((2, 20))
     Vn, Vp = np.ones((2, 6)), np.ones((2, 20))
@@ -315,11 +314,10 @@ def _fitted(**kw):
 def test_estimator_refuses_before_any_upload(lib, residuals, monkeypatch):
     from sklearn.exceptions import NotFittedError
 
-    from espm_amd import marginals, sampling
     from espm_amd.estimators import SmoothNMF
-    monkeypatch.setattr(residuals, "_on_device", lambda *a, **k: pytest.fail("the upload was reached"))
-    monkeypatch.setattr(marginals, "_on_device", lambda *a, **k: pytest.fail("the upload was reached"))
-    monkeypatch.setattr(sampling, "_upload", lambda *a, **k: pytest.fail("the upload was reached"))
+    from espm_amd import _image
+    monkeypatch.setattr(_image, "on_device", lambda *a, **k: pytest.fail("the upload was reached"))
+    monkeypatch.setattr(_image, "model_on_device", lambda *a, **k: pytest.fail("the upload was reached"))
     X = np.ones((6, 20), np.uint8)
     with pytest.raises(NotFittedError):
         SmoothNMF(n_components=3, verbose=0).residual_components(X=X)

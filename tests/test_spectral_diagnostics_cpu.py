@@ -71,7 +71,8 @@ def test_host_side_argument_errors_need_no_device(lib):
 
 def test_shape_checks_come_before_the_device(lib, monkeypatch):
     from espm_amd import measures
-    monkeypatch.setattr(measures, "_diag_upload", lambda *a, **k: pytest.fail("the upload was reached"))
+    from espm_amd import _image
+    monkeypatch.setattr(_image, "on_device", lambda *a, **k: pytest.fail("the upload was reached"))
     X, D, H = np.zeros((6, 10), np.float32), np.ones((6, 2)), np.ones((2, 10))
     f = measures.spectral_diagnostics
     with pytest.raises(ValueError, match="layout"):

@@ -218,8 +218,9 @@ def test_module_threshold(lib):
 def test_thin_raises_before_upload(lib, monkeypatch):
     import torch
 
-    from espm_amd import splitting
-    monkeypatch.setattr(splitting, "_on_device", lambda *a, **k: pytest.fail("the upload was reached"))
+    from espm_amd import _image, splitting
+    from espm_amd._image_args import counts_image
+    monkeypatch.setattr(_image, "on_device", lambda *a, **k: pytest.fail("the upload was reached"))
     X = np.zeros((6, 20), np.uint8)
     with pytest.raises(TypeError, match="defined for counts"):
         splitting.thin(X.astype(np.float32))
@@ -258,14 +259,14 @@ def test_thin_raises_before_upload(lib, monkeypatch):
     with pytest.raises(ValueError, match="log_shift"):
         splitting.split_deviance(X, np.ones((6, 2)), np.ones((2, 20)), log_shift=0)
     # what goes up: u8 and u16 as they are, other integers narrowed after the range check
-    assert splitting._counts(X, "cm")[0] is X
+    assert counts_image(X, "cm")[0] is X
     ok = X.astype(np.int64)
     ok[1, 1] = 255
-    assert splitting._counts(ok, "cm")[0].dtype == np.uint8
+    assert counts_image(ok, "cm")[0].dtype == np.uint8
     ok[1, 1] = 256
-    got, n, p = splitting._counts(ok, "pm")
+    got, n, p = counts_image(ok, "pm")
     assert got.dtype == np.uint16 and got[1, 1] == 256 and (n, p) == (20, 6)
-    assert splitting._counts(torch.from_numpy(ok.astype(np.int32)), "cm")[0].dtype == torch.uint16
+    assert counts_image(torch.from_numpy(ok.astype(np.int32)), "cm")[0].dtype == torch.uint16
 
 
 def test_no_cpu_fallback(lib, monkeypatch):
@@ -289,7 +290,8 @@ def _est(**kw):
 
 def test_fit_split_refuses_before_any_upload(lib, monkeypatch):
     from espm_amd import splitting
-    monkeypatch.setattr(splitting, "_on_device", lambda *a, **k: pytest.fail("the upload was reached"))
+    from espm_amd import _image
+    monkeypatch.setattr(_image, "on_device", lambda *a, **k: pytest.fail("the upload was reached"))
     X = np.ones((6, 20), np.uint8)
     with pytest.raises(NotImplementedError, match="shard"):
         _est().shard(object()).fit_split(X)

@@ -1,5 +1,6 @@
 """Do the estimator's post-fit methods compute the same thing in two trees?  The record behind moving them from estimators/base.py to
-estimators/analysis.py (profiles/estimator_analysis_equal.log).
+estimators/analysis.py (profiles/estimator_analysis_equal.log) and behind giving the analysis modules one upload
+(profiles/image_host_equal.log).
 
     python tools/analysis/estimator_analysis_equal.py run OUT.npz [--root TREE]
     python tools/analysis/estimator_analysis_equal.py compare PARENT.npz PARENT_AGAIN.npz NEW.npz [--out profiles/estimator_analysis_equal.log]
@@ -8,16 +9,18 @@ estimators/analysis.py (profiles/estimator_analysis_equal.log).
 and once with an 8-column dictionary (8 configurations), on a 32-channel, 16 x 16 pixel Poisson image with 3 components:
 
   fit/     SmoothNMF(max_iter=20).fit_transform, then on that estimator pixel_diagnostics, spectral_diagnostics and attribute_counts (each
-           with the counts and with X=None), assign_counts, simulate, calibrate_deviance(n_rep=8) and bootstrap(n_boot=3);
+           with the counts and with X=None), assign_counts, simulate, calibrate_deviance(n_rep=8), line_maps (a raw and a
+           background-corrected window), region_spectra (three regions), residual_components(n_vectors=2), presence_maps with "em" and
+           with "newton", and bootstrap(n_boot=3);
   binned/  fit_binned with bin (2, 2) on a fresh estimator;   split/  fit_split with q = 0.8 on a fresh estimator;
-  hand/    the seven methods that do not refit the image, on an estimator whose G_, W_, H_, X_ and norm_factor_ are set by hand (fp32 W_ and
-           H_, and an fp32 G_ for the dictionary): functions of their inputs alone.
+  hand/    the same methods, which do not refit the image, on an estimator whose G_, W_, H_, X_ and norm_factor_ are set by hand (fp32
+           W_ and H_, and an fp32 G_ for the dictionary): functions of their inputs alone.
 
 After every call every public attribute ending in "_" and every returned value is written to OUT.npz under configuration/stage/name.
 
 ``compare`` takes two runs of the parent and one of the new tree.  A key the parent reproduces bit for bit must be bit-equal in the new
-tree; a key it does not must agree within the parent's own run-to-run difference, which is written down.  The keys under hand/ of the six
-methods that fit nothing must be bit-equal whatever the parent does.  Exit status 1 on any miss."""
+tree; a key it does not must agree within the parent's own run-to-run difference, which is written down.  The keys under hand/ of the
+methods that fit nothing (all but bootstrap) must be bit-equal whatever the parent does.  Exit status 1 on any miss."""
 import argparse
 import itertools
 import os
@@ -28,6 +31,8 @@ import numpy as np
 HERE = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 N, SHAPE, K, M = 32, (16, 16), 3, 8
 P = SHAPE[0] * SHAPE[1]
+LINES = [((5, 9), None), ((12, 16), ((8, 11), (18, 21)))]   # channel windows of line_maps: raw, and with two background windows
+REGIONS = np.arange(P) % 3                                   # the label map of region_spectra
 
 
 def problem(dictionary):
@@ -81,13 +86,18 @@ class Record:
 
 
 def analyses(rec, prefix, est, Xc):
-    """The seven methods that leave the image's fit alone; Xc: the counts, oriented as the estimator reads them."""
+    """The methods that leave the image's fit alone; Xc: the counts, oriented as the estimator reads them."""
     for name in ("pixel_diagnostics", "spectral_diagnostics", "attribute_counts"):
         rec.state(f"{prefix}/{name}(X)", est, getattr(est, name)(Xc))
         rec.state(f"{prefix}/{name}(None)", est, getattr(est, name)())
     rec.state(f"{prefix}/assign_counts", est, est.assign_counts(Xc, seed=3))
     rec.state(f"{prefix}/simulate", est, est.simulate(seed=4, replicate=1))
     rec.state(f"{prefix}/calibrate_deviance", est, est.calibrate_deviance(Xc, n_rep=8, seed=5))
+    rec.state(f"{prefix}/line_maps", est, est.line_maps(LINES, Xc))
+    rec.state(f"{prefix}/region_spectra", est, est.region_spectra(REGIONS, Xc))
+    rec.state(f"{prefix}/residual_components", est, est.residual_components(n_vectors=2, X=Xc))
+    for method in ("em", "newton"):
+        rec.state(f"{prefix}/presence_maps({method})", est, est.presence_maps(Xc, method=method))
     fitted = {n: np.array(getattr(est, n), copy=True) for n in ("G_", "W_", "H_", "X_")}
     rec.state(f"{prefix}/bootstrap", est, est.bootstrap(n_boot=3, seed=6, return_samples=True))
     assert all(np.array_equal(getattr(est, n), v) for n, v in fitted.items()), "bootstrap changed a fitted attribute"
