@@ -1,5 +1,5 @@
 // Launchers of the sparse count store kernels (mu_ell_kernel.hpp).
-#include "mu_ell_kernel.hpp"
+#include "mu_ell_plan.hpp"
 
 #ifndef ESPM_ELL_UNR_H
 #define ESPM_ELL_UNR_H 4
@@ -10,35 +10,13 @@
 
 namespace espm {
 
-// dynamic LDS above 64 KB has to be granted per kernel (once)
-template <typename KernelT>
-static int allow_lds(KernelT kern, size_t bytes, const char* what) {
-  if (bytes <= 64 * 1024) return ESPM_OK;
-  if (bytes > ESPM_ELL_LDS_MAX) return set_error(ESPM_EUNSUPPORTED, "%s: %zu bytes of LDS exceed %d", what, bytes, ESPM_ELL_LDS_MAX);
-  return check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes), what);
-}
-
 template <int K>
 static int launch_h_ell_k(const HStepArgs& args_in, int nblk, hipStream_t stream) {
   constexpr int UNR = K > 8 ? 2 : ESPM_ELL_UNR_H;   // (a batch holds 2 UNR gathered rows of K floats)
-  const size_t red = (size_t)(ESPM_ELL_TILE / 64 + 1) * (ESPM_HP_NSCALAR + 2 * K + 1) * sizeof(double);
-  // [nsplit][K][tile_px]: K * 512 floats whatever the split; two such sets when the groups of a 512-pixel window are walked in pairs
-  size_t part = (size_t)K * ESPM_ELL_TILE * sizeof(float) * ((K <= ESPM_ELL_PAIR_MAX_K && args_in.ell_tp == ESPM_ELL_TILE) ? 2 : 1);
-  if (red > part) part = red;
-  const size_t tail_scratch = (size_t)((ESPM_ELL_TILE / 64 + 1) * (KP + 1) + 1) * sizeof(double);
-  if (tail_scratch > part) part = tail_scratch;
+  const EllHPlan pl = plan_h_ell<K>(args_in.n_pad, args_in.ell_tp, args_in.cs_parts != nullptr, false);
   HStepArgs args = args_in;
-  size_t bytes = (size_t)args.n_pad * EllTab<K>::FLOATS * sizeof(float) + part;
-  if (args.cs_parts) {   // the workgroup's own copy of colsum(GW'): k doubles behind the numerators
-    if (bytes + KP * sizeof(double) <= ESPM_ELL_LDS_MAX) {
-      args.cs_lds_off = (int)bytes;
-      bytes += KP * sizeof(double);
-    } else {
-      // ... or, where table and numerators take the workgroup's LDS to the last byte (16 components at 2048 channels: 128 + 32 KB), in the
-      // table's first bytes once the walk is over and the table dead (the kernel: cs_late)
-      args.cs_lds_off = 0;
-    }
-  }
+  if (args.cs_parts) args.cs_lds_off = pl.cs_lds_off;   // the workgroup's own copy of colsum(GW')
+  const size_t bytes = pl.bytes;
   const dim3 grid(nblk + (args.tail_on ? 1 : 0));   // (+ the tail of the previous W update, espm_mu_iterate)
   if (args.h_rule == 1 || args.h_rule == 2) {  // quadratic surrogate of the Laplacian term / projected gradient
     auto go = [&](auto kern) -> int {
@@ -164,3 +142,15 @@ int launch_ell_fill_num(const float* gw_s, const float* h_in, const int32_t* fil
 }
 
 }  // namespace espm
+
+// the sparse H-step's LDS at the full tile (include/espm_mu.h): what the store choice asks
+extern "C" size_t espm_mu_ell_h_lds_bytes(int n_pad, int k) {
+  switch (k) {
+#if ESPM_KP <= 16
+#define ESPM_X(KK) case KK: return espm::plan_h_ell<KK>(n_pad, ESPM_ELL_TILE, false, false).bytes;
+    ESPM_K_CASES(ESPM_X)
+#undef ESPM_X
+#endif
+  }
+  return (size_t)-1;
+}

@@ -4,7 +4,7 @@
 // bf16 and fp32 stores below ESPM_H_CHAIN_MAX_K components (from there on the dense stores run the matrix-core H-step, which is not
 // chained; neither is the 17..32 build).  Only the instances WITH the loss terms: espm_mu_iterate_h fills history rows.
 // The build may compile this file ESPM_CHAIN_PARTS times, part ESPM_CHAIN_PART instantiating every ESPM_CHAIN_PARTS-th component count.
-#include "mu_ell_kernel.hpp"
+#include "mu_ell_plan.hpp"
 
 #ifndef ESPM_H_CHAIN_MAX_K
 #define ESPM_H_CHAIN_MAX_K 12   // = ESPM_H_MFMA_MIN_K - 1 (mu_h_step.hip)
@@ -23,31 +23,12 @@ namespace espm {
 
 #if ESPM_KP <= 16
 
-template <typename KernelT>
-static int allow_lds(KernelT kern, size_t bytes, const char* what) {
-  if (bytes <= 64 * 1024) return ESPM_OK;
-  if (bytes > ESPM_ELL_LDS_MAX) return set_error(ESPM_EUNSUPPORTED, "%s: %zu bytes of LDS exceed %d", what, bytes, ESPM_ELL_LDS_MAX);
-  return check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes), what);
-}
-
-// LDS of the sparse H-step (launch_h_ell_k, mu_ell.hip) without the chain's scratch
-template <int K>
-static size_t ell_lds_bytes(int n_pad, int tile_px) {
-  const size_t red = (size_t)(ESPM_ELL_TILE / 64 + 1) * (ESPM_HP_NSCALAR + 2 * K + 1) * sizeof(double);
-  size_t part = (size_t)K * ESPM_ELL_TILE * sizeof(float) * ((K <= ESPM_ELL_PAIR_MAX_K && tile_px == ESPM_ELL_TILE) ? 2 : 1);
-  if (red > part) part = red;
-  const size_t fin = (size_t)4 * H_FINALIZE_NV * sizeof(double);   // (the extra workgroup's scratch, at the start of the LDS)
-  if (fin > part) part = fin;
-  return (size_t)n_pad * EllTab<K>::FLOATS * sizeof(float) + part;
-}
-static size_t chain_scr_bytes(int k) { return (size_t)8 * k * sizeof(double); }
-
 template <int K>
 static int launch_chain_k(const HStepArgs& args_in, int x_dtype, int tile_px, int nblk, hipStream_t stream) {
   HStepArgs args = args_in;
   args.tail_on = args.chain_fin_on ? 1 : 0;   // (the extra workgroup is not a record: h_epilogue)
   const dim3 grid(nblk + args.tail_on);
-  auto go = [&](auto kern, int threads, size_t bytes, const char* what) -> int {
+  auto go = [&](auto kern, int threads, size_t bytes, const char* what) -> int {   // bytes: the kernel's own LDS; the chain's scratch goes behind
     args.chain_lds_off = (int)bytes;
     bytes += chain_scr_bytes(K);
     if (int rc = allow_lds(kern, bytes, what)) return rc;
@@ -56,7 +37,7 @@ static int launch_chain_k(const HStepArgs& args_in, int x_dtype, int tile_px, in
   };
   if (x_dtype == ESPM_X_ELL) {
     constexpr int UNR = K > 8 ? 2 : ESPM_ELL_UNR_H;
-    return go(h_step_ell_kernel<K, true, UNR, 0, true>, ESPM_ELL_TILE, ell_lds_bytes<K>(args.n_pad, args.ell_tp), "h_step (ell, chained)");
+    return go(h_step_ell_kernel<K, true, UNR, 0, true>, ESPM_ELL_TILE, plan_h_ell<K>(args.n_pad, args.ell_tp, false, true).chain_lds_off, "h_step (ell, chained)");
   }
   if constexpr (K <= ESPM_H_CHAIN_MAX_K) {
     auto dense = [&](auto k256, auto k128) -> int {
@@ -95,7 +76,7 @@ int ESPM_CAT(launch_h_chain_part, ESPM_CHAIN_PART)(const HStepArgs& args, int x_
 int launch_h_chain_part1(const HStepArgs& args, int x_dtype, int tile_px, int nblk, hipStream_t stream);
 
 template <int K>
-static bool ell_chain_fits(int n_pad, int tile_px) { return ell_lds_bytes<K>(n_pad, tile_px) + chain_scr_bytes(K) <= ESPM_ELL_LDS_MAX; }
+static bool ell_chain_fits(int n_pad, int tile_px) { return plan_h_ell<K>(n_pad, tile_px, false, true).fits; }
 #endif
 
 bool h_chain_built(const espm_mu_state* st) {

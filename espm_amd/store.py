@@ -60,8 +60,9 @@ def choose_store(n, p, k, x_store, facts, *, h_rule=0, bregman=False, pg_gamma_w
             heavy_why = "the heavy elements are not wired into the Bregman variant"
         elif float(pg_gamma_w) > 0:
             heavy_why = "the heavy elements are not wired into the projected-gradient W step"
-    lds = lds_bytes_h((n + 7) // 8 * 8, k)
-    fits = k <= _lib.WIDE_MAX_K and n <= ELL_MAX_N and lds <= _lib.ELL_LDS_MAX
+    # (k first: a build is not asked for a component count it has no sparse kernels for)
+    lds = lds_bytes_h((n + 7) // 8 * 8, k) if k <= _lib.WIDE_MAX_K else None
+    fits = lds is not None and n <= ELL_MAX_N and lds <= _lib.ELL_LDS_MAX
     nnz = facts.nnz
     sparse = float(nnz) <= ELL_MAX_DENSITY * (n * p)
     light = n_heavy <= ELL_MAX_HEAVY_FRACTION * nnz

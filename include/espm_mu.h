@@ -1129,6 +1129,14 @@ int espm_pixel_ml_newton(const void* x, int x_dtype, int x_layout, int64_t ld, i
                          uint32_t mask, double log_shift, double tol, int n_pass, double* h_inout, double* dev, double* gap, int32_t* passes,
                          uint8_t* done, uint64_t* counters, void* state, size_t state_bytes, espm_stream_t stream);
 
+/* ---- LDS of the sparse H-step (csrc/mu_ell_plan.hpp: plan_h_ell; espm_amd.ell.lds_bytes_h, the store choice of espm_amd.store) ----
+ * Dynamic LDS, in bytes, that the H-step of the sparse count store (x_dtype = ESPM_X_ELL) takes for n_pad channels and k components
+ * at the full tile (tile_px = ESPM_ELL_TILE) without the copy of colsum(GW') that a riding W tail adds: the G W table plus the
+ * region of the partial numerators.  The store fits where this is at most ESPM_ELL_LDS_MAX.  Answered from the plan the launch
+ * itself lays out its LDS by, so the two cannot disagree.  (size_t)-1 for a k this build has no sparse kernels for (each build its
+ * own 1..8 or 9..16; the 17..32 build has none).  No device is touched.  No espm_mu_state is involved: ESPM_MU_ABI_VERSION stays. */
+size_t espm_mu_ell_h_lds_bytes(int n_pad, int k);
+
 #ifdef __cplusplus
 }
 #endif
