@@ -1,0 +1,314 @@
+// Pixel ML with one abundance pinned (include/espm_mu.h, "pixel ML, pinned"): the per-pixel Poisson maximum-likelihood problem of
+// mu_pixel_ml_newton.hip with component `pin` held at a value t of the pixel's own while the components of the mask are fitted - one
+// point of the profile likelihood of h_pin, which espm_amd.presence.intervals walks to its chi2 level.  A unit of its own:
+// mu_pixel_ml.hip and mu_pixel_ml_newton.hip compile to what they compiled to without it.
+//
+//   geometry and walk of pmlk::pixel_ml_newton_kernel: one pixel per thread, ESPM_DIAG_BLOCK pixels per workgroup, D staged UNPADDED
+//   through LDS in chunks of ESPM_DIAG_CHUNK channels, the exact K a template argument, mu_image_pass.hpp's transposing tile for
+//   pixel-major X, ascending fma sums, 4 entries in flight up to K = 6 and 1 at K = 7, 8
+//   per entry and pass: the Newton rule's y (the pinned term included), w, dev, q and triangle
+//   per pass, between walks: NO scale onto the ray (with a pinned term the scale of least deviance has no closed form), so h is the
+//   same before and after a walk and nothing is parked in h_io; a certificate of its own (the header derives it); the slope
+//   2 (s_pin - q_pin) of the profile; then the Newton rule's accept / reject test, blend, root-free Cholesky and clamps over the
+//   mask, the pinned component a row of the identity like every other component outside it.
+//
+// `pin` is uniform over the launch and never indexes a register array: every use is a select inside an unrolled loop.
+// Resumable as the Newton kernel is; a pixel that enters with done != 0 is never read or written beyond its done byte, and a
+// workgroup with none entered returns at once - what a root finder retires pixels by.  No float atomics.  Only the narrow build
+// (ESPM_KP == 8) instantiates the kernels; the wide builds export the entry point as a stub.
+#include <cmath>
+#include <type_traits>
+
+#include "mu_common.hpp"
+
+namespace espm {
+
+#if ESPM_KP == 8
+#include "mu_image_pass.hpp"
+#include "mu_pixel_ml.hpp"
+
+namespace pmlk {
+
+__device__ __forceinline__ constexpr int ptri(int i, int j) { return i * (i + 1) / 2 + j; }   // (i, j), j <= i, of the lower triangle
+
+// K = 8, channel-major: left to itself the allocator takes 251 VGPRs and 16 AGPRs, one wave per SIMD where the Newton kernel (255
+// and none) runs two; asked for two it fits 243 without scratch (profiles/pixel_ml_pinned_resources.txt).
+template <int K, typename XT, bool PM>
+__global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu((K == 8 && !PM) ? 2 : 1))) void pixel_ml_pinned_kernel(const XT* __restrict__ x, int64_t ld, int n, int p, const double* __restrict__ d,
+                                                            Sums<K> s, uint32_t mask, int pin, const double* __restrict__ t_in,
+                                                            double log_shift, double tol, int n_pass, double* __restrict__ h_io,
+                                                            double* __restrict__ dev_o, double* __restrict__ gap_o,
+                                                            double* __restrict__ slope_o, int32_t* __restrict__ passes,
+                                                            uint8_t* __restrict__ done, double* __restrict__ state,
+                                                            unsigned long long* __restrict__ counters) {
+  constexpr int T = K * (K + 1) / 2;
+  __shared__ double ds[CH * K];
+  __shared__ XT tile[PM ? tile_rows<XT>() * TP : 1];
+  __shared__ uint32_t cnt_part[ESPM_PML_COUNTERS][B / 64];
+  const int q0 = blockIdx.x * B;
+  const int q = q0 + threadIdx.x;
+  const bool valid = q < p;
+  const bool entered = valid && done[q] == 0;   // the pixels this call may write
+  if (__syncthreads_count(entered) == 0) return;   // (workgroup-uniform: counters[NOT_DONE] gets nothing from here)
+  // the pixel's rows of state (k + ESPM_PMLN_STATE_EXTRA, p): e, then dev_acc, tau, trial
+  double* const st_e = state + q;
+  double* const st_acc = state + (size_t)K * p + q;
+  double* const st_tau = state + (size_t)(K + 1) * p + q;
+  double* const st_trial = state + (size_t)(K + 2) * p + q;
+  bool live = entered;
+  int st = 0, np = 0;
+  double h[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) h[j] = live ? h_io[(size_t)j * p + q] : 0.0;
+  // dev, gap and slope are those of the last accepted point and live in the caller's arrays: written HERE when a point is accepted
+  // (a rejected pass leaves them), never carried over a walk in registers; so is t, which h[pin] holds from the entry on
+  double tq = 0.0;
+  if (live) {
+    np = passes[q];
+    tq = t_in[q];
+    if (np == 0) dev_o[q] = 0.0, gap_o[q] = 0.0, slope_o[q] = 0.0;
+  }
+
+  double N = 0.0;
+  walk<K, XT, PM, false>(x, ld, n, p, q0, d, ds, tile, false, live, [&](double xv, const double*) { N = N + xv; });
+
+  uint32_t n_un = 0, n_nf = 0;
+  const int m = __popc(mask);
+  if (live) {
+    if (!(tq >= 0.0) || !isfinite(tq)) {   // no point of the profile: h, dev, gap and slope stay as the call found them (0 before any pass)
+      st = 2, live = false;
+      n_nf = 1;
+    } else {
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        if (j == pin) h[j] = tq;
+        else if (!((mask >> j) & 1u) || N == 0.0) h[j] = 0.0;
+        else if (np == 0 && !(h[j] > 0.0)) h[j] = N / ((double)m * s.v[j]) * 1e-3;
+      }
+      if (np == 0) {   // the start of the extra state
+#pragma unroll
+        for (int j = 0; j < K; ++j) st_e[(size_t)j * p] = 0.0;
+        *st_acc = INFINITY, *st_tau = 1e-2, *st_trial = 0.0;
+      }
+    }
+  }
+
+  const bool one_chunk = n <= CH;
+  for (int it = 0; it < n_pass; ++it) {
+    if (__syncthreads_count(live) == 0) break;
+    double qv[K], a[T];
+#pragma unroll
+    for (int j = 0; j < K; ++j) qv[j] = 0.0;
+#pragma unroll
+    for (int i = 0; i < T; ++i) a[i] = 0.0;
+    // the channels, at h as it stands (no scale onto the ray)
+    double dv = 0.0;
+    uint32_t un = 0;
+    walk<K, XT, PM, true, (K >= 7 ? 1 : 4)>(x, ld, n, p, q0, d, ds, tile, !one_chunk || it == 0, live, [&](double xv, const double* __restrict__ g) {
+      double gj[K];
+      double y = 0.0;
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        gj[j] = g[j];
+        y = fma(gj[j], h[j], y);
+      }
+      const bool floored = !(y >= log_shift);
+      y = floored ? log_shift : y;
+      const double inv = 1.0 / y;
+      const double w = xv * inv;
+      double t = y - xv;
+      if (xv > 0) t = fma(xv, log(w), t);
+      dv += t;
+      un += (uint32_t)(floored && xv > 0);
+      const double wy = w * inv;   // x / y^2
+#pragma unroll
+      for (int j = 0; j < K; ++j) qv[j] = fma(gj[j], w, qv[j]);
+#pragma unroll
+      for (int i = 0; i < K; ++i) {
+        const double gw = gj[i] * wy;
+#pragma unroll
+        for (int j = 0; j <= i; ++j) a[ptri(i, j)] = fma(gw, gj[j], a[ptri(i, j)]);
+      }
+    });
+    if (live) {
+      // the ratios, the certificate and the slope
+      double r[K];
+      double rmax = -INFINITY, lin = 0.0, sl = 0.0;
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        r[j] = 0.0;
+        if ((mask >> j) & 1u) {
+          r[j] = qv[j] / s.v[j];
+          rmax = fmax(rmax, r[j]);
+          lin = fma(s.v[j] - qv[j], h[j], lin);
+        }
+        if (j == pin) sl = 2.0 * (s.v[j] - qv[j]);
+      }
+      const double dev_t = 2.0 * dv;
+      const double gap_t = 2.0 * fma(N, fmax(rmax - 1.0, 0.0), lin);
+      // the stop that is not finite; the trial rejected; or the point accepted, and then the stop or the next trial
+      if (!isfinite(dev_t) || !isfinite(gap_t)) {   // (h is as the pass found it: nothing rescaled it)
+        dev_o[q] = dev_t, gap_o[q] = gap_t, slope_o[q] = sl;
+        st = 2, live = false;
+        n_nf = 1;
+      } else {
+        double tau = *st_tau;
+        const bool trial = *st_trial != 0.0;
+        if (trial && !(dev_t <= *st_acc)) {   // rejected: the EM successor of the accepted point, and a heavier blend
+#pragma unroll
+          for (int j = 0; j < K; ++j) h[j] = (j == pin) ? h[j] : st_e[(size_t)j * p];
+          *st_trial = 0.0;
+          *st_tau = fmin(10.0 * tau, 1.0);
+          np += 1;
+        } else {
+          dev_o[q] = dev_t, gap_o[q] = gap_t, slope_o[q] = sl;
+          if (gap_t <= tol) {
+            st = 1, live = false;
+            n_un = un;
+          } else {
+            if (trial) tau = fmax(tau / 10.0, 1e-8);
+            // B = A_MM + tau diag(s / h) in place, the identity outside the mask (the pinned row too); the right-hand side -g = q - s
+            double z[K];
+#pragma unroll
+            for (int i = 0; i < K; ++i) {
+              const bool mi = (mask >> i) & 1u;
+              r[i] = h[i] * r[i];   // e: the EM successor (monotone with the pinned term as a fixed background)
+              st_e[(size_t)i * p] = r[i];
+              z[i] = mi ? -(s.v[i] - qv[i]) : 0.0;
+#pragma unroll
+              for (int j = 0; j < i; ++j)
+                if (!(mi && ((mask >> j) & 1u))) a[ptri(i, j)] = 0.0;
+              a[ptri(i, i)] = mi ? fma(tau, s.v[i] / h[i], a[ptri(i, i)]) : 1.0;
+            }
+            // B = L diag(dd) L^T (root-free Cholesky, in place: a holds L below the diagonal)
+            bool bad = false;
+            double dd[K];
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+              double dj = a[ptri(j, j)];
+#pragma unroll
+              for (int l = 0; l < j; ++l) dj = fma(-(a[ptri(j, l)] * a[ptri(j, l)]), dd[l], dj);
+              bad |= !(dj > 0.0) || !isfinite(dj);
+              dd[j] = dj;
+#pragma unroll
+              for (int i = j + 1; i < K; ++i) {
+                double v = a[ptri(i, j)];
+#pragma unroll
+                for (int l = 0; l < j; ++l) v = fma(-(a[ptri(i, l)] * a[ptri(j, l)]), dd[l], v);
+                a[ptri(i, j)] = v / dj;
+              }
+            }
+            // L z = -g; z = z / dd; L^T delta = z
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+#pragma unroll
+              for (int l = 0; l < j; ++l) z[j] = fma(-a[ptri(j, l)], z[l], z[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < K; ++j) z[j] = z[j] / dd[j];
+#pragma unroll
+            for (int j = K - 1; j >= 0; --j) {
+#pragma unroll
+              for (int l = j + 1; l < K; ++l) z[j] = fma(-a[ptri(l, j)], z[l], z[j]);
+            }
+            // the trial: never below 0.01 h (fraction to the boundary), never 0; a pivot that is no pivot: the EM step
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+              const double cand = fmax(fmax(h[j] + z[j], 0.01 * h[j]), 1e-30 * N / s.v[j]);
+              h[j] = (j == pin) ? h[j] : (bad ? r[j] : (((mask >> j) & 1u) ? cand : 0.0));
+            }
+            *st_acc = dev_t;
+            *st_tau = tau;
+            *st_trial = bad ? 0.0 : 1.0;
+            np += 1;
+          }
+        }
+      }
+    }
+  }
+
+  if (entered) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) h_io[(size_t)j * p + q] = h[j];
+    passes[q] = np;
+    done[q] = (uint8_t)st;
+  }
+  const uint32_t v[ESPM_PML_COUNTERS] = {live ? 1u : 0u, n_un, n_nf};
+  block_count_add<ESPM_PML_COUNTERS, B / 64>(cnt_part, v, counters);
+}
+
+template <int K, typename XT>
+int launch_pinned(const void* x, int x_layout, int64_t ld, int n, int p, const double* d, const double* s, uint32_t mask, int pin,
+                  const double* t, double log_shift, double tol, int n_pass, double* h_io, double* dev, double* gap, double* slope,
+                  int32_t* passes, uint8_t* done, double* state, unsigned long long* counters, hipStream_t st) {
+  const dim3 grid((unsigned)(((int64_t)p + B - 1) / B)), block(B);
+  const XT* xt = static_cast<const XT*>(x);
+  Sums<K> sv;
+  for (int j = 0; j < K; ++j) sv.v[j] = s[j];
+  if (x_layout == ESPM_LAYOUT_PM)
+    hipLaunchKernelGGL((pixel_ml_pinned_kernel<K, XT, true>), grid, block, 0, st, xt, ld, n, p, d, sv, mask, pin, t, log_shift, tol, n_pass,
+                       h_io, dev, gap, slope, passes, done, state, counters);
+  else
+    hipLaunchKernelGGL((pixel_ml_pinned_kernel<K, XT, false>), grid, block, 0, st, xt, ld, n, p, d, sv, mask, pin, t, log_shift, tol, n_pass,
+                       h_io, dev, gap, slope, passes, done, state, counters);
+  return check_hip(hipGetLastError(), "pixel ML (pinned) launch");
+}
+
+// what espm_pixel_ml_pinned refuses before the device is touched: pmlk::check_args with a mask that may be empty, and the pinned
+// component's own conditions (k is checked by the caller: ESPM_EUNSUPPORTED)
+inline int check_pinned_args(const char* who, const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, const double* d, const double* s,
+                             int k, uint32_t mask, int pin, const double* t, double log_shift, double tol, int n_pass, const double* h_inout,
+                             const double* dev, const double* gap, const double* slope, const int32_t* passes, const uint8_t* done,
+                             const uint64_t* counters) {
+  ESPM_REQUIRE(x && d && s && h_inout && dev && gap && passes && done && counters,
+               "%s: bad arguments (x %p, d %p, s %p, h %p, dev %p, gap %p, passes %p, done %p, counters %p)", who, x, (const void*)d,
+               (const void*)s, (const void*)h_inout, (const void*)dev, (const void*)gap, (const void*)passes, (const void*)done, (const void*)counters);
+  ESPM_REQUIRE(t && slope, "%s: bad arguments (t %p, slope %p)", who, (const void*)t, (const void*)slope);
+  if (int rc = check_image(who, x, x_dtype, ESPM_DIAG_X_F64, x_layout, ld, n, p)) return rc;
+  ESPM_REQUIRE(log_shift > 0, "%s: log_shift=%g must be positive", who, log_shift);
+  ESPM_REQUIRE(tol > 0, "%s: tol=%g must be positive", who, tol);
+  ESPM_REQUIRE(n_pass >= 1, "%s: n_pass=%d (at least one pass)", who, n_pass);
+  ESPM_REQUIRE((mask >> k) == 0, "%s: mask 0x%x over %d components (bits beyond them)", who, mask, k);
+  ESPM_REQUIRE(pin >= 0 && pin < k, "%s: pin=%d (one of the %d components)", who, pin, k);
+  ESPM_REQUIRE(!((mask >> pin) & 1u), "%s: pin=%d is in the mask 0x%x (the pinned component is not fitted)", who, pin, mask);
+  ESPM_REQUIRE(s[pin] > 0 && std::isfinite(s[pin]), "%s: component %d is pinned and its spectrum sums to %g", who, pin, s[pin]);
+  for (int j = 0; j < k; ++j)
+    if ((mask >> j) & 1u)
+      ESPM_REQUIRE(s[j] > 0 && std::isfinite(s[j]), "%s: component %d is in the mask and its spectrum sums to %g", who, j, s[j]);
+  return ESPM_OK;
+}
+
+}  // namespace pmlk
+#endif
+
+}  // namespace espm
+
+using namespace espm;
+
+extern "C" int espm_pixel_ml_pinned(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, const double* d, const double* s, int k,
+                                    uint32_t mask, int pin, const double* t, double log_shift, double tol, int n_pass, double* h_inout,
+                                    double* dev, double* gap, double* slope, int32_t* passes, uint8_t* done, uint64_t* counters, void* state,
+                                    size_t state_bytes, espm_stream_t stream) {
+#if ESPM_KP != 8
+  return set_error(ESPM_EUNSUPPORTED, "pixel ML (pinned): built into the 1..%d component library only", ESPM_PML_MAX_K);
+#else
+  const char* who = "pixel ML (pinned)";
+  if (k < 1 || k > ESPM_PML_MAX_K) return set_error(ESPM_EUNSUPPORTED, "%s: k=%d (1..%d components)", who, k, ESPM_PML_MAX_K);
+  if (int rc = pmlk::check_pinned_args(who, x, x_dtype, x_layout, ld, n, p, d, s, k, mask, pin, t, log_shift, tol, n_pass, h_inout, dev, gap,
+                                       slope, passes, done, counters))
+    return rc;
+  ESPM_REQUIRE(state && state_bytes >= ESPM_PMLN_STATE_BYTES(k, p), "%s: state %p of %zu bytes (%zu needed for k=%d, p=%d)", who, state,
+               state_bytes, (size_t)ESPM_PMLN_STATE_BYTES(k, p), k, p);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counters);
+  if (int rc = check_hip(hipMemsetAsync(cnt + ESPM_PML_NOT_DONE, 0, sizeof(unsigned long long), st), "pixel ML (pinned): zeroing the counter"))
+    return rc;
+  return dispatch_k_exact(k, [&](auto kk) {
+    return dispatch_xt<ESPM_DIAG_X_F64>(x_dtype, [&](auto xt) {
+      return pmlk::launch_pinned<decltype(kk)::value, typename decltype(xt)::type>(x, x_layout, ld, n, p, d, s, mask, pin, t, log_shift, tol,
+                                                                                    n_pass, h_inout, dev, gap, slope, passes, done,
+                                                                                    static_cast<double*>(state), cnt, st);
+    });
+  });
+#endif
+}

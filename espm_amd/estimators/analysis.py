@@ -481,6 +481,54 @@ class _FitAnalysis:
             out = dict(out, H_ml=out["H_ml"].T)
         return out
 
+    # ---- how much of phase j could be in this pixel: profile-likelihood intervals of the abundances -----------------------------------
+    def abundance_intervals(self, level=0.95, X=None, components=None, tol=1e-3, lr_tol=1e-2, max_eval=None):
+        """How much of phase j could be in this pixel?  ``espm_amd.presence.intervals`` on the fitted spectra ``G_ @ W_``, started at
+        ``H_``: for every pixel and every requested component the PROFILE-LIKELIHOOD interval of the abundance - the values t whose
+        best fit with h_j held at t lies within the chi2_1 quantile 2 erfinv(level)^2 of the pixel's best fit.  Where an abundance
+        sits at or near zero (where the Wald bar ``H_std_`` means nothing) the interval starts at exactly 0 and ``H_upper_`` is an
+        upper limit, the detection limit of the map; away from the boundary the two ends are an asymmetric error bar.
+        ``presence_maps``' statistic is the same profile at the single point t = 0.  The interval is two-sided: a one-sided 95 %
+        upper limit is ``H_upper_`` at ``level=0.90``.  No reference analogue.
+
+        Sets ``H_lower_``, ``H_upper_`` (k, p), oriented as ``H_`` (NaN in rows not requested and for pixels that did not finish);
+        ``H_interval_level_``; ``H_interval_converged_`` (bool) and ``H_interval_n_eval_`` (k, 2, p): [:, 0] the lower end, [:, 1] the
+        upper; and ``H_ml_`` (k, p), ``deviance_ml_`` (p,), the full fit by the Newton rule.  Returns dict(H_ml, deviance_ml, lower,
+        upper, level, threshold, converged, n_eval, n_pass, unmodelled, nonfinite); with ``hspy_comp`` the returned ``H_ml``,
+        ``lower`` and ``upper`` are (p, k), as ``fit_transform`` returns ``H_.T``; the attributes stay (k, p).  The fitted
+        attributes are not touched.
+
+        What the interval is NOT: it holds the spectra ``G_ @ W_`` fixed (their own uncertainty is ``spectral_diagnostics``'); it
+        imposes neither the regularisers of the fit (``mu``, ``lambda_L``) nor ``simplex_H``, as ``presence_maps`` does not; and it is
+        ASYMPTOTIC - at a few tens of counts per pixel, and where other abundances sit on their boundaries, its coverage is a guide
+        (``sampling`` / ``simulate`` draw the replicates a calibration would need).
+
+        ``level``: strictly between 0 and 1.  ``components``: the rows to compute (None: all).  ``tol``: the certified gap of every
+        fit; ``lr_tol``: how close to the quantile an end's deviance difference must come; ``max_eval``: the cap of the pinned fits
+        per end (None: 64).  ``X`` as for ``pixel_diagnostics``; ``X=None`` takes the fit's ``X_`` un-scaled, with the cost and the
+        ``log_shift`` fill described there (refused after ``fit_binned``).  Computed in fp64 whatever the estimator's precision, on
+        the current device (a ``shard()``ed estimator: every rank computes all pixels on its own device); 1 .. 8 components
+        (NotImplementedError beyond), all before anything is uploaded."""
+        from espm_amd import presence
+        check_is_fitted(self, "W_")
+        presence.threshold(level)
+        k = int(self.H_.shape[0])
+        if k > presence.MAX_K:
+            raise NotImplementedError(f"abundance_intervals: {k} components (the kernels are built for 1..{presence.MAX_K})")
+        if components is not None:
+            presence._components(components, k)
+        X, layout = self._image_argument(X, "abundance_intervals")
+        G, W, H = self._model_factors()
+        D = W if G is None else G @ W
+        out = presence.intervals(X, D, H, level=level, components=components, tol=tol, lr_tol=lr_tol,
+                                 max_eval=64 if max_eval is None else max_eval, log_shift=self.log_shift, layout=layout)
+        self.H_lower_, self.H_upper_, self.H_interval_level_ = out["lower"], out["upper"], out["level"]
+        self.H_interval_converged_, self.H_interval_n_eval_ = out["converged"], out["n_eval"]
+        self.H_ml_, self.deviance_ml_ = out["H_ml"], out["deviance_ml"]
+        if self.hspy_comp:
+            out = dict(out, H_ml=out["H_ml"].T, lower=out["lower"].T, upper=out["upper"].T)
+        return out
+
     # ---- draws from the fitted model: a simulated image, a scale for the deviance map, the parametric bootstrap -------------------
     def _sampling_model(self, who):
         """(D, H): the fitted model ``G_ @ W_`` (n, k) and ``H_`` (k, p) in counts, in fp64, after the refusals of ``simulate``,

@@ -215,6 +215,16 @@ def presence_maps(est, shape_2d=None, method=None):
     return tuple(np.asarray(a).reshape((-1, ny, nx)) for a in (est.H_ml_, est.presence_lr_, est.presence_pvalue_))
 
 
+def abundance_interval_maps(est, shape_2d=None):
+    """``est.H_lower_`` and ``est.H_upper_`` (set by ``est.abundance_intervals()``) in the navigation shape, like the loadings:
+    (k, ny, nx) each - the ends of the profile-likelihood interval of every abundance; the upper map is the detection limit where
+    the lower one is 0."""
+    if not hasattr(est, "H_upper_"):
+        raise AttributeError("call est.abundance_intervals() first: it sets H_lower_ and H_upper_")
+    ny, nx = (int(v) for v in (shape_2d if shape_2d is not None else est.shape_2d))
+    return tuple(np.asarray(a).reshape((-1, ny, nx)) for a in (est.H_lower_, est.H_upper_))
+
+
 def calibrated_deviance_maps(est, shape_2d=None):
     """``est.deviance_z_`` and ``est.deviance_pvalue_`` (set by ``est.calibrate_deviance()``) in the navigation shape: (ny, nx) each."""
     if not hasattr(est, "deviance_z_"):

@@ -10,7 +10,11 @@ out.  Both are per-pixel maximum-likelihood problems given the spectra D:
   "pixel ML, Newton") - every pixel with a stop of its own and an optimality CERTIFICATE: ``gap`` bounds how far the
   pixel's deviance is above the minimum over {h >= 0, support in the set}, wherever no entry with counts sits under the floor;
 * ``presence``: the k + 1 nested fits, the likelihood-ratio statistic ``lr`` of every (component, pixel) - certified to within
-  ``tol`` on either side - and its asymptotic p-value under the boundary mixture 1/2 chi2_0 + 1/2 chi2_1.
+  ``tol`` on either side - and its asymptotic p-value under the boundary mixture 1/2 chi2_0 + 1/2 chi2_1;
+* ``ml_unmix_pinned`` and ``intervals``: how much of component j COULD be in this pixel - the best fit with h_j held at a per-pixel
+  value (the entry point espm_pixel_ml_pinned, csrc/mu_pixel_ml_pinned.hip, "pixel ML, pinned"), and the profile-likelihood interval
+  a root finder on the device builds from such fits: an upper limit where the abundance sits at the boundary, an asymmetric error
+  bar away from it.  ``presence``'s statistic is that profile at the single point 0.
 
 The ML abundances are also what ``H_std`` is formally a bound for, and with a ``simplex_H`` fit their column sums map the per-pixel
 dose or thickness that the simplex model cannot express.  EM is slow (hundreds of passes, tails of thousands) and cannot fail, and
@@ -155,6 +159,70 @@ class _Solver:
         return dict(H=Hd, deviance=dv, gap=gp, n_pass=passes, done=done, unmodelled=int(cnt[_lib.PML_UNMODELLED]),
                     nonfinite=int(cnt[_lib.PML_NONFINITE]))
 
+    def check_pin(self, pin, components):
+        """(pin, the fitted set, its bitmask): ``components`` None is every component but ``pin``; the set may be empty (k = 1)."""
+        if isinstance(pin, bool) or int(pin) != pin or not 0 <= int(pin) < self.k:
+            raise ValueError(f"{self.who}: pin must be one of the components 0 .. {self.k - 1}, not {pin!r}")
+        pin = int(pin)
+        if not self.s[pin] > 0:
+            raise ValueError(f"{self.who}: the spectrum of the pinned component {pin} is all zero")
+        if components is None:
+            components = [j for j in range(self.k) if j != pin]
+        if len(list(components)) == 0:
+            return pin, [], 0
+        comp, mask = self.check_components(components)
+        if pin in comp:
+            raise ValueError(f"{self.who}: the pinned component {pin} is in `components`: it is held, not fitted")
+        return pin, comp, mask
+
+    def run_pinned(self, start, comp, mask, pin, t, done=None, searching=None):
+        """One fit over the component set with component ``pin`` held at ``t`` (espm_pixel_ml_pinned), on the resident image: ``run``'s
+        dict plus ``slope`` (p,) and ``searching``.  ``t``: a device (p,) float64 tensor.  ``start`` as for ``run``; a device tensor is
+        updated IN PLACE (the next evaluation's warm start).  ``done``: None, or a device (p,) uint8 tensor (consumed) - a pixel
+        with done != 0 is not touched, and its deviance, gap, slope and n_pass read 0.  ``searching``: None, or a device integer the
+        caller counts its unfinished pixels in: it rides in the same transfer as the one counter read between the launches, comes
+        back as an int, and where it is 0 nothing more is launched."""
+        import ctypes as C
+
+        import torch
+
+        from espm_amd import _lib
+        from espm_amd.engine import _ptr, _stream
+        self.upload()
+        k, p = self.k, self.p
+        with self.image.scope():
+            if start is None:
+                Hd = torch.zeros((k, p), dtype=torch.float64, device=self.dev)
+                if comp:
+                    Hd[comp] = (self.counts() / float(self.s[comp].sum()))[None, :]
+            elif isinstance(start, torch.Tensor):
+                Hd = start
+                assert Hd.is_contiguous()
+            else:
+                Hd = torch.from_numpy(start).to(self.dev)
+            dv, gp, sl = (torch.zeros(p, dtype=torch.float64, device=self.dev) for _ in range(3))
+            passes = torch.zeros(p, dtype=torch.int32, device=self.dev)
+            done = torch.zeros(p, dtype=torch.uint8, device=self.dev) if done is None else done
+            counters = torch.zeros(_lib.PML_COUNTERS + 1, dtype=torch.int64, device=self.dev)   # the kernel's three, and `searching`
+            if searching is not None:
+                counters[_lib.PML_COUNTERS] = searching
+            extra = torch.empty((k + _lib.PMLN_STATE_EXTRA, p), dtype=torch.float64, device=self.dev)   # the kernel initialises it
+            s_ptr = self.s.ctypes.data_as(C.c_void_p)
+            args = (*self.image.abi(), _ptr(self.Dd), s_ptr, k, mask, pin, _ptr(t), self.log_shift, self.tol)
+            state = (_ptr(Hd), _ptr(dv), _ptr(gp), _ptr(sl), _ptr(passes), _ptr(done), _ptr(counters), _ptr(extra),
+                     extra.numel() * extra.element_size())
+            issued = 0
+            while issued < self.max_pass:
+                step = min(self.chunk, self.max_pass - issued)
+                _lib.check(_lib.lib.espm_pixel_ml_pinned(*args, step, *state, _stream()))
+                issued += step
+                cnt = counters.cpu().numpy()   # the one read-back between the chunks
+                if cnt[_lib.PML_NOT_DONE] == 0:
+                    break
+            cnt = counters.cpu().numpy()
+        return dict(H=Hd, deviance=dv, gap=gp, slope=sl, n_pass=passes, done=done, unmodelled=int(cnt[_lib.PML_UNMODELLED]),
+                    nonfinite=int(cnt[_lib.PML_NONFINITE]), searching=int(cnt[_lib.PML_COUNTERS]))
+
 
 def _result(r):
     """A ``run``'s dict on the host, as ``ml_unmix`` returns it."""
@@ -255,3 +323,147 @@ def presence(X, D, H0=None, tol=1e-3, max_pass=MAX_PASS, chunk=CHUNK, log_shift=
     return dict(H_ml=rows[0]["H"], deviance_ml=rows[0]["deviance"], lr=lr, pvalue=pvalue(lr),
                 converged=np.stack([r["converged"] for r in rows]), gap=np.stack([r["gap"] for r in rows]),
                 n_pass=np.stack([r["n_pass"] for r in rows]), unmodelled=rows[0]["unmodelled"], nonfinite=rows[0]["nonfinite"])
+
+
+# ---- how much of phase j could be in this pixel: profile-likelihood intervals of the abundances ----------------------------------------
+def _check_pinned_value(t, p, who):
+    t = np.asarray(t, dtype=np.float64)
+    if t.ndim == 0:
+        t = np.full(p, float(t))
+    if t.shape != (p,):
+        raise ValueError(f"{who}: t must be a scalar or of shape ({p},), not {t.shape}")
+    if not np.isfinite(t).all() or (t < 0).any():
+        raise ValueError(f"{who}: t must be finite and not negative")
+    return np.ascontiguousarray(t)
+
+
+def ml_unmix_pinned(X, D, pin, t, H0=None, components=None, tol=1e-3, max_pass=MAX_PASS, chunk=CHUNK, log_shift=1e-14, layout="cm"):
+    """``ml_unmix`` with the abundance of component ``pin`` HELD at ``t`` (a scalar, or (p,): a value per pixel) while the components
+    of ``components`` (None: all but ``pin``; may be empty) are fitted: one point of the profile likelihood of h_pin, by the rule of
+    include/espm_mu.h, "pixel ML, pinned" (the Newton step of ``method="newton"`` without its scale onto the ray, which a pinned term
+    leaves without a closed form).  Returns ``ml_unmix``'s dict - ``H`` with row ``pin`` equal to ``t`` bit for bit, and NOT scaled
+    onto sum_j s_j h_j = N - plus ``slope`` (p,) = 2 (s_pin - (D^T (x / y))_pin), the derivative of the profile deviance in t
+    (exact at the inner optimum, approximate at a certified point).  ``gap`` is this rule's own certificate,
+    2 sum_M (s_j - q_j) h_j + 2 N max(max_M q_j / s_j - 1, 0): ``deviance`` is above its minimum over the set, at this t, by at most that.
+    Arguments and refusals as for ``ml_unmix``; ValueError also for a ``pin`` that is no component or is in ``components``, a pinned
+    spectrum that is all zero and a ``t`` that is negative, not finite or of another shape - all before anything is uploaded."""
+    sv = _Solver(X, D, tol, max_pass, chunk, log_shift, layout, "ml_unmix_pinned", "newton")
+    start = sv.check_start(H0)
+    pin, comp, mask = sv.check_pin(pin, components)
+    t = _check_pinned_value(t, sv.p, sv.who)
+    sv.upload()
+    td, = sv.image.model(t)
+    r = sv.run_pinned(start, comp, mask, pin, td)
+    return dict(_result(r), slope=_image.to_host(r["slope"]))
+
+
+def threshold(level):
+    """2 erfinv(level)^2: the chi2_1 quantile of a two-sided interval at ``level`` (0.95: 3.8415)."""
+    from scipy.special import erfinv
+    if isinstance(level, bool) or not 0.0 < float(level) < 1.0:
+        raise ValueError(f"level must lie strictly between 0 and 1, not {level!r}")
+    return float(2.0 * erfinv(float(level)) ** 2)
+
+
+def intervals(X, D, H0=None, level=0.95, components=None, tol=1e-3, lr_tol=1e-2, max_eval=64, max_pass=MAX_PASS, chunk=CHUNK,
+              log_shift=1e-14, layout="cm"):
+    """How much of component j could be in pixel q?  The PROFILE-LIKELIHOOD interval of every abundance: the values t whose best fit
+    with h_j held at t (``ml_unmix_pinned``) lies within the chi2_1 quantile ``threshold`` = 2 erfinv(level)^2 of the pixel's best fit
+    (``ml_unmix(method="newton")``).  Where the abundance sits at the boundary the interval starts at 0 and its upper end is an UPPER
+    LIMIT, the detection limit of the map; away from it the two ends are an asymmetric error bar.  ``presence``'s statistic is this
+    profile at the single point t = 0.  The intervals are two-sided: a one-sided 95 % upper limit is the upper end at ``level=0.90``.
+    Returns dict(
+
+    * ``H_ml`` (k, p), ``deviance_ml`` (p,): the full fit;
+    * ``lower``, ``upper`` (k, p): the ends, with |g(t) - deviance_ml - threshold| <= ``lr_tol`` for the certified pinned deviance g
+      (each of the two deviances within ``tol`` of its minimum); ``lower`` is EXACTLY 0 where ``H_ml`` is 0 and where
+      g(0) - deviance_ml <= threshold (``presence``'s lr <= threshold: the boundary); NaN in the rows that were not requested and
+      for the pixels that did not finish; a pixel without a count has lower = 0 and upper = threshold / (2 s_j);
+    * ``level``, ``threshold``;
+    * ``converged`` (k, 2, p) bool, ``n_eval`` (k, 2, p): the pinned fits an end took, ``n_pass`` (k, 2, p): their passes in all
+      ([:, 0] the lower end, [:, 1] the upper);
+    * ``unmodelled``, ``nonfinite``: of the full fit).
+
+    The root finder runs on the device in fp64, elementwise over the pixels, every pixel with a bracket of its own: the upper end
+    starts at h_ml + sqrt(threshold) sqrt(s_j h_ml + threshold) / s_j and the open bracket grows geometrically; the next point is the
+    Newton step on the convex profile with ``ml_unmix_pinned``'s ``slope`` where it falls inside the bracket and the midpoint where it
+    does not.  Every evaluation is one pinned fit of the pixels still searching, warm-started at the evaluation before (its fitted
+    abundances lifted to at least N / ((k - 1) s_i) * 1e-3, the fill of a start that is not positive); finished
+    pixels are retired through the kernel's ``done``, and between launches the counters are read back and nothing else.  At most
+    ``max_eval`` evaluations per end.
+
+    What the interval is NOT: it holds the spectra D fixed, imposes no regulariser and no simplex, and is asymptotic (``sampling``
+    draws the replicates a calibration of its coverage needs).  ``components``: the rows to compute (None: all); the fits are always
+    over all k components, each of which needs a spectrum that is not all zero.  Other arguments and refusals as for ``ml_unmix``;
+    ValueError also for ``level`` outside (0, 1), ``lr_tol`` not positive and ``max_eval`` below 1 - before anything is uploaded."""
+    import torch
+    q = threshold(level)
+    if not lr_tol > 0:
+        raise ValueError("lr_tol must be positive")
+    max_eval = _positive_int(max_eval, "max_eval")
+    sv = _Solver(X, D, tol, max_pass, chunk, log_shift, layout, "intervals", "newton")
+    start = sv.check_start(H0)
+    every, mask = sv.check_components(None)
+    k, p = sv.k, sv.p
+    rows = _components(components, k)[0]
+    full = sv.run(start, every, mask)
+    with sv.image.scope():
+        dev = sv.dev
+        H_ml, dev_ml, ok = full["H"], full["deviance"], full["done"] == 1
+        nan = float("nan")
+        lower, upper = (torch.full((k, p), nan, dtype=torch.float64, device=dev) for _ in range(2))
+        conv = torch.zeros((k, 2, p), dtype=torch.bool, device=dev)
+        n_eval, n_pass = (torch.zeros((k, 2, p), dtype=torch.int64, device=dev) for _ in range(2))
+        # what a warm start is lifted to: the kernel's own fill N / (|M| s_i) * 1e-3 of a start that is not positive
+        lift = None if k == 1 else (sv.counts()[None, :] / ((k - 1) * torch.from_numpy(sv.s).to(dev))[:, None]) * 1e-3
+        for j in rows:
+            rest = [i for i in every if i != j]
+            rmask = mask & ~(1 << j)
+            h_ml = H_ml[j]
+            w0 = (q ** 0.5) * torch.sqrt(float(sv.s[j]) * h_ml + q) / float(sv.s[j])
+            for side in (0, 1):
+                up = side == 1
+                out = torch.full((p,), nan, dtype=torch.float64, device=dev)
+                active = ok.clone()
+                if up:
+                    lo, hi, t = h_ml.clone(), torch.full_like(h_ml, float("inf")), h_ml + w0
+                else:
+                    lo, hi, t = torch.zeros_like(h_ml), h_ml.clone(), torch.zeros_like(h_ml)
+                    zero = active & (h_ml == 0)
+                    out = torch.where(zero, torch.zeros_like(out), out)
+                    conv[j, side] |= zero
+                    active &= ~zero
+                Hc = H_ml.clone()
+                for ev in range(max_eval):
+                    if rest:   # (an abundance the evaluation before drove to 1e-13 may have to come back: from there it grows slowly)
+                        Hc[rest] = torch.maximum(Hc[rest], lift[rest])
+                    r = sv.run_pinned(Hc, rest, rmask, j, t.contiguous(), done=(~active).to(torch.uint8), searching=active.sum())
+                    if r["searching"] == 0:   # (that launch found every pixel retired: its workgroups returned at once)
+                        break
+                    fitted = active & (r["done"] == 1)
+                    phi = r["deviance"] - dev_ml - q
+                    fin = fitted & (phi.abs() <= lr_tol)
+                    if not up and ev == 0:
+                        fin |= fitted & (phi <= 0)   # the boundary: the interval reaches 0
+                    out = torch.where(fin, t, out)
+                    conv[j, side] |= fin
+                    n_eval[j, side] += active
+                    n_pass[j, side] += torch.where(active, r["n_pass"].to(torch.int64), torch.zeros_like(n_pass[j, side]))
+                    go = fitted & ~fin
+                    inner = (phi < 0) if up else (phi > 0)   # the evaluated point replaces the lower end of the bracket
+                    lo, hi = torch.where(go & inner, t, lo), torch.where(go & ~inner, t, hi)
+                    tn = t - phi / r["slope"]
+                    open_ = torch.isinf(hi)
+                    good = torch.isfinite(tn) & (tn > lo) & (tn < hi)
+                    tn = torch.where(open_, torch.minimum(tn, h_ml + 8.0 * (t - h_ml)), tn)
+                    mid = torch.where(open_, h_ml + 2.0 * (t - h_ml), 0.5 * (lo + hi))
+                    nxt = torch.where(good, tn, mid)
+                    if not up and ev == 0:   # (the slope at t = 0 belongs to the floor where nothing else is fitted)
+                        nxt = torch.maximum(h_ml - w0, 0.5 * h_ml)
+                    t = torch.where(go, nxt, t)
+                    active = go
+                (upper if up else lower)[j] = out
+        host = _image.to_host
+        res = _result(full)
+        return dict(H_ml=res["H"], deviance_ml=res["deviance"], lower=host(lower), upper=host(upper), level=float(level), threshold=q,
+                    converged=host(conv), n_eval=host(n_eval), n_pass=host(n_pass), unmodelled=res["unmodelled"], nonfinite=res["nonfinite"])

@@ -65,7 +65,10 @@
  *   espm_pixel_ml_newton  <- (new) the same problem, certificate and stop by a safeguarded Newton step (EM's diagonal metric blended
  *                            into the Hessian, a fraction-to-boundary clamp, the EM successor after a rejected trial): tens of
  *                            passes where EM takes hundreds to thousands; no reference analogue
- *   espm_lu_pl           <- espm/estimators/updates.py:179 -> scikit-learn's _initialize_nmf -> _randomized_range_finder: the LU
+ *   espm_pixel_ml_pinned  <- (new) the same problem with one abundance held at a per-pixel value while the others are fitted, a
+ *                            certificate of its own and the slope of the profile deviance: the evaluation behind profile-likelihood
+ *                            intervals of the abundances (upper limits at the boundary); no reference analogue
+ *   espm_lu_pl          <- espm/estimators/updates.py:179 -> scikit-learn's _initialize_nmf -> _randomized_range_finder: the LU
  *                            normaliser of its power iterations (scipy.linalg.lu(A, permute_l=True)[0]) on tall device matrices
  *
  * Conventions
@@ -1128,6 +1131,54 @@ int espm_pixel_ml(const void* x, int x_dtype, int x_layout, int64_t ld, int n, i
 int espm_pixel_ml_newton(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, const double* d, const double* s, int k,
                          uint32_t mask, double log_shift, double tol, int n_pass, double* h_inout, double* dev, double* gap, int32_t* passes,
                          uint8_t* done, uint64_t* counters, void* state, size_t state_bytes, espm_stream_t stream);
+
+/* ---- pixel ML, pinned (csrc/mu_pixel_ml_pinned.hip; espm_amd.presence.ml_unmix_pinned, intervals; NMFEstimator.abundance_intervals) ----
+ * One point of the PROFILE likelihood of an abundance: the pixel's best Poisson fit over the component set M with component `pin`
+ * (not in M) held at the pixel's own value t[q] - the deviance g(t) whose level set {t: g(t) - min deviance <= chi2_1 quantile} is the
+ * profile-likelihood interval of h_pin, and whose value at t = 0 is the reduced fit of the presence test.  Arguments as for
+ * espm_pixel_ml_newton, plus pin, t (p,) and slope (p,), DEVICE arrays of doubles; the state has the Newton layout
+ * (ESPM_PMLN_STATE_BYTES(k, p); the kernel initialises it for a pixel that enters with passes == 0).  mask MAY be empty (k = 1, or the
+ * caller's choice): then the pixel is done in its first pass.
+ * THE RULE, all in fp64, for the pixel with the counts x; N as in espm_pixel_ml:
+ *   t[q] negative or not finite: the pixel stops at once with done = 2, adds to counters[ESPM_PML_NONFINITE], and h, dev, gap, slope
+ *     and passes stay as the call found them (dev, gap, slope 0 where passes == 0).
+ *   at EVERY entry: h_pin = t[q] (never updated by a step); h_j = 0 for j outside M and not pin; N == 0: h_j = 0 for j in M.
+ *   start (passes == 0 on entry): for j in M an h_j that is not > 0 becomes N / (|M| s_j) * 1e-3; e = 0, dev_acc = +inf, tau = 1e-2,
+ *     trial = 0.
+ *   one pass:
+ *     (no scale onto the ray: step 1 of the other two rules is dropped - with a pinned term the scale of least deviance has no closed
+ *      form - so h is the same before and after the walk)
+ *     2  the walk of espm_pixel_ml_newton's step 2 over all k components, the pinned one included in y: y, the floor, w, dev, q_j for
+ *        every j, and the triangle A
+ *     3  for j in M ascending: r_j = q_j / s_j; rmax = max(rmax, r_j) from -inf; lin = fma(s_j - q_j, h_j, lin) from 0
+ *     4  gap = 2 fma(N, max(rmax - 1, 0), lin); slope = 2 (s_pin - q_pin)
+ *        THE CERTIFICATE: the deviance f is convex in h_M, its gradient is 2 (s_i - q_i), so for the minimiser h* over {h_M >= 0}
+ *        f(h) - f(h*) <= grad . (h - h*) = 2 sum_M (s_i - q_i) h_i + 2 sum_M (q_i / s_i - 1) s_i h*_i
+ *                     <= 2 lin + 2 max(rmax - 1, 0) sum_M s_i h*_i, and at the optimum (complementary slackness, h*_i (s_i - q*_i) = 0)
+ *        sum_M s_i h*_i = sum_M h*_i q*_i = sum_c x_c (y*_c - t d_c,pin) / y*_c <= N.  It holds wherever no entry with counts is
+ *        floored, as the certificates of the other two rules.  With M empty gap = 0.
+ *        THE SLOPE: by the envelope theorem d/dt min_{h_M} f = df/dh_pin at the inner optimum = 2 (s_pin - q_pin); at a point that is
+ *        certified and not optimal it is approximate - a hint for a root finder that keeps a bracket.
+ *     5  dev or gap not finite: done = 2, h as it stands, dev, gap and slope as computed, counters[ESPM_PML_NONFINITE].
+ *        REJECT / ACCEPT, the stop gap <= tol, tau, the EM successor e_j = h_j r_j (monotone: the pinned term is a fixed background of
+ *        the EM model), B = A over M with B_jj = fma(tau, s_j / h_j, A_jj), the root-free Cholesky with every component outside M -
+ *        the pinned one too - a row of the identity, the step and the clamps at 0.01 h_j and 1e-30 N / s_j: espm_pixel_ml_newton's
+ *        step 5 word for word, with h for its scaled h and h_pin = t[q] after every step.  dev, gap and slope are reported for
+ *        ACCEPTED points only.
+ *   N == 0 needs no case of its own: h_M = 0, the first pass finds q = 0 and gap = 0 and the pixel is done with
+ *   dev = 2 sum_c max(t d_c,pin, log_shift) and 0 passes.
+ * RESUMABLE as espm_pixel_ml_newton is (h_inout, dev, gap, slope, passes, done and state carry a pixel from call to call: n_pass = a
+ * then b leaves the bits of a + b).  THE CALLER'S done IS HONOURED: a pixel that enters with done != 0 is neither read nor written
+ * (h_inout, dev, gap, slope, passes, state: bit-untouched), and a workgroup with no pixel entered returns at once - how a root finder
+ * retires the pixels whose endpoint it has found.  Counters, geometry, independence of neighbours, layout, dtype and slabs (a slab
+ * slices t and slope as it slices h) as for espm_pixel_ml.  No float atomics.
+ * ESPM_EINVAL, before the device is touched: espm_pixel_ml_newton's refusals but for the empty mask, and pin outside 0 .. k - 1, pin
+ * inside mask, s[pin] not > 0 (or not finite), a null t or slope.  ESPM_EUNSUPPORTED for k outside 1..ESPM_PML_MAX_K.  Only the narrow
+ * build has the kernels; the wide builds return ESPM_EUNSUPPORTED.  No espm_mu_state is involved: ESPM_MU_ABI_VERSION stays. */
+int espm_pixel_ml_pinned(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, const double* d, const double* s, int k,
+                         uint32_t mask, int pin, const double* t, double log_shift, double tol, int n_pass, double* h_inout, double* dev,
+                         double* gap, double* slope, int32_t* passes, uint8_t* done, uint64_t* counters, void* state, size_t state_bytes,
+                         espm_stream_t stream);
 
 /* ---- LDS of the sparse H-step (csrc/mu_ell_plan.hpp: plan_h_ell; espm_amd.ell.lds_bytes_h, the store choice of espm_amd.store) ----
  * Dynamic LDS, in bytes, that the H-step of the sparse count store (x_dtype = ESPM_X_ELL) takes for n_pad channels and k components

@@ -5,7 +5,12 @@ yardstick: an EM pass does strictly less arithmetic per entry (2 k FMAs, one div
 k (k + 1) / 2 FMAs), a Newton pass the two together.
 
     python tools/analysis/pixel_ml_time.py [--size n,nx,ny] [--k 5] [--counts 500] [--runs 3] [--max-pass 20000] [--method em|newton|both]
-                                           [--no-presence] [--out FILE]
+                                           [--no-presence] [--pinned] [--out FILE]
+
+``--pinned``: also espm_pixel_ml_pinned (csrc/mu_pixel_ml_pinned.hip) - the time of one pinned pass against one Newton pass, the two
+INTERLEAVED in one process (Newton with 1 pass, pinned with 1, Newton with 3, pinned with 3, and again: the same walk plus one
+output, so the two should agree), the last component held at 1.5 times its start; and ``presence.intervals`` end to end with its
+evaluation and pass counts per percentile of the pixels.
 
 X is device-resident (synthetic Poisson counts drawn on the device from ``pixel_diagnostics_time.model``).  The time per pass is the
 difference of two calls from the same fresh state, with 4 and with 12 passes (EM) or with 1 and with 3 (Newton, whose pixels stop
@@ -42,6 +47,25 @@ def passes_call(X, D, s, H, state, n_pass, tol, method="em"):
         _lib.check(_lib.lib.espm_pixel_ml(*args, _stream()))
 
 
+def pinned_call(X, D, s, H, state, t, slope, n_pass, tol):
+    dv, gp, passes, done, counters = state
+    n, p = X.shape
+    k = D.shape[1]
+    extra = torch.empty((k + _lib.PMLN_STATE_EXTRA, p), dtype=torch.float64, device="cuda")
+    _lib.check(_lib.lib.espm_pixel_ml_pinned(_ptr(X), pdt.CODES[X.dtype], _lib.LAYOUT_CM, int(X.stride(0)), n, p, _ptr(D), s.ctypes.data, k,
+                                             (1 << (k - 1)) - 1, k - 1, _ptr(t), float(log_shift), tol, n_pass, _ptr(H), _ptr(dv), _ptr(gp),
+                                             _ptr(slope), _ptr(passes), _ptr(done), _ptr(counters), _ptr(extra), extra.numel() * 8, _stream()))
+
+
+def event_ms(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1)
+
+
 def fresh(p, k, H0):
     return H0.clone(), (torch.zeros(p, dtype=torch.float64, device="cuda"), torch.zeros(p, dtype=torch.float64, device="cuda"),
                         torch.zeros(p, dtype=torch.int32, device="cuda"), torch.zeros(p, dtype=torch.uint8, device="cuda"),
@@ -57,6 +81,7 @@ def main():
     ap.add_argument("--max-pass", type=int, default=presence.MAX_PASS)
     ap.add_argument("--method", choices=("em", "newton", "both"), default="em")
     ap.add_argument("--no-presence", action="store_true")
+    ap.add_argument("--pinned", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     require_gpu()
@@ -116,6 +141,51 @@ def main():
                 qj = np.percentile(npass[1 + j], [50, 99, 100])
                 say(f"  {method}: without component {j}: {qj[0]:.0f} / {qj[1]:.0f} / {qj[2]:.0f} passes; {res['converged'][1 + j].mean():.6f} converged")
             say(f"  {method}: presence, {k + 1} nested fits, read-backs included: {total:.2f} s; median lr per component {np.median(res['lr'], axis=1)}")
+    if args.pinned and k >= 2:
+        t = (1.5 * H0[k - 1]).contiguous()
+        slope = torch.zeros(p, dtype=torch.float64, device="cuda")
+        left = {}
+
+        def newton(n_pass):
+            H, state = fresh(p, k, H0)
+            passes_call(X, D, s, H, state, n_pass, tol, "newton")
+            left["newton", n_pass] = state[4]
+
+        def pinned(n_pass):
+            H, state = fresh(p, k, H0)
+            pinned_call(X, D, s, H, state, t, slope, n_pass, tol)
+            left["pinned", n_pass] = state[4]
+
+        order = [("newton", newton, 1), ("pinned", pinned, 1), ("newton", newton, 3), ("pinned", pinned, 3)]
+        for _, fn, n_pass in order:   # warm-up
+            fn(n_pass)
+        torch.cuda.synchronize()
+        ms = {(name, n_pass): [] for name, _, n_pass in order}
+        for _ in range(args.runs):
+            for name, fn, n_pass in order:
+                ms[name, n_pass].append(event_ms(lambda: fn(n_pass)))
+        per = {}
+        for name in ("newton", "pinned"):
+            for n_pass in (1, 3):
+                v = ms[name, n_pass]
+                say(f"  interleaved, {name}, {n_pass} passes from a fresh state: {min(v):8.3f} - {max(v):8.3f} ms, "
+                    f"{int(left[name, n_pass][_lib.PML_NOT_DONE])} of {p} pixels not done")
+            d = [(b - a) / 2 for a, b in zip(ms[name, 1], ms[name, 3])]
+            per[name] = (min(d), max(d))
+            say(f"  interleaved, {name}: time per pass: {min(d):8.3f} - {max(d):8.3f} ms")
+        say(f"  pinned / newton, time per pass: {per['pinned'][0] / per['newton'][0]:.3f} (min over min)")
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = presence.intervals(X, D.cpu().numpy(), tol=tol, max_pass=args.max_pass)
+        torch.cuda.synchronize()
+        total = time.perf_counter() - t0
+        ne, npx = res["n_eval"].sum(axis=(0, 1)), res["n_pass"].sum(axis=(0, 1))
+        qe, qp = np.percentile(ne, [50, 99, 100]), np.percentile(npx, [50, 99, 100])
+        say(f"  intervals, level 0.95, {2 * k} ends per pixel, read-backs included: {total:.2f} s; {res['converged'].mean():.6f} of the ends converged")
+        say(f"  intervals: pinned fits per pixel over all ends, 50th / 99th / last percentile: {qe[0]:.0f} / {qe[1]:.0f} / {qe[2]:.0f}; "
+            f"passes: {qp[0]:.0f} / {qp[1]:.0f} / {qp[2]:.0f}; per end at most {res['n_eval'].max()} fits and {res['n_pass'].max()} passes")
+        say(f"  intervals: lower end at 0 in {np.mean(res['lower'] == 0):.4f} of the entries; median width per component "
+            f"{np.nanmedian(res['upper'] - res['lower'], axis=1)}")
 
 
 if __name__ == "__main__":
