@@ -1,7 +1,7 @@
 """What an estimator does with a fit besides fitting (no reference analogue; ``NMFEstimator`` inherits the mixin): the fits around
 ``fit_transform`` - on the binned image, on a thinned image - and the analyses of a fitted model - diagnostics, count attribution,
 line maps and region spectra, residual components, draws from the model.  Each method prepares host arrays and hands them to ``espm_amd.binning``,
-``splitting``, ``measures``, ``attribution``, ``marginals``, ``residuals`` or ``sampling``, imported when it is called; the set-up they share stands once, ahead of them.  The fit itself, ``unmix``
+``splitting``, ``measures``, ``attribution``, ``marginals``, ``residuals``, ``presence``, ``spectra_ml`` or ``sampling``, imported when it is called; the set-up they share stands once, ahead of them.  The fit itself, ``unmix``
 and the engine plumbing are next door in base.py.
 """
 from __future__ import annotations
@@ -527,6 +527,54 @@ class _FitAnalysis:
         self.H_ml_, self.deviance_ml_ = out["H_ml"], out["deviance_ml"]
         if self.hspy_comp:
             out = dict(out, H_ml=out["H_ml"].T, lower=out["lower"].T, upper=out["upper"].T)
+        return out
+
+    # ---- is element e in phase j at all: the ML of W given H and nested likelihood-ratio tests on its entries --------------------------
+    def element_presence(self, X=None, entries=None, tol=1e-3, max_pass=None):
+        """Is element e present in phase j?  ``espm_amd.spectra_ml.presence`` on the dictionary or physics model ``G_`` and the fitted
+        abundances ``H_``, started at ``W_``: the Poisson maximum-likelihood W >= 0 given the abundances, and for every tested entry
+        the likelihood ratio between that fit and the best fit WITH THE ENTRY HELD AT ZERO - the honest statistic where a
+        concentration sits at or near zero (a trace element) and the Wald bar ``W_std_`` (which ignores active floors) means nothing.
+        No reference analogue.
+
+        Sets, all oriented as ``W_``: ``W_ml_`` (m, k) and ``W_deviance_ml_``, the full fit; ``W_presence_lr_`` (m, k) =
+        max(deviance without (e, j) - deviance_ml, 0) and ``W_presence_pvalue_`` (m, k) = 1/2 erfc(sqrt(lr / 2)), the tail of the
+        boundary mixture 1/2 chi2_0 + 1/2 chi2_1 (asymptotic), both NaN for entries that were not tested; ``W_presence_entries_``
+        (E, 2), the tested (element, component) pairs; and ``W_ml_converged_`` (bool), ``W_ml_gap_``, ``W_ml_n_pass_``, each
+        (1 + E,): the full fit, then the fit without each tested entry.  Returns ``spectra_ml.presence``'s dict.
+
+        The ML is over W >= 0 with ``H_`` held: ``mu``, ``simplex_W`` and the floors of the fit are NOT imposed, so
+        ``W_deviance_ml_`` is at most the fit's own deviance (+ tol).  Entries that ``fixed_W`` imposes at 0 leave the free set: their
+        ``W_ml_`` is 0 and their lr NaN.  Entries imposed at a positive value, an identity G (``G=None``: the problem decouples per
+        channel) and more than 8 components raise NotImplementedError; m k is at most 2048.  Every refusal happens before anything
+        is uploaded.
+
+        ``entries``: (E, 2) index pairs into ``W_`` to test (None: every free entry the model sees); ``tol``: the certified gap, in
+        deviance units, at which a fit stops; ``max_pass``: the cap of a fit's passes over the image (None:
+        ``spectra_ml.MAX_PASS``).  ``X`` as for ``pixel_diagnostics``; ``X=None`` takes the fit's ``X_`` un-scaled, with the cost and
+        the ``log_shift`` fill described there (refused after ``fit_binned``).  Computed in fp64 whatever the estimator's precision,
+        on the current device (a ``shard()``ed estimator: every rank computes everything on its own device)."""
+        from espm_amd import spectra_ml
+        check_is_fitted(self, "W_")
+        k = int(self.H_.shape[0])
+        if k > spectra_ml.MAX_K:
+            raise NotImplementedError(f"element_presence: {k} components (the kernel is built for 1..{spectra_ml.MAX_K})")
+        G, W, H = self._model_factors()
+        if G is None:
+            raise NotImplementedError("element_presence: needs a dictionary or physics model G (with an identity G the problem "
+                                      "decouples per channel)")
+        free = None
+        if self.fixed_W is not None:
+            fixed = np.asarray(self.fixed_W)
+            if (fixed > 0).any():
+                raise NotImplementedError("element_presence: fixed_W entries imposed at a positive value are not covered")
+            free = ~(fixed == 0)
+        X, layout = self._image_argument(X, "element_presence")
+        out = spectra_ml.presence(X, G, H, W0=W, free=free, entries=entries, tol=tol,
+                                  max_pass=spectra_ml.MAX_PASS if max_pass is None else max_pass, log_shift=self.log_shift, layout=layout)
+        self.W_ml_, self.W_deviance_ml_ = out["W_ml"], out["deviance_ml"]
+        self.W_presence_lr_, self.W_presence_pvalue_, self.W_presence_entries_ = out["lr"], out["pvalue"], out["entries"]
+        self.W_ml_converged_, self.W_ml_gap_, self.W_ml_n_pass_ = out["converged"], out["gap"], out["n_pass"]
         return out
 
     # ---- draws from the fitted model: a simulated image, a scale for the deviance map, the parametric bootstrap -------------------

@@ -215,6 +215,16 @@ def presence_maps(est, shape_2d=None, method=None):
     return tuple(np.asarray(a).reshape((-1, ny, nx)) for a in (est.H_ml_, est.presence_lr_, est.presence_pvalue_))
 
 
+def element_presence(est):
+    """What ``est.element_presence()`` set, as a dict of (elements, phases) tables beside ``W_``: ``W_ml`` (the maximum-likelihood
+    concentrations given the abundances), ``lr`` (the likelihood-ratio statistic of every entry's presence), ``pvalue`` (its
+    asymptotic p-value; NaN where the entry was not tested), and ``entries``, ``converged``, ``gap``, ``n_pass`` of the fits."""
+    if not hasattr(est, "W_presence_lr_"):
+        raise AttributeError("call est.element_presence() first: it sets W_ml_, W_presence_lr_ and W_presence_pvalue_")
+    return dict(W_ml=est.W_ml_, deviance_ml=est.W_deviance_ml_, lr=est.W_presence_lr_, pvalue=est.W_presence_pvalue_,
+                entries=est.W_presence_entries_, converged=est.W_ml_converged_, gap=est.W_ml_gap_, n_pass=est.W_ml_n_pass_)
+
+
 def abundance_interval_maps(est, shape_2d=None):
     """``est.H_lower_`` and ``est.H_upper_`` (set by ``est.abundance_intervals()``) in the navigation shape, like the loadings:
     (k, ny, nx) each - the ends of the profile-likelihood interval of every abundance; the upper map is the detection limit where

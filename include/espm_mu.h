@@ -1180,6 +1180,31 @@ int espm_pixel_ml_pinned(const void* x, int x_dtype, int x_layout, int64_t ld, i
                          double* gap, double* slope, int32_t* passes, uint8_t* done, uint64_t* counters, void* state, size_t state_bytes,
                          espm_stream_t stream);
 
+/* ---- spectra ML pass (csrc/mu_spectra_ml.hip; espm_amd.spectra_ml, NMFEstimator.element_presence) ----
+ * What one pass of the maximum-likelihood fit of W given H needs from the image (the rule itself is small dense algebra above this
+ * pass: espm_amd/spectra_ml.py): the sums of espm_channel_diagnostics under the OBSERVED weights, in one fp64
+ * pass over X that reduces over the pixels.  x, x_dtype (ESPM_DIAG_X_*), x_layout, ld, d (n, k), h (k, p) and log_shift are exactly
+ * as for espm_channel_diagnostics.  Per entry: y = sum_j d[c, j] h[j, p] (fma, j ascending); floored = !(y >= log_shift);
+ * y = floored ? log_shift : y; i = 1 / y; w = x * i; v = w * i.  Per channel c (all outputs fp64):
+ *   dev[c]       = 2 sum_p (x ln(w) - x + y), the first term 0 where x == 0
+ *   xsum[c]      = sum_p x (exact for counts), ysum[c] = sum_p y
+ *   q[c, j]      (n, k): sum_p w h[j, p] - Q = (X / Y) H^T; with a dictionary G^T Q is the numerator of the multiplicative W step
+ *   a_tri[c, t]  (n, k (k + 1) / 2): the lower triangle, row by row as m_tri, of A_c = sum_p v h_p h_p^T, the observed information
+ *                  of row c of d with the abundances held; that of W in d = G W is F_obs = sum_c (g_c g_c^T) (x) A_c.
+ *   *unmodelled  (device, zeroed by the call): the entries with x > 0 that are floored - an integer sum, the only thing accumulated
+ *                  atomically.
+ * Geometry, scratch layout (espm_spectra_ml_pass_scratch(n, p, k) bytes: chunks x (3 + k + k (k + 1) / 2) x n doubles) and the
+ * second launch that adds the chunks in ascending order are espm_channel_diagnostics': two calls, the two layouts of one image,
+ * every dtype that holds the same values and rows padded by ld give the same bits (a split of the pixels into slabs does not: the
+ * chunk sums change).  k = 1..ESPM_DIAG_MAX_K.  ESPM_EINVAL, before the device is touched, for a null pointer, a layout or dtype
+ * that does not exist, ld below the row length, n or p below 1, log_shift not positive, or scratch_bytes below what the query
+ * returns (the message names both sizes); ESPM_EUNSUPPORTED for k outside 1..ESPM_DIAG_MAX_K.  Only the narrow build has the kernels;
+ * the wide builds return ESPM_EUNSUPPORTED, and their query returns 0.  No espm_mu_state is involved: ESPM_MU_ABI_VERSION stays. */
+int espm_spectra_ml_pass(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, const double* d, const double* h, int k,
+                         double log_shift, double* dev, double* xsum, double* ysum, double* q, double* a_tri, int64_t* unmodelled,
+                         void* scratch, size_t scratch_bytes, espm_stream_t stream);
+size_t espm_spectra_ml_pass_scratch(int n, int p, int k);
+
 /* ---- LDS of the sparse H-step (csrc/mu_ell_plan.hpp: plan_h_ell; espm_amd.ell.lds_bytes_h, the store choice of espm_amd.store) ----
  * Dynamic LDS, in bytes, that the H-step of the sparse count store (x_dtype = ESPM_X_ELL) takes for n_pad channels and k components
  * at the full tile (tile_px = ESPM_ELL_TILE) without the copy of colsum(GW') that a riding W tail adds: the G W table plus the
