@@ -452,17 +452,23 @@ class _FitAnalysis:
         The ML is over h >= 0 alone: the regularisers of the fit (``mu``, ``lambda_L``) and ``simplex_H`` are NOT imposed.  A fit
         without ``simplex_H`` therefore has ``deviance_ml_ <= deviance_`` (+ tol) in every pixel.  Under ``simplex_H`` the per-pixel ML
         frees the pixel's scale: the fit's model is a sub-model of it, and ``H_ml_.sum(0)`` is a map of the per-pixel dose or thickness
-        that the simplex model cannot express (a simplex-constrained ML is not provided).
+        that the simplex model cannot express.  ``method="simplex"`` is the ML OF the fit's model instead: sum h = 1 in every pixel,
+        the spectra carry the intensity, and the k reduced fits sum to 1 again (``presence.presence(method="simplex")``) - a test with
+        no parameter per pixel that the fit did not have.  It needs an estimator with ``simplex_H=True`` (ValueError otherwise, before
+        every other refusal) and at least two components; ``H_ml_`` then sums to 1 per pixel and ``ml_gap_`` is the Frank-Wolfe
+        certificate.
 
         ``tol``: the certified gap, in deviance units, at which a pixel stops; ``max_pass``: the cap of a pixel's EM passes (None:
         ``presence.MAX_PASS``) - EM takes hundreds of passes, with tails of thousands, and pixels still running at the cap are False in
         ``ml_converged_``.  ``method``: "em" (the default: the rule defined bit for bit) or "newton" (the safeguarded Newton step of
-        ``presence.ml_unmix``: the same certified statistic within ``tol``, tens of passes per pixel), the one method for all k + 1
-        fits; anything else is a ValueError.  ``X`` as for ``pixel_diagnostics``; ``X=None`` takes the fit's ``X_`` un-scaled, with the cost and the
+        ``presence.ml_unmix``: the same certified statistic within ``tol``, tens of passes per pixel) or "simplex" (above), the one
+        method for all k + 1 fits; anything else is a ValueError.  ``X`` as for ``pixel_diagnostics``; ``X=None`` takes the fit's ``X_`` un-scaled, with the cost and the
         ``log_shift`` fill described there (refused after ``fit_binned``).  Computed in fp64 whatever the estimator's precision, on the
         current device (a ``shard()``ed estimator: every rank computes all pixels on its own device); 1 .. 8 components
         (NotImplementedError beyond), all before anything is uploaded."""
         from espm_amd import presence
+        if method == "simplex" and not self.simplex_H:
+            raise ValueError("presence_maps: method='simplex' is the pixel model of a simplex_H fit, and this estimator has simplex_H=False")
         check_is_fitted(self, "W_")
         presence._check_method(method)
         k = int(self.H_.shape[0])
@@ -482,7 +488,7 @@ class _FitAnalysis:
         return out
 
     # ---- how much of phase j could be in this pixel: profile-likelihood intervals of the abundances -----------------------------------
-    def abundance_intervals(self, level=0.95, X=None, components=None, tol=1e-3, lr_tol=1e-2, max_eval=None):
+    def abundance_intervals(self, level=0.95, X=None, components=None, tol=1e-3, lr_tol=1e-2, max_eval=None, simplex=False):
         """How much of phase j could be in this pixel?  ``espm_amd.presence.intervals`` on the fitted spectra ``G_ @ W_``, started at
         ``H_``: for every pixel and every requested component the PROFILE-LIKELIHOOD interval of the abundance - the values t whose
         best fit with h_j held at t lies within the chi2_1 quantile 2 erfinv(level)^2 of the pixel's best fit.  Where an abundance
@@ -503,6 +509,12 @@ class _FitAnalysis:
         ASYMPTOTIC - at a few tens of counts per pixel, and where other abundances sit on their boundaries, its coverage is a guide
         (``sampling`` / ``simulate`` draw the replicates a calibration would need).
 
+        ``simplex=True``: the interval of a phase FRACTION under the fit's own pixel model, sum h = 1
+        (``presence.intervals(simplex=True)``): 0 <= ``H_lower_`` <= ``H_ml_`` <= ``H_upper_`` <= 1, an upper end of exactly 1 where
+        the pixel could be all phase j, and ``H_ml_`` the constrained fit.  It needs an estimator with ``simplex_H=True`` (ValueError
+        otherwise, before every other refusal).  ``H_interval_simplex_`` (bool) records which of the two the attributes hold.  The
+        spectra are still fixed, the regularisers still off, the level still asymptotic.
+
         ``level``: strictly between 0 and 1.  ``components``: the rows to compute (None: all).  ``tol``: the certified gap of every
         fit; ``lr_tol``: how close to the quantile an end's deviance difference must come; ``max_eval``: the cap of the pinned fits
         per end (None: 64).  ``X`` as for ``pixel_diagnostics``; ``X=None`` takes the fit's ``X_`` un-scaled, with the cost and the
@@ -510,6 +522,8 @@ class _FitAnalysis:
         the current device (a ``shard()``ed estimator: every rank computes all pixels on its own device); 1 .. 8 components
         (NotImplementedError beyond), all before anything is uploaded."""
         from espm_amd import presence
+        if simplex and not self.simplex_H:
+            raise ValueError("abundance_intervals: simplex=True is the pixel model of a simplex_H fit, and this estimator has simplex_H=False")
         check_is_fitted(self, "W_")
         presence.threshold(level)
         k = int(self.H_.shape[0])
@@ -521,7 +535,9 @@ class _FitAnalysis:
         G, W, H = self._model_factors()
         D = W if G is None else G @ W
         out = presence.intervals(X, D, H, level=level, components=components, tol=tol, lr_tol=lr_tol,
-                                 max_eval=64 if max_eval is None else max_eval, log_shift=self.log_shift, layout=layout)
+                                 max_eval=64 if max_eval is None else max_eval, log_shift=self.log_shift, layout=layout,
+                                 simplex=bool(simplex))
+        self.H_interval_simplex_ = bool(simplex)
         self.H_lower_, self.H_upper_, self.H_interval_level_ = out["lower"], out["upper"], out["level"]
         self.H_interval_converged_, self.H_interval_n_eval_ = out["converged"], out["n_eval"]
         self.H_ml_, self.deviance_ml_ = out["H_ml"], out["deviance_ml"]

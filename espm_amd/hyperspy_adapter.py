@@ -205,8 +205,9 @@ def diagnostic_maps(est, shape_2d=None):
 def presence_maps(est, shape_2d=None, method=None):
     """``est.H_ml_``, ``est.presence_lr_`` and ``est.presence_pvalue_`` (set by ``est.presence_maps()``) in the navigation shape, like
     the loadings: (k, ny, nx) each - the per-pixel ML abundances, the likelihood-ratio statistic of every phase's presence and its
-    asymptotic p-value.  ``method``: None takes the maps as the last ``est.presence_maps()`` left them; "em" or "newton" runs
-    ``est.presence_maps(method=method)`` on the fit's own image first."""
+    asymptotic p-value.  ``method``: None takes the maps as the last ``est.presence_maps()`` left them; "em", "newton" or
+    "simplex" (the test under sum h = 1, for an estimator with ``simplex_H=True``) runs ``est.presence_maps(method=method)`` on the
+    fit's own image first."""
     if method is not None:
         est.presence_maps(method=method)
     if not hasattr(est, "presence_lr_"):

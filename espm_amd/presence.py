@@ -17,8 +17,10 @@ out.  Both are per-pixel maximum-likelihood problems given the spectra D:
   bar away from it.  ``presence``'s statistic is that profile at the single point 0.
 
 The ML abundances are also what ``H_std`` is formally a bound for, and with a ``simplex_H`` fit their column sums map the per-pixel
-dose or thickness that the simplex model cannot express.  EM is slow (hundreds of passes, tails of thousands) and cannot fail, and
-it is the default; the Newton rule reaches the same certified points in tens of passes.  The
+dose or thickness that the simplex model cannot express.  ``method="simplex"`` / ``simplex=True`` solve the pixel problem OF that
+model instead - sum h = 1, the spectra carry the intensity (espm_pixel_ml_simplex, csrc/mu_pixel_ml_simplex.hip, "pixel ML,
+simplex") - so that the tests and the intervals are about phase fractions, with no scale per pixel that the fit did not have.
+EM is slow (hundreds of passes, tails of thousands) and cannot fail, and it is the default; the Newton rule reaches the same certified points in tens of passes.  The
 kernel runs a bounded number of passes per launch and the loop here reads one integer, the pixels not yet done, between launches.
 fp64 throughout, no float atomics: two calls, both layouts, every dtype that holds the counts and every ``chunk`` give the same bits.
 Everything but the argument checks needs the GPU (there is no CPU path)."""
@@ -32,12 +34,13 @@ from espm_amd._image_args import check_image, check_layout, check_log_shift, ima
 MAX_K = 8            # ESPM_PML_MAX_K: components of the model
 MAX_PASS = 20000     # the default cap of the passes of a pixel
 CHUNK = 64           # passes per launch
-METHODS = ("em", "newton")   # espm_pixel_ml, espm_pixel_ml_newton
+METHODS = ("em", "newton")   # espm_pixel_ml, espm_pixel_ml_newton: the two rules of the SAME problem, h >= 0 with a free scale
+ALL_METHODS = METHODS + ("simplex",)   # ... and espm_pixel_ml_simplex: another problem, the fit under sum h = 1
 
 
 def _check_method(method):
-    if method not in METHODS:
-        raise ValueError(f"method must be one of {METHODS}, not {method!r}")
+    if method not in ALL_METHODS:
+        raise ValueError(f"method must be one of {ALL_METHODS}, not {method!r}")
     return method
 
 
@@ -67,6 +70,7 @@ class _Solver:
     def __init__(self, X, D, tol, max_pass, chunk, log_shift, layout, who, method="em"):
         check_layout(layout)
         self.method = _check_method(method)
+        self.simplex = method == "simplex"   # the flag ``run`` and ``run_pinned`` go by: espm_pixel_ml_simplex, sum_M h = 1 - h_pin
         X = check_image(X)
         D = np.ascontiguousarray(D, dtype=np.float64)
         if D.ndim != 2 or D.size == 0:
@@ -119,7 +123,8 @@ class _Solver:
 
     def run(self, start, comp, mask):
         """One fit over the component set: dict of DEVICE tensors H (k, p), deviance, gap (p,), n_pass (p,) int32, done (p,) uint8 and the
-        ints unmodelled, nonfinite.  ``start``: a device (k, p) float64 tensor (consumed), a checked host array, or None: N / sum_M s."""
+        ints unmodelled, nonfinite.  ``start``: a device (k, p) float64 tensor (consumed), a checked host array, or None: N / sum_M s
+        (under the simplex: 1 / |M|)."""
         import ctypes as C
 
         import torch
@@ -131,7 +136,7 @@ class _Solver:
         with self.image.scope():
             if start is None:
                 Hd = torch.zeros((k, p), dtype=torch.float64, device=self.dev)
-                Hd[comp] = (self.counts() / float(self.s[comp].sum()))[None, :]
+                Hd[comp] = 1.0 / len(comp) if self.simplex else (self.counts() / float(self.s[comp].sum()))[None, :]
             elif isinstance(start, torch.Tensor):
                 Hd = start.contiguous()
             else:
@@ -143,9 +148,12 @@ class _Solver:
             s_ptr = self.s.ctypes.data_as(C.c_void_p)
             args = (*self.image.abi(), _ptr(self.Dd), s_ptr, k, mask, self.log_shift, self.tol)
             state = (_ptr(Hd), _ptr(dv), _ptr(gp), _ptr(passes), _ptr(done), _ptr(counters))
-            if self.method == "newton":   # the rule's own scratch (e, dev_acc, tau, trial per pixel): the kernel initialises it
+            if self.method != "em":   # the rule's own scratch (e, dev_acc, tau, trial per pixel): the kernel initialises it
                 extra = torch.empty((k + _lib.PMLN_STATE_EXTRA, p), dtype=torch.float64, device=self.dev)
                 entry, state = _lib.lib.espm_pixel_ml_newton, state + (_ptr(extra), extra.numel() * extra.element_size())
+                if self.simplex:   # nothing pinned: pin = -1, and neither t nor slope
+                    entry = _lib.lib.espm_pixel_ml_simplex
+                    args, state = (*args[:-2], -1, None, *args[-2:]), (*state[:3], None, *state[3:])
             else:
                 entry = _lib.lib.espm_pixel_ml
             issued = 0
@@ -176,7 +184,8 @@ class _Solver:
         return pin, comp, mask
 
     def run_pinned(self, start, comp, mask, pin, t, done=None, searching=None):
-        """One fit over the component set with component ``pin`` held at ``t`` (espm_pixel_ml_pinned), on the resident image: ``run``'s
+        """One fit over the component set with component ``pin`` held at ``t`` (espm_pixel_ml_pinned; under the simplex
+        espm_pixel_ml_simplex, where the set sums to 1 - t and a start of None is 1 / |M|), on the resident image: ``run``'s
         dict plus ``slope`` (p,) and ``searching``.  ``t``: a device (p,) float64 tensor.  ``start`` as for ``run``; a device tensor is
         updated IN PLACE (the next evaluation's warm start).  ``done``: None, or a device (p,) uint8 tensor (consumed) - a pixel
         with done != 0 is not touched, and its deviance, gap, slope and n_pass read 0.  ``searching``: None, or a device integer the
@@ -194,7 +203,7 @@ class _Solver:
             if start is None:
                 Hd = torch.zeros((k, p), dtype=torch.float64, device=self.dev)
                 if comp:
-                    Hd[comp] = (self.counts() / float(self.s[comp].sum()))[None, :]
+                    Hd[comp] = 1.0 / len(comp) if self.simplex else (self.counts() / float(self.s[comp].sum()))[None, :]
             elif isinstance(start, torch.Tensor):
                 Hd = start
                 assert Hd.is_contiguous()
@@ -211,10 +220,11 @@ class _Solver:
             args = (*self.image.abi(), _ptr(self.Dd), s_ptr, k, mask, pin, _ptr(t), self.log_shift, self.tol)
             state = (_ptr(Hd), _ptr(dv), _ptr(gp), _ptr(sl), _ptr(passes), _ptr(done), _ptr(counters), _ptr(extra),
                      extra.numel() * extra.element_size())
+            entry = _lib.lib.espm_pixel_ml_simplex if self.simplex else _lib.lib.espm_pixel_ml_pinned
             issued = 0
             while issued < self.max_pass:
                 step = min(self.chunk, self.max_pass - issued)
-                _lib.check(_lib.lib.espm_pixel_ml_pinned(*args, step, *state, _stream()))
+                _lib.check(entry(*args, step, *state, _stream()))
                 issued += step
                 cnt = counters.cpu().numpy()   # the one read-back between the chunks
                 if cnt[_lib.PML_NOT_DONE] == 0:
@@ -253,7 +263,14 @@ def ml_unmix(X, D, H0=None, components=None, tol=1e-3, max_pass=MAX_PASS, chunk=
     (NotImplementedError beyond), finite, not negative; a component of the set needs a spectrum that is not all zero.  ``H0`` (k, p): the start; an entry of the set that is not > 0 is
     replaced by N / (|set| s_j) * 1e-3; None: N / sum_set s.  ``chunk``: the passes per launch (the results do not depend on it).
     ValueError for shapes that do not match, ``tol`` or ``log_shift`` not positive, X, D or H0 not finite and a ``method`` that does
-    not exist - before anything is uploaded."""
+    not exist - before anything is uploaded.
+
+    ``method="simplex"``: the CONSTRAINED ML of a ``simplex_H`` model - abundances are phase fractions, sum_set h = 1 in every pixel,
+    and the spectra carry the intensity - by the rule of include/espm_mu.h, "pixel ML, simplex" (the Newton step with the multiplier
+    of the sum, an EM successor with a per-pixel root).  The same dict: the columns of ``H`` sum to 1 over the set (to within k ulps)
+    and are NOT scaled onto sum_j s_j h_j = N; ``gap`` is the Frank-Wolfe certificate 2 (sum_j g_j h_j - min_j g_j), g = s - D^T (x / y):
+    ``deviance`` is above its minimum over the simplex by at most that.  A pixel without a count puts h = 1 on the component of the
+    least s_j.  ``H0``: lifted to at least 1e-3 / |set| and scaled to sum 1; None: 1 / |set|."""
     sv = _Solver(X, D, tol, max_pass, chunk, log_shift, layout, "ml_unmix", method)
     start = sv.check_start(H0)
     comp, mask = sv.check_components(components)
@@ -299,11 +316,18 @@ def presence(X, D, H0=None, tol=1e-3, max_pass=MAX_PASS, chunk=CHUNK, log_shift=
     * ``unmodelled``, ``nonfinite``: of the full fit).
 
     With one component the reduced model is empty: its deviance is the floor rule's, y = log_shift in every channel, formed on the
-    host without a launch.  Arguments and refusals as for ``ml_unmix``; every component needs a spectrum that is not all zero."""
+    host without a launch.  Arguments and refusals as for ``ml_unmix``; every component needs a spectrum that is not all zero.
+
+    ``method="simplex"``: the test a ``simplex_H`` fit calls for - the full fit under sum h = 1 against the fit over the other
+    components, which sum to 1 again (each started at the full solution with row j zeroed and rescaled): no free scale per pixel on
+    either side.  ``lr`` is exactly 0 wherever the full fit has h_j = 0 (there the full solution is a point of the reduced problem).
+    One component: ValueError, nothing is fitted under the simplex."""
     sv = _Solver(X, D, tol, max_pass, chunk, log_shift, layout, "presence", method)
     start = sv.check_start(H0)
     comp, mask = sv.check_components(None)
     k, p = sv.k, sv.p
+    if sv.simplex and k == 1:
+        raise ValueError("presence: one component under the simplex (h = 1 in every pixel: nothing is fitted, nothing to test)")
     held = sv.image.host if k == 1 else None
     full = sv.run(start, comp, mask)
     without = np.empty((k, p))
@@ -320,13 +344,15 @@ def presence(X, D, H0=None, tol=1e-3, max_pass=MAX_PASS, chunk=CHUNK, log_shift=
         without[j] = red["deviance"]
         rows.append(red)
     lr = np.maximum(without - rows[0]["deviance"][None, :], 0.0)
+    if sv.simplex:   # h_j == 0 in the full fit: its point is a point of the reduced problem, whose minimum is therefore not above it
+        lr = np.where(rows[0]["H"] == 0, 0.0, lr)   # (the rule's start lifts such zeros: the reduced fit may certify within tol above)
     return dict(H_ml=rows[0]["H"], deviance_ml=rows[0]["deviance"], lr=lr, pvalue=pvalue(lr),
                 converged=np.stack([r["converged"] for r in rows]), gap=np.stack([r["gap"] for r in rows]),
                 n_pass=np.stack([r["n_pass"] for r in rows]), unmodelled=rows[0]["unmodelled"], nonfinite=rows[0]["nonfinite"])
 
 
 # ---- how much of phase j could be in this pixel: profile-likelihood intervals of the abundances ----------------------------------------
-def _check_pinned_value(t, p, who):
+def _check_pinned_value(t, p, who, simplex=False):
     t = np.asarray(t, dtype=np.float64)
     if t.ndim == 0:
         t = np.full(p, float(t))
@@ -334,10 +360,13 @@ def _check_pinned_value(t, p, who):
         raise ValueError(f"{who}: t must be a scalar or of shape ({p},), not {t.shape}")
     if not np.isfinite(t).all() or (t < 0).any():
         raise ValueError(f"{who}: t must be finite and not negative")
+    if simplex and (t > 1).any():
+        raise ValueError(f"{who}: t must not exceed 1 under the simplex (the others sum to 1 - t)")
     return np.ascontiguousarray(t)
 
 
-def ml_unmix_pinned(X, D, pin, t, H0=None, components=None, tol=1e-3, max_pass=MAX_PASS, chunk=CHUNK, log_shift=1e-14, layout="cm"):
+def ml_unmix_pinned(X, D, pin, t, H0=None, components=None, tol=1e-3, max_pass=MAX_PASS, chunk=CHUNK, log_shift=1e-14, layout="cm",
+                    simplex=False):
     """``ml_unmix`` with the abundance of component ``pin`` HELD at ``t`` (a scalar, or (p,): a value per pixel) while the components
     of ``components`` (None: all but ``pin``; may be empty) are fitted: one point of the profile likelihood of h_pin, by the rule of
     include/espm_mu.h, "pixel ML, pinned" (the Newton step of ``method="newton"`` without its scale onto the ray, which a pinned term
@@ -346,11 +375,15 @@ def ml_unmix_pinned(X, D, pin, t, H0=None, components=None, tol=1e-3, max_pass=M
     (exact at the inner optimum, approximate at a certified point).  ``gap`` is this rule's own certificate,
     2 sum_M (s_j - q_j) h_j + 2 N max(max_M q_j / s_j - 1, 0): ``deviance`` is above its minimum over the set, at this t, by at most that.
     Arguments and refusals as for ``ml_unmix``; ValueError also for a ``pin`` that is no component or is in ``components``, a pinned
-    spectrum that is all zero and a ``t`` that is negative, not finite or of another shape - all before anything is uploaded."""
-    sv = _Solver(X, D, tol, max_pass, chunk, log_shift, layout, "ml_unmix_pinned", "newton")
+    spectrum that is all zero and a ``t`` that is negative, not finite or of another shape - all before anything is uploaded.
+
+    ``simplex=True``: the same point of the profile under sum h = 1 (include/espm_mu.h, "pixel ML, simplex": espm_pixel_ml_simplex) -
+    the fitted abundances sum to 1 - t, ``gap`` is the Frank-Wolfe certificate 2 (sum_M g_j h_j - (1 - t) min_M g_j), g = s - q, and
+    ``slope`` = 2 (g_pin - sum_M g_j h_j / (1 - t)) carries the multiplier of the sum.  A ``t`` above 1 is a ValueError too."""
+    sv = _Solver(X, D, tol, max_pass, chunk, log_shift, layout, "ml_unmix_pinned", "simplex" if simplex else "newton")
     start = sv.check_start(H0)
     pin, comp, mask = sv.check_pin(pin, components)
-    t = _check_pinned_value(t, sv.p, sv.who)
+    t = _check_pinned_value(t, sv.p, sv.who, sv.simplex)
     sv.upload()
     td, = sv.image.model(t)
     r = sv.run_pinned(start, comp, mask, pin, td)
@@ -366,7 +399,7 @@ def threshold(level):
 
 
 def intervals(X, D, H0=None, level=0.95, components=None, tol=1e-3, lr_tol=1e-2, max_eval=64, max_pass=MAX_PASS, chunk=CHUNK,
-              log_shift=1e-14, layout="cm"):
+              log_shift=1e-14, layout="cm", simplex=False):
     """How much of component j could be in pixel q?  The PROFILE-LIKELIHOOD interval of every abundance: the values t whose best fit
     with h_j held at t (``ml_unmix_pinned``) lies within the chi2_1 quantile ``threshold`` = 2 erfinv(level)^2 of the pixel's best fit
     (``ml_unmix(method="newton")``).  Where the abundance sits at the boundary the interval starts at 0 and its upper end is an UPPER
@@ -395,13 +428,21 @@ def intervals(X, D, H0=None, level=0.95, components=None, tol=1e-3, lr_tol=1e-2,
     What the interval is NOT: it holds the spectra D fixed, imposes no regulariser and no simplex, and is asymptotic (``sampling``
     draws the replicates a calibration of its coverage needs).  ``components``: the rows to compute (None: all); the fits are always
     over all k components, each of which needs a spectrum that is not all zero.  Other arguments and refusals as for ``ml_unmix``;
-    ValueError also for ``level`` outside (0, 1), ``lr_tol`` not positive and ``max_eval`` below 1 - before anything is uploaded."""
+    ValueError also for ``level`` outside (0, 1), ``lr_tol`` not positive and ``max_eval`` below 1 - before anything is uploaded.
+
+    ``simplex=True``: the interval of a phase FRACTION, for spectra of a ``simplex_H`` fit (they carry the intensity): the full fit is
+    ``ml_unmix(method="simplex")``, every evaluation a pinned fit under sum h = 1 (``ml_unmix_pinned(simplex=True)``), and the same
+    root finder runs with its bracket capped at 1 - every candidate t is min(t, 1), a point at t = 1 that is still inside the level
+    finishes with ``upper`` EXACTLY 1, and ``H_ml`` = 1 gives ``upper`` = 1 without an evaluation - so that
+    0 <= lower <= H_ml <= upper <= 1.  The warm starts are lifted to 1e-3 (1 - t) / (k - 1) and rescaled onto 1 - t by the rule's own
+    start.  A pixel without a count has no closed form here: its profile is linear in t and one Newton step lands on the end (or the
+    cap).  Still fixed spectra, no regulariser, asymptotic, one component at a time."""
     import torch
     q = threshold(level)
     if not lr_tol > 0:
         raise ValueError("lr_tol must be positive")
     max_eval = _positive_int(max_eval, "max_eval")
-    sv = _Solver(X, D, tol, max_pass, chunk, log_shift, layout, "intervals", "newton")
+    sv = _Solver(X, D, tol, max_pass, chunk, log_shift, layout, "intervals", "simplex" if simplex else "newton")
     start = sv.check_start(H0)
     every, mask = sv.check_components(None)
     k, p = sv.k, sv.p
@@ -415,7 +456,7 @@ def intervals(X, D, H0=None, level=0.95, components=None, tol=1e-3, lr_tol=1e-2,
         conv = torch.zeros((k, 2, p), dtype=torch.bool, device=dev)
         n_eval, n_pass = (torch.zeros((k, 2, p), dtype=torch.int64, device=dev) for _ in range(2))
         # what a warm start is lifted to: the kernel's own fill N / (|M| s_i) * 1e-3 of a start that is not positive
-        lift = None if k == 1 else (sv.counts()[None, :] / ((k - 1) * torch.from_numpy(sv.s).to(dev))[:, None]) * 1e-3
+        lift = None if k == 1 or sv.simplex else (sv.counts()[None, :] / ((k - 1) * torch.from_numpy(sv.s).to(dev))[:, None]) * 1e-3
         for j in rows:
             rest = [i for i in every if i != j]
             rmask = mask & ~(1 << j)
@@ -427,6 +468,12 @@ def intervals(X, D, H0=None, level=0.95, components=None, tol=1e-3, lr_tol=1e-2,
                 active = ok.clone()
                 if up:
                     lo, hi, t = h_ml.clone(), torch.full_like(h_ml, float("inf")), h_ml + w0
+                    if sv.simplex:   # the cap: no fraction above 1; a pixel that is all j has its upper end there
+                        t = torch.clamp(t, max=1.0)
+                        one = active & (h_ml >= 1)
+                        out = torch.where(one, torch.ones_like(out), out)
+                        conv[j, side] |= one
+                        active &= ~one
                 else:
                     lo, hi, t = torch.zeros_like(h_ml), h_ml.clone(), torch.zeros_like(h_ml)
                     zero = active & (h_ml == 0)
@@ -435,7 +482,8 @@ def intervals(X, D, H0=None, level=0.95, components=None, tol=1e-3, lr_tol=1e-2,
                     active &= ~zero
                 Hc = H_ml.clone()
                 for ev in range(max_eval):
-                    if rest:   # (an abundance the evaluation before drove to 1e-13 may have to come back: from there it grows slowly)
+                    if rest and lift is not None:   # (an abundance the evaluation before drove to 1e-13 may have to come back: from
+                        # there it grows slowly; under the simplex the rule's own start lifts and rescales)
                         Hc[rest] = torch.maximum(Hc[rest], lift[rest])
                     r = sv.run_pinned(Hc, rest, rmask, j, t.contiguous(), done=(~active).to(torch.uint8), searching=active.sum())
                     if r["searching"] == 0:   # (that launch found every pixel retired: its workgroups returned at once)
@@ -445,6 +493,8 @@ def intervals(X, D, H0=None, level=0.95, components=None, tol=1e-3, lr_tol=1e-2,
                     fin = fitted & (phi.abs() <= lr_tol)
                     if not up and ev == 0:
                         fin |= fitted & (phi <= 0)   # the boundary: the interval reaches 0
+                    if up and sv.simplex:
+                        fin |= fitted & (t == 1) & (phi <= 0)   # the cap: the interval reaches 1
                     out = torch.where(fin, t, out)
                     conv[j, side] |= fin
                     n_eval[j, side] += active
@@ -460,6 +510,8 @@ def intervals(X, D, H0=None, level=0.95, components=None, tol=1e-3, lr_tol=1e-2,
                     nxt = torch.where(good, tn, mid)
                     if not up and ev == 0:   # (the slope at t = 0 belongs to the floor where nothing else is fitted)
                         nxt = torch.maximum(h_ml - w0, 0.5 * h_ml)
+                    if up and sv.simplex:
+                        nxt = torch.clamp(nxt, max=1.0)
                     t = torch.where(go, nxt, t)
                     active = go
                 (upper if up else lower)[j] = out

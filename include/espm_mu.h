@@ -68,7 +68,10 @@
  *   espm_pixel_ml_pinned  <- (new) the same problem with one abundance held at a per-pixel value while the others are fitted, a
  *                            certificate of its own and the slope of the profile deviance: the evaluation behind profile-likelihood
  *                            intervals of the abundances (upper limits at the boundary); no reference analogue
- *   espm_lu_pl          <- espm/estimators/updates.py:179 -> scikit-learn's _initialize_nmf -> _randomized_range_finder: the LU
+ *   espm_pixel_ml_simplex <- (new) the same problem under sum h = 1, the pixel model of a simplex_H fit, with or without a pinned
+ *                            abundance: a Frank-Wolfe certificate, the equality multiplier in the Newton step and in the EM
+ *                            successor; presence tests and intervals of phase FRACTIONS; no reference analogue
+ *   espm_lu_pl         <- espm/estimators/updates.py:179 -> scikit-learn's _initialize_nmf -> _randomized_range_finder: the LU
  *                            normaliser of its power iterations (scipy.linalg.lu(A, permute_l=True)[0]) on tall device matrices
  *
  * Conventions
@@ -1179,6 +1182,64 @@ int espm_pixel_ml_pinned(const void* x, int x_dtype, int x_layout, int64_t ld, i
                          uint32_t mask, int pin, const double* t, double log_shift, double tol, int n_pass, double* h_inout, double* dev,
                          double* gap, double* slope, int32_t* passes, uint8_t* done, uint64_t* counters, void* state, size_t state_bytes,
                          espm_stream_t stream);
+
+/* ---- pixel ML, simplex (csrc/mu_pixel_ml_simplex.hip; espm_amd.presence with method="simplex" / simplex=True; NMFEstimator.presence_maps,
+ *      abundance_intervals on a simplex_H fit) ----
+ * The pixel problem of a simplex_H fit: the pixel's best Poisson fit over the component set M with the fitted abundances held to
+ * sum_M h = total - total = 1 where nothing is pinned (pin = -1), total = 1 - t[q] with component `pin` (not in M) held at t[q] in
+ * [0, 1].  Abundances are phase FRACTIONS here and the spectra carry the intensity: there is no free scale per pixel.  Arguments, state
+ * (ESPM_PMLN_STATE_BYTES(k, p), initialised by the kernel for a pixel that enters with passes == 0), counters and outputs as for
+ * espm_pixel_ml_pinned; pin = -1 means no pinned component, and then t and slope may be null (slope is not written).  mask may be
+ * empty only with a pinned component.
+ * THE RULE, all in fp64, for the pixel with the counts x; s_j the column sums of d, m = |M|:
+ *   t[q] negative, above 1 or not finite (pin >= 0): the pixel stops at once with done = 2, adds to counters[ESPM_PML_NONFINITE], and
+ *     h, dev, gap, slope and passes stay as the call found them (dev, gap, slope 0 where passes == 0).
+ *   total = 1 - t[q] (1 with pin = -1).
+ *   start (passes == 0 on entry): for j in M ascending h_j = max(h_j, 1e-3 total / m), sum = sum + h_j; then h_j = h_j (total / sum);
+ *     with m == 1 or total == 0, h_j = total exactly.  e = 0, dev_acc = +inf, tau = 1e-2, trial = 0.
+ *   at EVERY entry: h_pin = t[q] (never updated by a step); h_j = 0 for j outside M and not pin.
+ *   one pass:
+ *     (no scale onto the ray: the sum is constrained, nothing is free to scale)
+ *     2  the walk of espm_pixel_ml_pinned's step 2: y over all k components, the floor, w, dev, q_j for every j, the triangle A
+ *     3  for j in M ascending, g_j = s_j - q_j: lin = fma(g_j, h_j, lin), hq = fma(h_j, q_j, hq) from 0; gmin = min(gmin, g_j) from +inf
+ *     4  gap = 2 (lin - total gmin), the product rounded on its own (no fma: exactly 0 at a vertex and with m == 1); 0 with M empty.
+ *        slope = 2 (g_pin - lin / total); 2 (g_pin - gmin) where total == 0; 2 g_pin with M empty.
+ *        THE CERTIFICATE (a Frank-Wolfe gap): the deviance f is convex in h_M with the gradient 2 g, so for the minimiser h* over
+ *        {h_M >= 0, sum_M h = total}: f(h) - f(h*) <= grad . (h - h*) = 2 lin - 2 sum_M g_i h*_i <= 2 lin - 2 total gmin, a linear
+ *        function over the scaled simplex being least at a vertex.  No bound on N enters it.  It is a property of the point and holds
+ *        wherever no entry with counts is floored, as the certificates of the other rules.
+ *        THE SLOPE: d/dt min f = df/dh_pin + nu d(total)/dt with nu the multiplier of the sum constraint, and at the inner optimum
+ *        2 g_i = -nu wherever h_i > 0, so nu = -2 lin / total (envelope theorem); approximate at a point that is certified and not optimal.
+ *     5  dev or gap not finite: done = 2, h as it stands, dev, gap and slope as computed, counters[ESPM_PML_NONFINITE].
+ *        REJECT, if trial and not dev <= dev_acc: h_M = e, trial = 0, tau = min(10 tau, 1); the pass is counted.
+ *        ACCEPT, otherwise: dev, gap and slope are reported.  gap <= tol: DONE (done = 1; the floored entries with counts add to
+ *        counters[ESPM_PML_UNMODELLED]).  Else, if hq == 0 (no count that M models - an empty pixel, or counts only where no
+ *        component of M reaches: f is linear in h_M with the gradient 2 s): h = total at the j in M of the least s_j (lowest index on
+ *        ties), 0 on the rest of M; e = h, dev_acc = dev, trial = 0; the pass is counted, and the next one certifies with gap = 0.
+ *        Else, in this order: if trial, tau = max(tau / 10, 1e-8);
+ *        THE EM SUCCESSOR e (the multiplicative H step under the simplex, regularisers off: monotone): n_j = (h_j q_j) (1 / total), j in M;
+ *        over P = {n_j > 0}: nu = max_P (n_j - s_j); at most 64 times: i_j = 1 / (s_j + nu), c_j = n_j i_j, psi = sum c_j,
+ *        dps = fma(c_j, i_j, dps), next = nu + (psi - 1) / dps, stop unless next > nu, nu = next (psi is convex and decreasing and
+ *        psi(nu_0) >= 1: the iteration rises monotonically to the root); e_j = total (n_j (1 / (s_j + nu))), 0 on the rest of M,
+ *        se = sum e_j, e_j = e_j (total / se);
+ *        THE TRIAL: over the active set {j in M, h_j > 0} (an abundance at exactly 0 stays there, as under EM) B = A with
+ *        B_jj = fma(tau, max(q_j, s_j) / h_j, A_jj) - the EM surrogate's curvature is q_j / h_j; the max keeps B definite where a
+ *        component sees no counts -, every other component a row of the identity; ONE root-free Cholesky B = L diag(p) L^T and two
+ *        solves, u = B^-1 (-g), v = B^-1 1 (both 0 off the active set; the middle step multiplies by 1 / p_j); mult = sum u / sum v; delta_j = fma(-mult, v_j, u_j) - the
+ *        Newton step of the blended model with the sum held; trial_j = max(h_j + delta_j, 0.01 h_j), sc = sum trial_j,
+ *        h_j = trial_j (total / sc); trial = 1, dev_acc = dev.  A pivot that is not positive or not finite, or an h_j that is not
+ *        finite: h_M = e, trial = 0 instead.  The pass is counted.
+ *   sum_M h_j = total to within m ulps of total after every step (one rounding in each of the m products, m - 1 in the sum behind the
+ *   scale); h_pin = t[q] bit for bit; rows outside M and pin exactly 0.
+ * RESUMABLE, THE CALLER'S done HONOURED, counters, geometry, independence of neighbours, layout, dtype and slabs as for
+ * espm_pixel_ml_pinned.  No float atomics.
+ * ESPM_EINVAL, before the device is touched: espm_pixel_ml_pinned's refusals with pin = -1 allowed, and an empty mask with pin = -1,
+ * pin < -1, a null t or slope with pin >= 0.  ESPM_EUNSUPPORTED for k outside 1..ESPM_PML_MAX_K.  Only the narrow build has the kernels;
+ * the wide builds return ESPM_EUNSUPPORTED.  No espm_mu_state is involved: ESPM_MU_ABI_VERSION stays. */
+int espm_pixel_ml_simplex(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, const double* d, const double* s, int k,
+                          uint32_t mask, int pin, const double* t, double log_shift, double tol, int n_pass, double* h_inout, double* dev,
+                          double* gap, double* slope, int32_t* passes, uint8_t* done, uint64_t* counters, void* state, size_t state_bytes,
+                          espm_stream_t stream);
 
 /* ---- spectra ML pass (csrc/mu_spectra_ml.hip; espm_amd.spectra_ml, NMFEstimator.element_presence) ----
  * What one pass of the maximum-likelihood fit of W given H needs from the image (the rule itself is small dense algebra above this

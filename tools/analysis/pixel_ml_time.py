@@ -5,12 +5,17 @@ yardstick: an EM pass does strictly less arithmetic per entry (2 k FMAs, one div
 k (k + 1) / 2 FMAs), a Newton pass the two together.
 
     python tools/analysis/pixel_ml_time.py [--size n,nx,ny] [--k 5] [--counts 500] [--runs 3] [--max-pass 20000] [--method em|newton|both]
-                                           [--no-presence] [--pinned] [--out FILE]
+                                           [--no-presence] [--pinned] [--simplex] [--out FILE]
 
 ``--pinned``: also espm_pixel_ml_pinned (csrc/mu_pixel_ml_pinned.hip) - the time of one pinned pass against one Newton pass, the two
 INTERLEAVED in one process (Newton with 1 pass, pinned with 1, Newton with 3, pinned with 3, and again: the same walk plus one
 output, so the two should agree), the last component held at 1.5 times its start; and ``presence.intervals`` end to end with its
 evaluation and pass counts per percentile of the pixels.
+
+``--simplex``: also espm_pixel_ml_simplex (csrc/mu_pixel_ml_simplex.hip) on the same image with the spectra brought to the data's
+dose (D times mean N / mean s: the simplex model has no scale per pixel) - the time of one simplex pass, with the last component
+pinned at 0.3 and with nothing pinned, against one pinned pass, the three INTERLEAVED in one process as above (the same walk; the
+additions are between the walks); then ``presence.presence(method="simplex")`` and ``presence.intervals(simplex=True)`` end to end.
 
 X is device-resident (synthetic Poisson counts drawn on the device from ``pixel_diagnostics_time.model``).  The time per pass is the
 difference of two calls from the same fresh state, with 4 and with 12 passes (EM) or with 1 and with 3 (Newton, whose pixels stop
@@ -57,6 +62,19 @@ def pinned_call(X, D, s, H, state, t, slope, n_pass, tol):
                                              _ptr(slope), _ptr(passes), _ptr(done), _ptr(counters), _ptr(extra), extra.numel() * 8, _stream()))
 
 
+def simplex_call(X, D, s, H, state, t, slope, n_pass, tol):
+    """espm_pixel_ml_simplex with the last component pinned at ``t``, or with nothing pinned (``t`` None)."""
+    dv, gp, passes, done, counters = state
+    n, p = X.shape
+    k = D.shape[1]
+    extra = torch.empty((k + _lib.PMLN_STATE_EXTRA, p), dtype=torch.float64, device="cuda")
+    mask, pin = ((1 << k) - 1, -1) if t is None else ((1 << (k - 1)) - 1, k - 1)
+    _lib.check(_lib.lib.espm_pixel_ml_simplex(_ptr(X), pdt.CODES[X.dtype], _lib.LAYOUT_CM, int(X.stride(0)), n, p, _ptr(D), s.ctypes.data, k,
+                                              mask, pin, None if t is None else _ptr(t), float(log_shift), tol, n_pass, _ptr(H), _ptr(dv),
+                                              _ptr(gp), None if t is None else _ptr(slope), _ptr(passes), _ptr(done), _ptr(counters),
+                                              _ptr(extra), extra.numel() * 8, _stream()))
+
+
 def event_ms(fn):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -82,6 +100,7 @@ def main():
     ap.add_argument("--method", choices=("em", "newton", "both"), default="em")
     ap.add_argument("--no-presence", action="store_true")
     ap.add_argument("--pinned", action="store_true")
+    ap.add_argument("--simplex", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     require_gpu()
@@ -186,6 +205,68 @@ def main():
             f"passes: {qp[0]:.0f} / {qp[1]:.0f} / {qp[2]:.0f}; per end at most {res['n_eval'].max()} fits and {res['n_pass'].max()} passes")
         say(f"  intervals: lower end at 0 in {np.mean(res['lower'] == 0):.4f} of the entries; median width per component "
             f"{np.nanmedian(res['upper'] - res['lower'], axis=1)}")
+    if args.simplex and k >= 2:
+        Ds = (D * float(X.sum(dim=0, dtype=torch.float64).mean() / s.mean())).contiguous()
+        ss = np.ascontiguousarray(Ds.sum(dim=0).cpu().numpy())
+        Hs = torch.full((k, p), 1.0 / k, dtype=torch.float64, device="cuda")
+        tp, ts = (1.5 * H0[k - 1]).contiguous(), torch.full((p,), 0.3, dtype=torch.float64, device="cuda")
+        slope = torch.zeros(p, dtype=torch.float64, device="cuda")
+        left = {}
+
+        def make(name, n_pass):
+            def fn():
+                H, state = fresh(p, k, H0 if name == "pinned" else Hs)
+                if name == "pinned":
+                    pinned_call(X, D, s, H, state, tp, slope, n_pass, tol)
+                else:
+                    simplex_call(X, Ds, ss, H, state, ts if name == "simplex, pinned" else None, slope, n_pass, tol)
+                left[name, n_pass] = state[4]
+            return fn
+
+        names = ("pinned", "simplex, pinned", "simplex")
+        order = [(name, make(name, n_pass), n_pass) for n_pass in (1, 3) for name in names]
+        for _, fn, _ in order:   # warm-up
+            fn()
+        torch.cuda.synchronize()
+        ms = {(name, n_pass): [] for name, _, n_pass in order}
+        for _ in range(args.runs):
+            for name, fn, n_pass in order:
+                ms[name, n_pass].append(event_ms(fn))
+        per = {}
+        for name in names:
+            for n_pass in (1, 3):
+                v = ms[name, n_pass]
+                say(f"  interleaved, {name}, {n_pass} passes from a fresh state: {min(v):8.3f} - {max(v):8.3f} ms, "
+                    f"{int(left[name, n_pass][_lib.PML_NOT_DONE])} of {p} pixels not done")
+            d = [(b - a) / 2 for a, b in zip(ms[name, 1], ms[name, 3])]
+            per[name] = (min(d), max(d))
+            say(f"  interleaved, {name}: time per pass: {min(d):8.3f} - {max(d):8.3f} ms")
+        for name in names[1:]:
+            say(f"  {name} / pinned, time per pass: {per[name][0] / per['pinned'][0]:.3f} (min over min)")
+        Dh = Ds.cpu().numpy()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = presence.presence(X, Dh, tol=tol, max_pass=args.max_pass, method="simplex")
+        torch.cuda.synchronize()
+        total = time.perf_counter() - t0
+        q = np.percentile(res["n_pass"][0], [50, 99, 100])
+        qr = np.percentile(res["n_pass"][1:], [50, 99, 100])
+        say(f"  simplex: presence, {k + 1} nested fits, read-backs included: {total:.2f} s; passes of the full fit, 50th / 99th / last percentile "
+            f"of the pixels: {q[0]:.0f} / {q[1]:.0f} / {q[2]:.0f}; of a reduced fit: {qr[0]:.0f} / {qr[1]:.0f} / {qr[2]:.0f}; "
+            f"{res['converged'].mean():.6f} converged; median lr per component {np.median(res['lr'], axis=1)}")
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = presence.intervals(X, Dh, tol=tol, max_pass=args.max_pass, simplex=True)
+        torch.cuda.synchronize()
+        total = time.perf_counter() - t0
+        ne, npx = res["n_eval"].sum(axis=(0, 1)), res["n_pass"].sum(axis=(0, 1))
+        qe, qp = np.percentile(ne, [50, 99, 100]), np.percentile(npx, [50, 99, 100])
+        say(f"  simplex: intervals, level 0.95, {2 * k} ends per pixel, read-backs included: {total:.2f} s; {res['converged'].mean():.6f} of the ends "
+            f"converged")
+        say(f"  simplex: intervals: pinned fits per pixel over all ends, 50th / 99th / last percentile: {qe[0]:.0f} / {qe[1]:.0f} / {qe[2]:.0f}; "
+            f"passes: {qp[0]:.0f} / {qp[1]:.0f} / {qp[2]:.0f}; per end at most {res['n_eval'].max()} fits and {res['n_pass'].max()} passes")
+        say(f"  simplex: intervals: lower end at 0 in {np.mean(res['lower'] == 0):.4f} of the entries, upper end at 1 in "
+            f"{np.mean(res['upper'] == 1):.4f}; median width per component {np.nanmedian(res['upper'] - res['lower'], axis=1)}")
 
 
 if __name__ == "__main__":
