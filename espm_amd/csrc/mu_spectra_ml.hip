@@ -16,6 +16,9 @@
 //                the chunks in ascending order.  No float atomics: two calls give the same bits.  The entries with counts under the
 //                floor are an integer count (block_count_add onto the zeroed counter).
 //
+// The batched entry point (espm_spectra_ml_pass_batch) runs the same body for B models of one image, the model index in the third grid
+// dimension, with its own slice of d, of the scratch and of the outputs; a model whose flag is 0 leaves both launches at entry.
+//
 // Only the narrow build (ESPM_KP == 8) instantiates the kernels; the wide builds export the entry points as stubs.
 #include <type_traits>
 
@@ -84,10 +87,11 @@ struct Acc {
   }
 };
 
+// the pass of ONE model at d, its partial sums to part and its count onto *unmodelled: the whole body of both kernels below
 template <int K, typename XT, bool PM>
-__global__ __launch_bounds__(CB) void pass_kernel(const XT* __restrict__ x, int64_t ld, int n, int p, const double* __restrict__ d,
-                                                  const double* __restrict__ h, double log_shift, double* __restrict__ part,
-                                                  unsigned long long* __restrict__ unmodelled) {
+__device__ __forceinline__ void pass_body(const XT* __restrict__ x, int64_t ld, int n, int p, const double* __restrict__ d,
+                                          const double* __restrict__ h, double log_shift, double* __restrict__ part,
+                                          unsigned long long* __restrict__ unmodelled) {
   constexpr int PT = PM ? PM_TILE : Tile<XT>::P;
   constexpr int NA = n_acc(K);
   constexpr int FL = K >= 7 ? 4 : 8;   // rows of pixel-major X in flight per thread
@@ -159,10 +163,28 @@ __global__ __launch_bounds__(CB) void pass_kernel(const XT* __restrict__ x, int6
   block_count_add<1, CB / 64>(cnt_part, {valid ? a.n_un : 0u}, unmodelled);   // (every thread of the workgroup is here)
 }
 
-// the chunks of every (sum, channel) added in ascending order: the one order there is, whatever the grid did
-__global__ __launch_bounds__(256) void reduce_kernel(const double* __restrict__ part, int n, int k, int n_chunks, double* __restrict__ dev,
-                                                     double* __restrict__ xsum, double* __restrict__ ysum, double* __restrict__ q,
-                                                     double* __restrict__ a_tri) {
+template <int K, typename XT, bool PM>
+__global__ __launch_bounds__(CB) void pass_kernel(const XT* __restrict__ x, int64_t ld, int n, int p, const double* __restrict__ d,
+                                                  const double* __restrict__ h, double log_shift, double* __restrict__ part,
+                                                  unsigned long long* __restrict__ unmodelled) {
+  pass_body<K, XT, PM>(x, ld, n, p, d, h, log_shift, part, unmodelled);
+}
+
+// model blockIdx.z of a batch: d (B, n, K), part (B, chunks, sums, n), unmodelled (B,).  A retired model's workgroups leave at entry
+// (the flag is the same for the whole workgroup: nobody waits at a barrier), before anything of X, d or h is read.
+template <int K, typename XT, bool PM>
+__global__ __launch_bounds__(CB) void pass_batch_kernel(const XT* __restrict__ x, int64_t ld, int n, int p, const double* __restrict__ d,
+                                                        const double* __restrict__ h, const uint8_t* __restrict__ active, double log_shift,
+                                                        double* __restrict__ part, unsigned long long* __restrict__ unmodelled) {
+  const size_t b = blockIdx.z;
+  if (active && !active[b]) return;
+  pass_body<K, XT, PM>(x, ld, n, p, d + b * (size_t)n * K, h, log_shift, part + b * (size_t)gridDim.x * n_acc(K) * n, unmodelled + b);
+}
+
+// the chunks of every (sum, channel) added in ascending order: the one order there is, whatever the grid did (xsum null: not wanted)
+__device__ __forceinline__ void reduce_body(const double* __restrict__ part, int n, int k, int n_chunks, double* __restrict__ dev,
+                                            double* __restrict__ xsum, double* __restrict__ ysum, double* __restrict__ q,
+                                            double* __restrict__ a_tri) {
   const int na = n_acc(k), nt = n_tri(k);
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= (int64_t)na * n) return;
@@ -170,10 +192,33 @@ __global__ __launch_bounds__(256) void reduce_kernel(const double* __restrict__ 
   double v = 0;
   for (int u = 0; u < n_chunks; ++u) v += part[((size_t)u * na + s) * n + c];
   if (s == 0) dev[c] = 2.0 * v;
-  else if (s == 1) xsum[c] = v;
+  else if (s == 1) { if (xsum) xsum[c] = v; }
   else if (s == 2) ysum[c] = v;
   else if (s < 3 + k) q[(size_t)c * k + (s - 3)] = v;
   else a_tri[(size_t)c * nt + (s - 3 - k)] = v;
+}
+
+__global__ __launch_bounds__(256) void reduce_kernel(const double* __restrict__ part, int n, int k, int n_chunks, double* __restrict__ dev,
+                                                     double* __restrict__ xsum, double* __restrict__ ysum, double* __restrict__ q,
+                                                     double* __restrict__ a_tri) {
+  reduce_body(part, n, k, n_chunks, dev, xsum, ysum, q, a_tri);
+}
+
+// model blockIdx.y of a batch; a retired model's outputs are not written
+__global__ __launch_bounds__(256) void reduce_batch_kernel(const double* __restrict__ part, int n, int k, int n_chunks,
+                                                           const uint8_t* __restrict__ active, double* __restrict__ dev,
+                                                           double* __restrict__ ysum, double* __restrict__ q, double* __restrict__ a_tri) {
+  const size_t b = blockIdx.y;
+  if (active && !active[b]) return;
+  const size_t bn = b * (size_t)n;
+  reduce_body(part + bn * n_acc(k) * n_chunks, n, k, n_chunks, dev + bn, nullptr, ysum + bn, q + bn * k, a_tri + bn * n_tri(k));
+}
+
+// the counters of the models that run, zeroed ahead of the pass (the flags live on the device: the host cannot pick them out)
+__global__ __launch_bounds__(256) void zero_active_kernel(const uint8_t* __restrict__ active, int n_models,
+                                                          unsigned long long* __restrict__ unmodelled) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b < n_models && active[b]) unmodelled[b] = 0;
 }
 
 template <int K, typename XT>
@@ -186,6 +231,18 @@ int launch(const void* x, int x_layout, int64_t ld, int n, int p, const double* 
   else
     hipLaunchKernelGGL((pass_kernel<K, XT, false>), grid, block, 0, s, xt, ld, n, p, d, h, log_shift, part, unmodelled);
   return check_hip(hipGetLastError(), "spectra ML pass launch");
+}
+
+template <int K, typename XT>
+int launch_batch(const void* x, int x_layout, int64_t ld, int n, int p, const double* d, const double* h, int n_models,
+                 const uint8_t* active, double log_shift, double* part, unsigned long long* unmodelled, hipStream_t s) {
+  const dim3 grid((unsigned)(((int64_t)p + PC - 1) / PC), (unsigned)((n + CB - 1) / CB), (unsigned)n_models), block(CB);
+  const XT* xt = static_cast<const XT*>(x);
+  if (x_layout == ESPM_LAYOUT_PM)
+    hipLaunchKernelGGL((pass_batch_kernel<K, XT, true>), grid, block, 0, s, xt, ld, n, p, d, h, active, log_shift, part, unmodelled);
+  else
+    hipLaunchKernelGGL((pass_batch_kernel<K, XT, false>), grid, block, 0, s, xt, ld, n, p, d, h, active, log_shift, part, unmodelled);
+  return check_hip(hipGetLastError(), "spectra ML batch pass launch");
 }
 
 }  // namespace smlk
@@ -237,5 +294,54 @@ extern "C" int espm_spectra_ml_pass(const void* x, int x_dtype, int x_layout, in
   const unsigned blocks = (unsigned)(((int64_t)na * n + 255) / 256);
   hipLaunchKernelGGL(smlk::reduce_kernel, dim3(blocks), dim3(256), 0, s, part, n, k, n_chunks, dev, xsum, ysum, q, a_tri);
   return check_hip(hipGetLastError(), "spectra ML pass reduction");
+#endif
+}
+
+extern "C" size_t espm_spectra_ml_pass_batch_scratch(int n, int p, int k, int n_models) {
+  if (n_models < 1 || n_models > ESPM_SML_MAX_MODELS) return 0;
+  return (size_t)n_models * espm_spectra_ml_pass_scratch(n, p, k);
+}
+
+extern "C" int espm_spectra_ml_pass_batch(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, const double* d,
+                                          const double* h, int k, int n_models, const uint8_t* active, double log_shift, double* dev,
+                                          double* ysum, double* q, double* a_tri, int64_t* unmodelled, void* scratch, size_t scratch_bytes,
+                                          espm_stream_t stream) {
+#if ESPM_KP != 8
+  return set_error(ESPM_EUNSUPPORTED, "spectra ML batch pass: built into the 1..%d component library only", ESPM_DIAG_MAX_K);
+#else
+  if (k < 1 || k > ESPM_DIAG_MAX_K)
+    return set_error(ESPM_EUNSUPPORTED, "spectra ML batch pass: k=%d (1..%d components)", k, ESPM_DIAG_MAX_K);
+  ESPM_REQUIRE(x && d && h && dev && ysum && q && a_tri && unmodelled && scratch && n >= 1 && p >= 1, "spectra ML batch pass: bad arguments");
+  ESPM_REQUIRE(n_models >= 1 && n_models <= ESPM_SML_MAX_MODELS, "spectra ML batch pass: n_models=%d (1..%d)", n_models, ESPM_SML_MAX_MODELS);
+  if (int rc = check_image("spectra ML batch pass", x, x_dtype, ESPM_DIAG_X_F64, x_layout, ld, n, p)) return rc;
+  ESPM_REQUIRE(log_shift > 0, "spectra ML batch pass: log_shift must be positive");
+  ESPM_REQUIRE((n + ESPM_CDIAG_BLOCK - 1) / ESPM_CDIAG_BLOCK <= 65535, "spectra ML batch pass: n=%d (at most %d channels)", n,
+               65535 * ESPM_CDIAG_BLOCK);
+  const size_t need = espm_spectra_ml_pass_batch_scratch(n, p, k, n_models);
+  ESPM_REQUIRE(scratch_bytes >= need, "spectra ML batch pass: scratch of %zu bytes, %zu needed (espm_spectra_ml_pass_batch_scratch)",
+               scratch_bytes, need);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  unsigned long long* un = reinterpret_cast<unsigned long long*>(unmodelled);
+  if (active) {
+    hipLaunchKernelGGL(smlk::zero_active_kernel, dim3((unsigned)((n_models + 255) / 256)), dim3(256), 0, s, active, n_models, un);
+    if (int rc = check_hip(hipGetLastError(), "spectra ML batch pass: zeroing the counters")) return rc;
+  } else if (int rc = check_hip(hipMemsetAsync(unmodelled, 0, (size_t)n_models * sizeof(int64_t), s),
+                                "spectra ML batch pass: zeroing the counters")) {
+    return rc;
+  }
+  double* part = static_cast<double*>(scratch);
+  const int rc = dispatch_k_exact(k, [&](auto kk) {
+    return dispatch_xt<ESPM_DIAG_X_F64>(x_dtype, [&](auto xt) {
+      return smlk::launch_batch<decltype(kk)::value, typename decltype(xt)::type>(x, x_layout, ld, n, p, d, h, n_models, active, log_shift,
+                                                                                  part, un, s);
+    });
+  });
+  if (rc) return rc;
+  const int na = smlk::n_acc(k);
+  const int n_chunks = (int)(((int64_t)p + ESPM_CDIAG_PCHUNK - 1) / ESPM_CDIAG_PCHUNK);
+  const unsigned blocks = (unsigned)(((int64_t)na * n + 255) / 256);
+  hipLaunchKernelGGL(smlk::reduce_batch_kernel, dim3(blocks, (unsigned)n_models), dim3(256), 0, s, part, n, k, n_chunks, active, dev, ysum,
+                     q, a_tri);
+  return check_hip(hipGetLastError(), "spectra ML batch pass reduction");
 #endif
 }

@@ -593,6 +593,59 @@ class _FitAnalysis:
         self.W_ml_converged_, self.W_ml_gap_, self.W_ml_n_pass_ = out["converged"], out["gap"], out["n_pass"]
         return out
 
+    # ---- how much of element e could be in phase j: profile-likelihood intervals of the entries of W ----------------------------------
+    def concentration_intervals(self, level=0.95, X=None, entries=None, tol=1e-3, lr_tol=1e-2, max_eval=None, max_pass=None):
+        """How much of element e could be in phase j?  ``espm_amd.spectra_ml.intervals`` on the dictionary or physics model ``G_``
+        and the fitted abundances ``H_``, started at ``W_``: for every tested entry the PROFILE-LIKELIHOOD interval of the
+        concentration - the values t whose best fit with W_ej held at t lies within the chi2_1 quantile 2 erfinv(level)^2 of the best
+        fit.  What an analyst reports: "0.8 (0.5 - 1.2)" away from the boundary, and for a trace element, where the interval starts
+        at exactly 0, the upper limit "< 0.05 at 95 %" - where the Wald bar ``W_std_`` means nothing and ``element_presence`` says only
+        "present or not".  The interval is two-sided: a one-sided 95 % upper limit is ``W_upper_`` at ``level=0.90``.  No reference
+        analogue.
+
+        Sets, oriented as ``W_``: ``W_lower_``, ``W_upper_`` (m, k), NaN for entries that were not tested and for ends that were not
+        found; ``W_interval_level_``; ``W_interval_entries_`` (E, 2), the tested (element, component) pairs;
+        ``W_interval_converged_`` (bool) and ``W_interval_n_eval_`` (E, 2): [:, 0] the lower end, [:, 1] the upper; and ``W_ml_``
+        (m, k), ``W_deviance_ml_``, the full fit.  Returns ``spectra_ml.intervals``'s dict.  The fitted attributes are not touched.
+
+        What the interval is NOT: it holds ``H_`` fixed (the abundances' own uncertainty is not in it); it is the interval of W_ej
+        itself, not of a normalised concentration W_ej / sum_e W_ej; ``mu``, ``simplex_W`` and the floors of the fit are NOT imposed;
+        it is ASYMPTOTIC; and it runs on one GPU.  Set-up and refusals are ``element_presence``'s: entries that ``fixed_W`` imposes at
+        0 leave the free set (their ends are NaN, and they are not tested); entries imposed at a positive value, an identity G
+        (``G=None``) and more than 8 components raise NotImplementedError; m k is at most 2048; refused after ``fit_binned``.  Every
+        refusal happens before anything is uploaded.
+
+        ``level``: strictly between 0 and 1.  ``entries``: (E, 2) index pairs into ``W_`` (None: every free entry the model sees).
+        ``tol``: the certified gap of every fit; ``lr_tol``: how close to the quantile an end's deviance difference must come;
+        ``max_eval``: the cap of the pinned fits per end (None: 64); ``max_pass``: the cap of a fit's passes over the image (None:
+        ``spectra_ml.MAX_PASS_PINNED``).  ``X`` as for ``pixel_diagnostics``.  Computed in fp64 whatever the estimator's precision, on
+        the current device."""
+        from espm_amd import presence, spectra_ml
+        check_is_fitted(self, "W_")
+        presence.threshold(level)
+        k = int(self.H_.shape[0])
+        if k > spectra_ml.MAX_K:
+            raise NotImplementedError(f"concentration_intervals: {k} components (the kernel is built for 1..{spectra_ml.MAX_K})")
+        G, W, H = self._model_factors()
+        if G is None:
+            raise NotImplementedError("concentration_intervals: needs a dictionary or physics model G (with an identity G the problem "
+                                      "decouples per channel)")
+        free = None
+        if self.fixed_W is not None:
+            fixed = np.asarray(self.fixed_W)
+            if (fixed > 0).any():
+                raise NotImplementedError("concentration_intervals: fixed_W entries imposed at a positive value are not covered")
+            free = ~(fixed == 0)
+        X, layout = self._image_argument(X, "concentration_intervals")
+        out = spectra_ml.intervals(X, G, H, W0=W, free=free, entries=entries, level=level, tol=tol, lr_tol=lr_tol,
+                                   max_eval=64 if max_eval is None else max_eval,
+                                   max_pass=spectra_ml.MAX_PASS_PINNED if max_pass is None else max_pass, log_shift=self.log_shift,
+                                   layout=layout)
+        self.W_lower_, self.W_upper_, self.W_interval_level_ = out["lower"], out["upper"], out["level"]
+        self.W_interval_entries_, self.W_interval_converged_, self.W_interval_n_eval_ = out["entries"], out["converged"], out["n_eval"]
+        self.W_ml_, self.W_deviance_ml_ = out["W_ml"], out["deviance_ml"]
+        return out
+
     # ---- draws from the fitted model: a simulated image, a scale for the deviance map, the parametric bootstrap -------------------
     def _sampling_model(self, who):
         """(D, H): the fitted model ``G_ @ W_`` (n, k) and ``H_`` (k, p) in counts, in fp64, after the refusals of ``simulate``,

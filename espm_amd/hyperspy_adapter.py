@@ -226,6 +226,17 @@ def element_presence(est):
                 entries=est.W_presence_entries_, converged=est.W_ml_converged_, gap=est.W_ml_gap_, n_pass=est.W_ml_n_pass_)
 
 
+def concentration_intervals(est):
+    """What ``est.concentration_intervals()`` set, as a dict of (elements, phases) tables beside ``W_``: ``W_ml`` (the
+    maximum-likelihood concentrations given the abundances), ``lower`` and ``upper`` (the ends of every tested entry's
+    profile-likelihood interval; ``upper`` is an upper limit where ``lower`` is 0; NaN where the entry was not tested), and ``level``,
+    ``entries``, ``converged``, ``n_eval`` of the ends."""
+    if not hasattr(est, "W_upper_"):
+        raise AttributeError("call est.concentration_intervals() first: it sets W_ml_, W_lower_ and W_upper_")
+    return dict(W_ml=est.W_ml_, deviance_ml=est.W_deviance_ml_, lower=est.W_lower_, upper=est.W_upper_, level=est.W_interval_level_,
+                entries=est.W_interval_entries_, converged=est.W_interval_converged_, n_eval=est.W_interval_n_eval_)
+
+
 def abundance_interval_maps(est, shape_2d=None):
     """``est.H_lower_`` and ``est.H_upper_`` (set by ``est.abundance_intervals()``) in the navigation shape, like the loadings:
     (k, ny, nx) each - the ends of the profile-likelihood interval of every abundance; the upper map is the detection limit where

@@ -14,10 +14,17 @@ of X and whose design columns are g_e (x) h_j.  The certificate, the scale onto 
   over the pixels without float atomics) followed by small dense algebra on m k <= 2048 unknowns in torch fp64 on the device, and
   ONE small read-back (deviance, gap, the decision);
 * ``presence``: the full fit, then for every tested entry the fit without it, warm-started at the full solution; the
-  likelihood-ratio statistic ``lr`` and its p-value under the boundary mixture 1/2 chi2_0 + 1/2 chi2_1.
+  likelihood-ratio statistic ``lr`` and its p-value under the boundary mixture 1/2 chi2_0 + 1/2 chi2_1;
+* ``ml_spectra_pinned``: the best fit with ONE entry held at a value t >= 0 - a point of that entry's profile - by the pinned rule
+  (tests/spectra_ml_pinned_reference.py: no scale onto the ray, a certificate of its own, the slope of the profile);
+* ``intervals``: how much of element e could be in phase j - the profile-likelihood interval of every tested entry, an upper limit
+  where the entry sits at the boundary.  The 2 E ends (two per tested entry) are 2 E pinned problems of ONE image: they run in
+  LOCKSTEP on espm_spectra_ml_pass_batch, which serves B models in one pass launch and skips the ones that have retired, with the
+  dense algebra, the decisions and the bracketed root finder as batched, masked tensor updates and one small read-back per pass.
 
-Everything but the argument checks needs the GPU (there is no CPU path).  Out of scope: profile-likelihood intervals of entries of
-W, the simplex over W, entries held at positive values, G = None, more than 8 components or m k above 2048, more than one GPU."""
+Everything but the argument checks needs the GPU (there is no CPU path).  Out of scope: intervals of normalised concentrations
+W_ej / sum_e W_ej, the simplex over W, the uncertainty of H, ``mu`` and the floors of a fit, entries that the caller fixes at
+positive values (``fixed_W``), G = None, more than 8 components or m k above 2048, more than one GPU."""
 from __future__ import annotations
 
 import numpy as np
@@ -30,6 +37,11 @@ MAX_F = 2048       # unknowns m k of the dense information matrix (measures.spec
 MAX_PASS = 64      # the default cap of the passes of a fit
 TAU0, TAU_MIN, TAU_MAX, TAU_STEP = 1e-2, 1e-8, 1.0, 10.0
 THETA, START = 0.01, 1e-3
+H_FLOOR = 1e-30    # the pinned rule's floor of a step, H_FLOOR N / a: it has no scale onto the ray to keep an entry from underflowing
+MAX_PASS_PINNED = 128   # the default cap of the passes of one pinned fit, and of the full fit of ``intervals``
+# ``intervals(batch=None)`` takes the largest batch within two budgets - design choices, not measurements:
+BATCH_SCRATCH_BYTES = 1 << 30   # the scratch of espm_spectra_ml_pass_batch (the partial sums of every model's pass)
+BATCH_INFO_BYTES = 256 << 20    # the stacked information matrices, B (m k)^2 doubles
 
 
 def _positive_int(v, name):
@@ -210,6 +222,175 @@ class _Solver:
                 res["W"], res["channel_deviance"] = _image.to_host(kept[0]), _image.to_host(kept[1])
         return res
 
+    # ---- the pinned rule, many problems in lockstep (tests/spectra_ml_pinned_reference.py) -----------------------------------------------
+    def batch_buffers(self, B):
+        """The outputs, the counters and the scratch of espm_spectra_ml_pass_batch for B models (kept for the next call at the same B)."""
+        import torch
+
+        from espm_amd import _lib
+        if getattr(self, "_batch", (0, None))[0] != B:
+            n, k = self.n, self.k
+            nt = k * (k + 1) // 2
+            nbytes = int(_lib.lib.espm_spectra_ml_pass_batch_scratch(n, self.p, k, B))
+            z = dict(dtype=torch.float64, device=self.dev)
+            self._batch = None   # (the buffers of another B go before these come)
+            self._batch = (B, dict(dev=torch.zeros((B, n), **z), ysum=torch.zeros((B, n), **z), q=torch.zeros((B, n, k), **z),
+                                   tri=torch.zeros((B, n, nt), **z), un=torch.zeros(B, dtype=torch.int64, device=self.dev),
+                                   scratch=torch.empty(nbytes // 8, **z), nbytes=nbytes))
+        return self._batch[1]
+
+    def device_pass_batch(self, Wd, active, buf):
+        """The pass at D_b = G W_b for the models with ``active`` (B,) uint8 set: (dev (B, n), Q (B, n, k), A (B, n, k, k)) on the
+        device, the unmodelled counts in ``buf["un"]``.  The rows of a model that is not active are those of its last active pass."""
+        import torch
+
+        from espm_amd import _lib
+        from espm_amd.engine import _ptr, _stream
+        B, k = Wd.shape[0], self.k
+        Dd = (self.Gd @ Wd).contiguous()
+        _lib.check(_lib.lib.espm_spectra_ml_pass_batch(*self.image.abi(), _ptr(Dd), _ptr(self.Hd), k, B, _ptr(active), self.log_shift,
+                                                       _ptr(buf["dev"]), _ptr(buf["ysum"]), _ptr(buf["q"]), _ptr(buf["tri"]), _ptr(buf["un"]),
+                                                       _ptr(buf["scratch"]), buf["nbytes"], _stream()))
+        A = torch.empty((B, self.n, k, k), dtype=torch.float64, device=self.dev)
+        A[:, :, self.il, self.jl] = buf["tri"]
+        A[:, :, self.jl, self.il] = buf["tri"]
+        return buf["dev"], buf["q"], A
+
+    def lockstep(self, F, pins, t, W0, root=None):
+        """B pinned problems of the free set F (host bool (m, k)) at once, every pass ONE batched device pass and ONE small read-back:
+        problem b holds entry ``pins[b]`` (an entry of F) at ``t[b]`` and fits the others from ``W0[b]`` (host, (B, m, k), positive on
+        F).  Without ``root`` a problem is that one fit.  With ``root`` = dict(up (B,) bool, w_ml, w0 (B,), dev_ml, q_level, lr_tol,
+        max_eval, lift (m, k)) it is one END of a profile interval: the bracketed root finder of the reference moves t from fit to
+        fit, each fit warm-started at the one before.  A problem retires on its own (its flag in ``active`` goes to 0: the device
+        pass skips it); nothing is re-packed.  Returns host arrays: W (B, m, k), deviance, gap, slope, channel_deviance (B, n) of the
+        last accepted point, n_pass, n_rejected, n_fallback, converged (of the last fit), unmodelled, n_lockstep (the batched passes
+        this call took: its loop's own count), and with ``root`` also end (NaN where the end was not found), found, n_eval.
+
+        ONE SHAPE FOR ALL: every lockstep pass forms the whole (B, m k, m k) stack of information matrices and factors B systems of
+        |F| unknowns, also for the problems that have retired or that only evaluate this pass - those solve the identity, and their
+        results are never selected.  The device pass skips a retired problem; the dense algebra does not, so on a small image, where
+        that algebra is the cost of a pass, the retired problems of a batch are paid for until its last problem ends.  (Re-packing
+        the batch would save that at the price of new shapes, and new roundings, from pass to pass.)"""
+        import torch
+        self.upload()
+        m, k, n, N = self.m, self.k, self.n, self.N
+        B, mk = len(pins), self.m * self.k
+        inf = float("inf")
+        with self.image.scope():
+            f64, i64 = dict(dtype=torch.float64, device=self.dev), dict(dtype=torch.int64, device=self.dev)
+            buf = self.batch_buffers(B)
+            idx = torch.from_numpy(np.flatnonzero(F.ravel())).to(self.dev)
+            flat = pins[:, 0] * k + pins[:, 1]
+            Mh = np.repeat(F.ravel()[None], B, axis=0)
+            Mh[np.arange(B), flat] = False
+            M = torch.from_numpy(Mh).to(self.dev)
+            MF = M[:, idx]
+            pin, ar = torch.from_numpy(flat).to(self.dev), torch.arange(B, device=self.dev)
+            a = self.ad.reshape(mk)
+            a1 = torch.where(a > 0, a, torch.ones_like(a))   # (outside F, where a may be 0, nothing of this is used)
+            floor = H_FLOOR * N / a1
+            tt = torch.from_numpy(np.ascontiguousarray(t, dtype=np.float64)).to(self.dev)
+            W = torch.from_numpy(np.ascontiguousarray(W0, dtype=np.float64).reshape(B, mk)).to(self.dev)
+            W[ar, pin] = tt
+            alive = torch.ones(B, dtype=torch.bool, device=self.dev)
+            tau, dev_acc = torch.full((B,), TAU0, **f64), torch.full((B,), inf, **f64)
+            trial, conv = torch.zeros_like(alive), torch.zeros_like(alive)
+            e = W.clone()
+            fit_pass, n_pass, n_rej, n_fb, kept_un = (torch.zeros(B, **i64) for _ in range(5))
+            kept_W, kept_devc = W.clone(), torch.zeros((B, n), **f64)
+            kept_dev, kept_gap, kept_slope = (torch.zeros(B, **f64) for _ in range(3))
+            eye = torch.eye(idx.numel(), **f64)
+            if root is not None:
+                up = torch.from_numpy(np.ascontiguousarray(root["up"], dtype=bool)).to(self.dev)
+                w_ml, w0 = (torch.from_numpy(np.ascontiguousarray(root[key], dtype=np.float64)).to(self.dev) for key in ("w_ml", "w0"))
+                lift = torch.from_numpy(np.ascontiguousarray(root["lift"], dtype=np.float64).reshape(mk)).to(self.dev)
+                lo, hi = torch.where(up, w_ml, torch.zeros_like(w_ml)), torch.where(up, torch.full_like(w_ml, inf), w_ml)
+                n_eval, end, found = torch.zeros(B, **i64), torch.full((B,), float("nan"), **f64), torch.zeros_like(alive)
+            un_max = n_lockstep = 0
+            while True:
+                n_lockstep += 1
+                active = alive.to(torch.uint8)
+                dev_c, Q, A = self.device_pass_batch(W.view(B, m, k), active, buf)
+                q = (self.Gd.T @ Q).reshape(B, mk)
+                dv = dev_c.sum(dim=1)
+                n_pass += alive
+                fit_pass += alive
+                rej = alive & trial & ~(dv <= dev_acc)
+                acc = alive & ~rej
+                r = torch.where(M, q / a1, torch.zeros_like(q))
+                rmax = torch.where(M, r, torch.full_like(r, -inf)).max(dim=1).values   # (M empty: -inf, and a gap of 0)
+                gap = 2.0 * torch.where(M, (a - q) * W, torch.zeros_like(q)).sum(dim=1) + 2.0 * N * torch.clamp(rmax - 1.0, min=0.0)
+                slope = 2.0 * (a[pin] - q[ar, pin])
+                stop = acc & (gap <= self.tol)
+                go = acc & ~stop
+                # ACCEPT: the point is the one reported
+                dev_acc = torch.where(acc, dv, dev_acc)
+                kept_W, kept_devc = torch.where(acc[:, None], W, kept_W), torch.where(acc[:, None], dev_c, kept_devc)
+                kept_dev, kept_gap, kept_slope = torch.where(acc, dv, kept_dev), torch.where(acc, gap, kept_gap), torch.where(acc, slope, kept_slope)
+                kept_un = torch.where(acc, buf["un"], kept_un)
+                conv = torch.where(alive, stop, conv)
+                tau = torch.where(go & trial, torch.clamp(tau / TAU_STEP, min=TAU_MIN), tau)
+                # ... its EM successor and the blended Newton step over M (a problem that does not step solves the identity)
+                e_new = W * r
+                e_new[ar, pin] = tt
+                WF, aF = W[:, idx], a[idx]
+                step_at = MF & go[:, None]
+                Bm = torch.einsum("ce,cf,bcij->beifj", self.Gd, self.Gd, A).reshape(B, mk, mk)[:, idx][:, :, idx]
+                Bm = torch.where(step_at[:, :, None] & step_at[:, None, :], Bm, torch.zeros_like(Bm))
+                Bm.diagonal(dim1=1, dim2=2).add_(torch.where(step_at, tau[:, None] * (aF / WF), torch.ones_like(WF)))
+                Bm = torch.where(go[:, None, None], Bm, eye)
+                rhs = torch.where(step_at, (q - a)[:, idx], torch.zeros_like(WF))
+                L, info = torch.linalg.cholesky_ex(Bm)
+                delta = torch.cholesky_solve(rhs[:, :, None], L)[:, :, 0]
+                ok = (info == 0) & torch.isfinite(delta).all(dim=1)
+                step = W.clone()
+                step[:, idx] = torch.where(MF, torch.maximum(torch.maximum(WF + delta, THETA * WF), floor[idx]), WF)
+                n_fb += go & ~ok
+                n_rej += rej
+                # REJECT: the EM successor of the last accepted point
+                W = torch.where(go[:, None], torch.where(ok[:, None], step, e_new), torch.where(rej[:, None], e, W))
+                e = torch.where(go[:, None], e_new, e)
+                trial = torch.where(go, ok, trial & ~rej)
+                tau = torch.where(rej, torch.clamp(tau * TAU_STEP, max=TAU_MAX), tau)
+                capped = alive & ~stop & (fit_pass >= self.max_pass)
+                if root is None:
+                    alive = alive & ~stop & ~capped
+                else:
+                    # a fit that certified is one evaluation of phi: the end, or the bracket and the next t (the reference's _advance)
+                    phi = dv - root["dev_ml"] - root["q_level"]
+                    n_eval += stop
+                    first_low = ~up & (n_eval == 1)
+                    fin = stop & ((phi.abs() <= root["lr_tol"]) | (first_low & (phi <= 0)))
+                    end, found = torch.where(fin, tt, end), found | fin
+                    more = stop & ~fin & (n_eval < root["max_eval"])
+                    inner = torch.where(up, phi < 0, phi > 0)
+                    lo2, hi2 = torch.where(inner, tt, lo), torch.where(inner, hi, tt)
+                    tn = tt - phi / slope
+                    open_ = torch.isinf(hi2)
+                    good = torch.isfinite(tn) & (tn > lo2) & (tn < hi2)
+                    tn = torch.where(open_, torch.minimum(tn, w_ml + 8.0 * (tt - w_ml)), tn)
+                    mid = torch.where(open_, w_ml + 2.0 * (tt - w_ml), 0.5 * (lo2 + hi2))
+                    tn = torch.where(good, tn, mid)
+                    tn = torch.where(first_low, torch.maximum(w_ml - w0, 0.5 * w_ml), tn)
+                    tt, lo, hi = torch.where(more, tn, tt), torch.where(more, lo2, lo), torch.where(more, hi2, hi)
+                    Wr = torch.where(M, torch.maximum(W, lift), W)
+                    Wr[ar, pin] = tt
+                    W = torch.where(more[:, None], Wr, W)
+                    tau, dev_acc = torch.where(more, torch.full_like(tau, TAU0), tau), torch.where(more, torch.full_like(tau, inf), dev_acc)
+                    trial, fit_pass = trial & ~more, torch.where(more, torch.zeros_like(fit_pass), fit_pass)
+                    alive = alive & ~capped & ~(stop & ~more)
+                # the one read-back of a lockstep pass: how many problems go on, and the counters (the most entries under the floor)
+                live, un = (int(v) for v in torch.stack((alive.sum(), torch.where(active.bool(), buf["un"], torch.zeros_like(kept_un)).max())).cpu())
+                un_max = max(un_max, un)
+                if live == 0:
+                    break
+            h = _image.to_host
+            out = dict(W=h(kept_W).reshape(B, m, k), deviance=h(kept_dev), gap=h(kept_gap), slope=h(kept_slope), channel_deviance=h(kept_devc),
+                       n_pass=h(n_pass), n_rejected=h(n_rej), n_fallback=h(n_fb), converged=h(conv), unmodelled=h(kept_un), unmodelled_max=un_max, n_lockstep=n_lockstep)
+            if root is not None:
+                out.update(end=h(end), found=h(found), n_eval=h(n_eval))
+        return out
+
 
 def ml_spectra(X, G, H, W0=None, free=None, tol=1e-3, max_pass=MAX_PASS, log_shift=1e-14, layout="cm", device=None):
     """The Poisson maximum-likelihood W (m, k) >= 0 of D = G W given the dictionary G (n, m) and the abundances H (k, p), over the
@@ -280,3 +461,144 @@ def presence(X, G, H, W0=None, free=None, entries=None, tol=1e-3, max_pass=MAX_P
     return dict(W_ml=full["W"], deviance_ml=full["deviance"], lr=lr, pvalue=pv, entries=ent,
                 converged=np.array([r["converged"] for r in rows], dtype=bool), gap=np.array([r["gap"] for r in rows], dtype=np.float64),
                 n_pass=np.array([r["n_pass"] for r in rows], dtype=np.int64), inert=inert, unmodelled=full["unmodelled"])
+
+
+def _check_pin(pin, F, who):
+    try:
+        e, j = (int(v) for v in pin)
+        ok = len(pin) == 2 and all(int(v) == v and not isinstance(v, bool) for v in pin)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or not (0 <= e < F.shape[0] and 0 <= j < F.shape[1]) or not F[e, j]:
+        raise ValueError(f"{who}: pin must be an (element, component) pair inside the free set the model sees, not {pin!r}")
+    return e, j
+
+
+def ml_spectra_pinned(X, G, H, pin, t, W0=None, free=None, tol=1e-3, max_pass=MAX_PASS_PINNED, log_shift=1e-14, layout="cm", device=None):
+    """ONE POINT OF THE PROFILE: the Poisson maximum-likelihood W >= 0 over ``free`` with the entry ``pin`` = (element, component)
+    HELD AT ``t`` >= 0, by the pinned rule of tests/spectra_ml_pinned_reference.py - ``ml_spectra``'s rule without the scale onto
+    the ray, with a certificate of its own.  Returns ``ml_spectra``'s dict, where
+
+    * ``W`` has ``W[pin] == t`` bit for bit and is NOT scaled onto the ray;
+    * ``gap`` = 2 sum_M (a - q) W + 2 N max(max_M q / a - 1, 0) over M = the free set less the pin: ``deviance`` is above its minimum
+      over {W >= 0, W[pin] = t} by at most ``gap`` (convexity, and sum_M a W* <= N at the pinned optimum; ``ml_spectra``'s caveat for
+      counted entries under the floor applies);
+
+    plus ``slope`` = 2 (a_pin - q_pin): the derivative of the profile deviance in t at this point (by the envelope theorem, exact at
+    the pinned optimum).  A free set of the pin alone is one evaluating pass with gap 0.  Arguments and refusals as for
+    ``ml_spectra``; ValueError also for a ``pin`` outside the free set the model sees and for a ``t`` that is negative or not finite
+    - before anything is uploaded.  ``W0``: the start of the other entries (None: 1; an entry that is not > 0 becomes
+    N / (|M| a_ej) * 1e-3)."""
+    sv = _Solver(X, G, H, tol, max_pass, log_shift, layout, device, "ml_spectra_pinned")
+    W0 = sv.check_start(W0)
+    F, inert = sv.check_free(free)
+    pin = _check_pin(pin, F, "ml_spectra_pinned")
+    if isinstance(t, bool) or not np.isfinite(float(t)) or float(t) < 0:
+        raise ValueError(f"ml_spectra_pinned: t must be finite and not negative, not {t!r}")
+    sv.upload()
+    M = F.copy()
+    M[pin] = False
+    W0 = np.where(M, W0, 0.0)
+    if sv.N == 0:
+        W0[:] = 0.0
+    elif M.any():
+        bad = M & ~(W0 > 0)
+        W0[bad] = sv.N / (M.sum() * sv.a[bad]) * START
+    out = sv.lockstep(F, np.array([pin], dtype=np.int64), np.array([float(t)]), W0[None])
+    return dict(W=out["W"][0], deviance=float(out["deviance"][0]), channel_deviance=out["channel_deviance"][0], gap=float(out["gap"][0]),
+                slope=float(out["slope"][0]), n_pass=int(out["n_pass"][0]), n_rejected=int(out["n_rejected"][0]),
+                n_fallback=int(out["n_fallback"][0]), converged=bool(out["converged"][0]), unmodelled=int(out["unmodelled"][0]), inert=inert)
+
+
+def _auto_batch(sv, n_problems):
+    """The largest batch within BATCH_SCRATCH_BYTES and BATCH_INFO_BYTES (at least 1, at most the problems there are)."""
+    from espm_amd import _lib
+    per_model = int(_lib.lib.espm_spectra_ml_pass_batch_scratch(sv.n, sv.p, sv.k, 1))
+    return int(max(1, min(n_problems, BATCH_SCRATCH_BYTES // per_model, BATCH_INFO_BYTES // ((sv.m * sv.k) ** 2 * 8))))
+
+
+def intervals(X, G, H, W0=None, free=None, entries=None, level=0.95, tol=1e-3, lr_tol=1e-2, max_eval=64, max_pass=MAX_PASS_PINNED,
+              batch=None, log_shift=1e-14, layout="cm", device=None):
+    """How much of element e could be in phase j?  The PROFILE-LIKELIHOOD interval of entries of W with the abundances H held: the
+    values t whose best fit with W_ej held at t (``ml_spectra_pinned``) lies within the chi2_1 quantile ``threshold`` =
+    2 erfinv(level)^2 of the best fit (``ml_spectra``).  Where the entry sits at the boundary - a trace element - the interval starts
+    at exactly 0 and its upper end is an UPPER LIMIT ("< 0.05 at 95 %"); away from it the two ends are an asymmetric error bar
+    ("0.8 (0.5 - 1.2)").  ``presence``'s statistic is this profile at the single point t = 0.  The intervals are two-sided: a one-sided
+    95 % upper limit is the upper end at ``level=0.90``.  Returns dict(
+
+    * ``W_ml`` (m, k), ``deviance_ml``: the full fit;
+    * ``lower``, ``upper`` (m, k): the ends, with |g(t) - deviance_ml - threshold| <= ``lr_tol`` for the certified pinned deviance g
+      (each of the two deviances within ``tol`` of its minimum); ``lower`` is EXACTLY 0 where ``W_ml`` is 0 and where
+      g(0) - deviance_ml <= threshold (``presence``'s lr <= threshold: the boundary); NaN for the entries not tested, for an entry
+      outside the free set, and for an end that was not found;
+    * ``level``, ``threshold``, ``entries`` (E, 2): the tested (element, component) pairs - ``entries`` as given, by default every
+      free entry the model sees;
+    * ``converged`` (bool), ``n_eval``, ``n_pass``, each (E, 2): [:, 0] the lower end, [:, 1] the upper - whether the end was found,
+      the pinned fits it took and their passes over the image (an entry outside the free set is no fit: converged, 0, 0);
+    * ``n_full_pass``: the passes of the full fit; ``inert``, ``unmodelled``: of the full fit;
+    * ``batch``: the problems that ran in lockstep; ``n_lockstep``: the batched device passes (and read-backs) the ends took).
+
+    The full fit is ``ml_spectra``'s; then all 2 E ends advance TOGETHER, ``batch`` problems at a time (None: the largest batch for
+    which the scratch of the batched pass stays within BATCH_SCRATCH_BYTES and the stacked information matrices within
+    BATCH_INFO_BYTES).  A lockstep pass is one batched G W, one espm_spectra_ml_pass_batch over the resident image for the problems
+    still running, batched G^T Q, information matrices and Cholesky in torch fp64 on the device, the accept / reject / stop of
+    every problem and the root finder's bracket and next t as masked tensor updates, and ONE small read-back.  Every evaluation is a
+    pinned fit warm-started at the one before with the fitted entries lifted to the rule's own start fill.  A pinned fit that does
+    not converge within ``max_pass``, or an end that takes more than ``max_eval`` fits, ends as not converged (NaN), without an
+    exception.  Two calls with the same arguments give the same bits; another ``batch`` meets the same bound, not the same bits.
+
+    What the interval is NOT: it holds H fixed (its uncertainty is not in it); it is the interval of W_ej itself, not of a normalised
+    concentration W_ej / sum_e W_ej; no simplex over W, no ``mu`` and no floor of a fit is imposed; and it is ASYMPTOTIC.  One GPU per
+    call.  Arguments and refusals as for ``presence``; ValueError also for ``level`` outside (0, 1), ``lr_tol`` not positive, and
+    ``max_eval`` or ``batch`` that are no positive integers - all before anything is uploaded."""
+    from espm_amd.presence import threshold
+    sv = _Solver(X, G, H, tol, max_pass, log_shift, layout, device, "intervals")
+    W0 = sv.check_start(W0)
+    F, inert = sv.check_free(free)
+    if not F.any():
+        raise ValueError("intervals: no free entry of W that the model can see")
+    ql = threshold(level)
+    if not lr_tol > 0:
+        raise ValueError("lr_tol must be positive")
+    max_eval = _positive_int(max_eval, "max_eval")
+    if batch is not None:
+        batch = _positive_int(batch, "batch")
+    ent = np.argwhere(F) if entries is None else _check_entries(entries, sv.m, sv.k, "intervals")
+    E = len(ent)
+    full = sv.run(W0, F)
+    W_ml, N = full["W"], sv.N
+    lower, upper = np.full((sv.m, sv.k), np.nan), np.full((sv.m, sv.k), np.nan)
+    conv, n_eval, n_pass = np.zeros((E, 2), dtype=bool), np.zeros((E, 2), dtype=np.int64), np.zeros((E, 2), dtype=np.int64)
+    # the ends that need no fit are settled here; the others are the problems of the lockstep, in the order (entry, side)
+    prob = []
+    for i, (e, j) in enumerate(ent):
+        if not F[e, j]:
+            conv[i] = True
+        elif full["converged"]:
+            if W_ml[e, j] == 0:
+                lower[e, j], conv[i, 0] = 0.0, True
+            else:
+                prob.append((i, 0))
+            prob.append((i, 1))
+    nF = int(F.sum())
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lift = np.where(F, N / ((nF - 1) * sv.a) * START, 0.0) if nF > 1 else np.zeros(F.shape)
+    B = 0 if not prob else (_auto_batch(sv, len(prob)) if batch is None else min(batch, len(prob)))
+    n_lockstep = 0
+    for at in range(0, len(prob), max(B, 1)):
+        part = np.array(prob[at:at + B])
+        pins, up = ent[part[:, 0]], part[:, 1] == 1
+        w_ml, ae = W_ml[pins[:, 0], pins[:, 1]], sv.a[pins[:, 0], pins[:, 1]]
+        w0 = np.sqrt(ql) * np.sqrt(ae * w_ml + ql) / ae
+        start = np.repeat(np.where(F, np.maximum(W_ml, lift), 0.0)[None], len(part), axis=0)
+        out = sv.lockstep(F, pins, np.where(up, w_ml + w0, 0.0), start,
+                          root=dict(up=up, w_ml=w_ml, w0=w0, dev_ml=full["deviance"], q_level=ql, lr_tol=float(lr_tol), max_eval=max_eval,
+                                    lift=lift))
+        for b, (i, side) in enumerate(part):
+            e, j = ent[i]
+            conv[i, side], n_eval[i, side], n_pass[i, side] = out["found"][b], out["n_eval"][b], out["n_pass"][b]
+            (upper if side else lower)[e, j] = out["end"][b]
+        n_lockstep += out["n_lockstep"]
+    return dict(W_ml=W_ml, deviance_ml=full["deviance"], lower=lower, upper=upper, level=float(level), threshold=ql, entries=ent,
+                converged=conv, n_eval=n_eval, n_pass=n_pass, n_full_pass=full["n_pass"], inert=inert, unmodelled=full["unmodelled"],
+                batch=B, n_lockstep=n_lockstep)

@@ -1266,6 +1266,28 @@ int espm_spectra_ml_pass(const void* x, int x_dtype, int x_layout, int64_t ld, i
                          void* scratch, size_t scratch_bytes, espm_stream_t stream);
 size_t espm_spectra_ml_pass_scratch(int n, int p, int k);
 
+/* ---- spectra ML pass, batched (csrc/mu_spectra_ml.hip; espm_amd.spectra_ml.intervals, NMFEstimator.concentration_intervals) ----
+ * espm_spectra_ml_pass for n_models models d[b] (n, k), b = 0 .. n_models - 1, of ONE resident image and ONE h, in one pass launch
+ * and one reduction launch: the model index is the third grid dimension, the kernel body, the tile code, the accumulation order and
+ * the ascending chunk reduction are the single pass's own (one device function that both kernels call).  Model b's dev[b] (n,),
+ * ysum[b] (n,), q[b] (n, k), a_tri[b] (n, k (k + 1) / 2) and unmodelled[b] are BIT-EQUAL to what espm_spectra_ml_pass gives at d[b],
+ * whatever n_models, the order of the models and the flags of the others.  (xsum does not depend on the model: not an output.)
+ * active (device, (n_models,) bytes; null: every model): a workgroup of either launch whose model has active[b] == 0 returns at
+ * entry, before it touches x - a RETIRED model costs a launch slot and nothing else, and its outputs and its counter are left
+ * exactly as they were.  The counters of the active models are zeroed by the call (a launch of n_models threads ahead of the pass).
+ * This is what lets many fits of one image run in lockstep, each retiring on its own, without re-packing the problems.
+ * Scratch: espm_spectra_ml_pass_batch_scratch(n, p, k, n_models) bytes = n_models x espm_spectra_ml_pass_scratch(n, p, k), model b's
+ * partial sums at b x that.  X is re-read once per model (the pass is bound by its arithmetic, not by X).  No float atomics.
+ * ESPM_EINVAL, before the device is touched: the single pass's refusals (active may be null), n_models outside
+ * 1..ESPM_SML_MAX_MODELS, scratch_bytes below what the query returns (the message names both sizes); ESPM_EUNSUPPORTED for k outside
+ * 1..ESPM_DIAG_MAX_K.  Only the narrow build has the kernels; the wide builds return ESPM_EUNSUPPORTED, and their query returns 0
+ * (as it does for arguments out of range).  No espm_mu_state is involved: ESPM_MU_ABI_VERSION stays. */
+#define ESPM_SML_MAX_MODELS 65535   /* models of one call: the third grid dimension */
+int espm_spectra_ml_pass_batch(const void* x, int x_dtype, int x_layout, int64_t ld, int n, int p, const double* d, const double* h,
+                               int k, int n_models, const uint8_t* active, double log_shift, double* dev, double* ysum, double* q,
+                               double* a_tri, int64_t* unmodelled, void* scratch, size_t scratch_bytes, espm_stream_t stream);
+size_t espm_spectra_ml_pass_batch_scratch(int n, int p, int k, int n_models);
+
 /* ---- LDS of the sparse H-step (csrc/mu_ell_plan.hpp: plan_h_ell; espm_amd.ell.lds_bytes_h, the store choice of espm_amd.store) ----
  * Dynamic LDS, in bytes, that the H-step of the sparse count store (x_dtype = ESPM_X_ELL) takes for n_pad channels and k components
  * at the full tile (tile_px = ESPM_ELL_TILE) without the copy of colsum(GW') that a riding W tail adds: the G W table plus the
