@@ -41,6 +41,7 @@ RESID_MAX_G, RESID_MAX_K, RESID_BLOCK, RESID_PCHUNK = (_D["ESPM_RESID_" + n] for
 RESID_PIXELS, RESID_CHANNELS = _E["ESPM_RESID_PIXELS"], _E["ESPM_RESID_CHANNELS"]
 PML_MAX_K = _D["ESPM_PML_MAX_K"]
 PMLN_STATE_EXTRA = _D["ESPM_PMLN_STATE_EXTRA"]   # espm_pixel_ml_newton's state: (k + PMLN_STATE_EXTRA, p) doubles
+CML_STATE_EXTRA = _D["ESPM_CML_STATE_EXTRA"]     # espm_channel_ml_step's state: (n_models, 2 k + CML_STATE_EXTRA, n) doubles
 PML_NOT_DONE, PML_UNMODELLED, PML_NONFINITE, PML_COUNTERS = (_E["ESPM_PML_" + n] for n in ("NOT_DONE", "UNMODELLED", "NONFINITE", "COUNTERS"))
 SRC_F32, SRC_F64 =_E["ESPM_SRC_F32"], _E["ESPM_SRC_F64"]
 LAYOUT_CM, LAYOUT_PM = _E["ESPM_LAYOUT_CM"], _E["ESPM_LAYOUT_PM"]

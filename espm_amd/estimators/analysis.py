@@ -1,7 +1,7 @@
 """What an estimator does with a fit besides fitting (no reference analogue; ``NMFEstimator`` inherits the mixin): the fits around
 ``fit_transform`` - on the binned image, on a thinned image - and the analyses of a fitted model - diagnostics, count attribution,
 line maps and region spectra, residual components, draws from the model.  Each method prepares host arrays and hands them to ``espm_amd.binning``,
-``splitting``, ``measures``, ``attribution``, ``marginals``, ``residuals``, ``presence``, ``spectra_ml`` or ``sampling``, imported when it is called; the set-up they share stands once, ahead of them.  The fit itself, ``unmix``
+``splitting``, ``measures``, ``attribution``, ``marginals``, ``residuals``, ``presence``, ``spectra_ml``, ``channel_ml`` or ``sampling``, imported when it is called; the set-up they share stands once, ahead of them.  The fit itself, ``unmix``
 and the engine plumbing are next door in base.py.
 """
 from __future__ import annotations
@@ -644,6 +644,101 @@ class _FitAnalysis:
         self.W_lower_, self.W_upper_, self.W_interval_level_ = out["lower"], out["upper"], out["level"]
         self.W_interval_entries_, self.W_interval_converged_, self.W_interval_n_eval_ = out["entries"], out["converged"], out["n_eval"]
         self.W_ml_, self.W_deviance_ml_ = out["W_ml"], out["deviance_ml"]
+        return out
+
+    # ---- is this line of phase j real, and how much could be under it: free spectra given H, channel by channel -----------------------
+    def _channel_ml_refusal(self, who):
+        """The refusals ``spectrum_presence`` and ``spectrum_intervals`` share, raised before anything is uploaded.  Returns k."""
+        from espm_amd import channel_ml
+        check_is_fitted(self, "W_")
+        if getattr(self, "_shard_group", None) is not None:
+            raise NotImplementedError(f"{who} does not cover shard(): the channel fits run on one GPU")
+        k = int(self.H_.shape[0])
+        if k > channel_ml.MAX_K:
+            raise NotImplementedError(f"{who}: {k} components (the kernels are built for 1..{channel_ml.MAX_K})")
+        return k
+
+    def spectrum_presence(self, X=None, windows=None, tol=1e-3, max_pass=None):
+        """Is this line of phase j real?  ``espm_amd.channel_ml.presence`` on the fitted abundances ``H_``, started at the fitted
+        spectra D = ``W_`` (identity G) or ``G_ @ W_``: the Poisson maximum-likelihood spectra given the abundances with NO dictionary
+        behind them - every channel a problem of its own - and for every channel and component the likelihood ratio between that fit
+        and the channel's best fit WITHOUT the component.  It is the test for a fit with ``G=None``, where most channels of a phase
+        spectrum sit at or near zero and the Wald bar ``W_std_`` means nothing; with a dictionary it is the dictionary-free fit to
+        hold ``G_ @ W_`` against - a line the element list missed shows in ``D_excess_deviance_``.  No reference analogue.
+
+        Sets ``D_ml_`` (n, k) and ``D_deviance_ml_`` (n,), the free fit; ``D_excess_deviance_`` (n,) = the deviance of every channel at
+        the fitted spectra less ``D_deviance_ml_``: what the fitted (or dictionary-bound) spectra lose against free spectra, at least
+        -tol; ``D_presence_lr_`` (n, k) = max(deviance without j - deviance_ml, 0), exactly 0 where ``D_ml_`` is 0, and
+        ``D_presence_pvalue_`` (n, k), its tail under 1/2 chi2_0 + 1/2 chi2_1 (asymptotic); ``D_ml_converged_`` (k + 1, n): row 0 the
+        full fit, row 1 + j the fit without j.  With ``windows`` - half-open ranges (lo, hi) of channel indices, one per line - also
+        ``line_presence_lr_`` and ``line_presence_pvalue_`` (windows, k): the test of "phase j has nothing in the whole window"
+        (``channel_ml.line_presence``: given ``H_`` the channels are independent and their ratios add).  Returns
+        ``channel_ml.presence``'s dict, with ``excess_deviance`` and, with ``windows``, ``line_lr`` and ``line_pvalue``.
+
+        The ML is over D >= 0 with ``H_`` held: ``mu``, ``simplex_W`` and the floors of the fit are NOT imposed, and the uncertainty of
+        ``H_`` is not in the statistic.  At least 2 and at most 8 components (ValueError, NotImplementedError); ``shard()``ed
+        estimators raise NotImplementedError; ``windows`` are checked against the channels - all before anything is uploaded.
+
+        ``tol``: the certified gap, in deviance units, at which a channel stops; ``max_pass``: the cap of a fit's passes over the
+        image (None: ``channel_ml.MAX_PASS``).  ``X`` as for ``pixel_diagnostics``; ``X=None`` takes the fit's ``X_`` un-scaled, with
+        the cost and the ``log_shift`` fill described there (refused after ``fit_binned``).  Computed in fp64 whatever the estimator's
+        precision, on the current device."""
+        from espm_amd import channel_ml, marginals
+        k = self._channel_ml_refusal("spectrum_presence")
+        if k < 2:
+            raise ValueError("spectrum_presence: one component (without it the model is empty: nothing to test)")
+        if windows is not None:
+            windows = list(windows)
+            marginals.window_weights(int(self.G_.shape[0]), windows)
+        X, layout = self._image_argument(X, "spectrum_presence")
+        D, H = self._model_counts()
+        out = channel_ml.presence(X, H, D0=D, tol=tol, max_pass=channel_ml.MAX_PASS if max_pass is None else max_pass,
+                                  log_shift=self.log_shift, layout=layout)
+        out = dict(out, excess_deviance=out["deviance_start"] - out["deviance_ml"])
+        self.D_ml_, self.D_deviance_ml_, self.D_excess_deviance_ = out["D_ml"], out["deviance_ml"], out["excess_deviance"]
+        self.D_presence_lr_, self.D_presence_pvalue_, self.D_ml_converged_ = out["lr"], out["pvalue"], out["converged"]
+        if windows is not None:
+            line = channel_ml.line_presence(out["lr"], windows)
+            self.line_presence_lr_, self.line_presence_pvalue_ = line["lr"], line["pvalue"]
+            out = dict(out, line_lr=line["lr"], line_pvalue=line["pvalue"])
+        return out
+
+    def spectrum_intervals(self, level=0.95, X=None, components=None, tol=1e-3, lr_tol=1e-2, max_eval=None, max_pass=None):
+        """How much could be under this peak at most?  ``espm_amd.channel_ml.intervals`` on the fitted abundances ``H_``, started at
+        the fitted spectra D = ``W_`` (identity G) or ``G_ @ W_``: for every channel and every requested component the
+        PROFILE-LIKELIHOOD band of the spectrum - the values t whose best fit with d_cj held at t lies within the chi2_1 quantile
+        2 erfinv(level)^2 of the channel's best fit with free spectra.  Where the spectrum sits at or near zero the band starts at
+        exactly 0 and ``D_upper_`` is an upper limit; on a peak the two ends are an asymmetric error bar.  ``spectrum_presence``'s
+        statistic is the same profile at the single point t = 0.  Two-sided: a one-sided 95 % upper limit is ``D_upper_`` at
+        ``level=0.90``.  No reference analogue.
+
+        Sets ``D_lower_``, ``D_upper_`` (n, k) (NaN in columns not requested and for channels that did not finish);
+        ``D_interval_level_``; ``D_interval_converged_`` (bool) and ``D_interval_n_eval_`` (k, 2, n): [:, 0] the lower end, [:, 1] the
+        upper; and ``D_ml_`` (n, k), ``D_deviance_ml_`` (n,), the free fit.  Returns ``channel_ml.intervals``'s dict.  The fitted
+        attributes are not touched.
+
+        What the band is NOT: it holds ``H_`` fixed (the abundances' own uncertainty is not in it); ``mu``, ``simplex_W`` and the
+        floors of the fit are NOT imposed; it is ASYMPTOTIC in the counts of a channel; and it runs on one GPU.  1 .. 8 components
+        (NotImplementedError beyond); ``shard()``ed estimators raise NotImplementedError - before anything is uploaded.
+
+        ``level``: strictly between 0 and 1.  ``components``: the columns to compute (None: all).  ``tol``: the certified gap of
+        every fit; ``lr_tol``: how close to the quantile an end's deviance difference must come; ``max_eval``: the cap of the pinned
+        fits per end (None: 64); ``max_pass``: the cap of a fit's passes over the image (None: ``channel_ml.MAX_PASS``).  ``X`` as for
+        ``pixel_diagnostics`` (``X=None`` is refused after ``fit_binned``).  Computed in fp64 whatever the estimator's precision, on
+        the current device."""
+        from espm_amd import channel_ml, presence
+        k = self._channel_ml_refusal("spectrum_intervals")
+        presence.threshold(level)
+        if components is not None:
+            presence._components(components, k)
+        X, layout = self._image_argument(X, "spectrum_intervals")
+        D, H = self._model_counts()
+        out = channel_ml.intervals(X, H, D0=D, level=level, components=components, tol=tol, lr_tol=lr_tol,
+                                   max_eval=64 if max_eval is None else max_eval,
+                                   max_pass=channel_ml.MAX_PASS if max_pass is None else max_pass, log_shift=self.log_shift, layout=layout)
+        self.D_lower_, self.D_upper_, self.D_interval_level_ = out["lower"], out["upper"], out["level"]
+        self.D_interval_converged_, self.D_interval_n_eval_ = out["converged"], out["n_eval"]
+        self.D_ml_, self.D_deviance_ml_ = out["D_ml"], out["deviance_ml"]
         return out
 
     # ---- draws from the fitted model: a simulated image, a scale for the deviance map, the parametric bootstrap -------------------

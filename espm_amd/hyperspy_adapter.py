@@ -237,6 +237,23 @@ def concentration_intervals(est):
                 entries=est.W_interval_entries_, converged=est.W_interval_converged_, n_eval=est.W_interval_n_eval_)
 
 
+def spectrum_bands(est):
+    """What ``est.spectrum_intervals()`` and ``est.spectrum_presence()`` set, on the signal axis like the factors - a dict of (k, n)
+    tables: ``D_ml`` (the maximum-likelihood spectra given the abundances, no dictionary behind them), and after
+    ``spectrum_intervals()`` ``lower`` and ``upper`` (the profile-likelihood band of every spectrum; ``upper`` is an upper limit where
+    ``lower`` is 0; NaN where a component was not asked for) with ``level``; after ``spectrum_presence()`` ``lr`` and ``pvalue`` (is
+    component j in this channel at all) and ``excess_deviance`` (n,): what the fitted spectra lose against free ones, per channel."""
+    if not hasattr(est, "D_ml_"):
+        raise AttributeError("call est.spectrum_intervals() or est.spectrum_presence() first: they set D_ml_ and the tables beside it")
+    out = dict(D_ml=np.asarray(est.D_ml_).T)
+    if hasattr(est, "D_upper_"):
+        out.update(lower=np.asarray(est.D_lower_).T, upper=np.asarray(est.D_upper_).T, level=est.D_interval_level_)
+    if hasattr(est, "D_presence_lr_"):
+        out.update(lr=np.asarray(est.D_presence_lr_).T, pvalue=np.asarray(est.D_presence_pvalue_).T,
+                   excess_deviance=np.asarray(est.D_excess_deviance_))
+    return out
+
+
 def abundance_interval_maps(est, shape_2d=None):
     """``est.H_lower_`` and ``est.H_upper_`` (set by ``est.abundance_intervals()``) in the navigation shape, like the loadings:
     (k, ny, nx) each - the ends of the profile-likelihood interval of every abundance; the upper map is the detection limit where

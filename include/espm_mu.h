@@ -1288,6 +1288,65 @@ int espm_spectra_ml_pass_batch(const void* x, int x_dtype, int x_layout, int64_t
                                double* a_tri, int64_t* unmodelled, void* scratch, size_t scratch_bytes, espm_stream_t stream);
 size_t espm_spectra_ml_pass_batch_scratch(int n, int p, int k, int n_models);
 
+/* ---- channel ML step (csrc/mu_channel_ml.hip; espm_amd.channel_ml, NMFEstimator.spectrum_presence, spectrum_intervals) ----
+ * The maximum-likelihood spectra d (n, k) >= 0 given the abundances h (k, p), WITHOUT a dictionary: the problem decouples per
+ * channel.  Channel c is one pixel problem of espm_pixel_ml_newton / espm_pixel_ml_pinned with the roles of the factors swapped:
+ * its observations are the p pixels of row c of X, its design is h^T, its "spectrum sums" are s_j = sum_p h[j, p] (the same for every
+ * channel) and its count total is N_c = xsum[c].  The walk over the observations is espm_spectra_ml_pass_batch, which delivers per
+ * (model, channel) exactly the sums a pixel kernel holds after its walk: dev (already doubled), q (k) and the lower triangle of A.
+ * This entry point is everything those kernels do BETWEEN two walks, for n_models x n problems at once, one thread per problem:
+ *     loop:  espm_spectra_ml_pass_batch(d, active) -> dev_in, q, a_tri;   espm_channel_ml_step(...) -> the next d, done, active
+ * All device arrays but s and pin, which are HOST arrays (k doubles, n_models int32: checked, then passed by value):
+ *   dev_in (n_models, n), q (n_models, n, k), a_tri (n_models, n, k (k + 1) / 2): the batched pass's outputs at the d this call finds
+ *     (not read with start != 0, and may be null then); xsum (n,): espm_spectra_ml_pass's sum_p x, which no model changes
+ *   mask: the component set, the same for every model; pin[b]: -1 - model b fits all of mask by the FREE-SCALE rule
+ *     (espm_pixel_ml_newton's); j, a component of mask - model b holds component j at t[b, c] and fits M = mask less j by the PINNED
+ *     rule (espm_pixel_ml_pinned's; M may be empty).  t (n_models, n) and slope (n_models, n) are read and written for pinned models
+ *     only, and may be null where every pin is -1.  Components outside mask are held at 0.
+ *   d (n_models, n, k), in and out: the point the pass evaluated, replaced by the point the next pass evaluates
+ *   state: caller-owned, ESPM_CML_STATE_BYTES(k, n, n_models) bytes, (n_models, 2 k + ESPM_CML_STATE_EXTRA, n) doubles - rows
+ *     0 .. k - 1: the last ACCEPTED point (what dev and gap belong to), k .. 2 k - 1: e, its EM successor, then dev_acc, tau, trial
+ *   dev, gap, slope (n_models, n) doubles, passes (n_models, n) int32, done (n_models, n) bytes: the outputs per problem, of the last
+ *     accepted point, exactly as the pixel entry points keep them
+ *   active (n_models,) bytes and live (n_models,) int64, both written: live[b] = the problems of model b with done == 0 after the call
+ *     (zeroed by the call, then added to per workgroup: integers), active[b] = (live[b] != 0), set by a second launch of n_models
+ *     threads behind the first on `stream` - the flags espm_spectra_ml_pass_batch skips a retired model by.
+ * start != 0, PASS 0 of every problem with done == 0 (the caller zeroes done; nothing of a pass is consumed, none is counted):
+ *   a pinned t[b, c] that is negative or not finite: done = 2, d as it was.  Otherwise the rule's own start: d_pin = t; d_j = 0
+ *   outside M and pin; N_c == 0: d_M = 0 and, for the free rule, done = 1 at once (the row of zeros, dev = gap = 0); a start in M that
+ *   is not > 0 becomes N_c / (|M| s_j) * 1e-3; the free rule then scales onto the ray (below).  e = 0, dev_acc = +inf, tau = 1e-2,
+ *   trial = 0, the accepted point = the start, dev = gap = slope = 0, passes = 0.  (A pinned problem with N_c == 0 needs no case of
+ *   its own: its first pass finds q = 0, gap = 0 and is done with dev = 2 sum_p max(t h[pin, p], log_shift) and 0 passes.)
+ * start == 0, per problem with done == 0, h = d[b, c], in fp64 and in this order:
+ *   for j in M ascending: r_j = q_j / s_j; rmax = max(rmax, r_j) from -inf; lin = fma(s_j - q_j, h_j, lin) from 0
+ *   free:   gap = 2 N_c (rmax - 1)                              pinned: gap = 2 fma(N_c, max(rmax - 1, 0), lin), slope = 2 (s_pin - q_pin)
+ *   (the certificates of espm_pixel_ml and espm_pixel_ml_pinned: dev is above its minimum over the set by at most gap)
+ *   dev_in or gap not finite: done = 2, dev, gap and slope as computed.
+ *   REJECT, if trial and not dev_in <= dev_acc: h = e (h_pin stays), trial = 0, tau = min(10 tau, 1); passes goes up by one; dev, gap,
+ *   slope and the accepted point stay.
+ *   ACCEPT, otherwise: dev, gap, slope and the accepted point are this point's.  gap <= tol: done = 1, d keeps the point.  Otherwise
+ *   espm_pixel_ml_newton's step 5 word for word: if trial, tau = max(tau / 10, 1e-8); e_j = h_j r_j; B = A over M with
+ *   B_jj = fma(tau, s_j / h_j, A_jj), components outside M (the pinned one too) rows of the identity; the root-free Cholesky
+ *   B = L diag(p) L^T; L z = q - s, z = z / p, L^T delta = z; h_j = max(h_j + delta_j, 0.01 h_j, 1e-30 N_c / s_j) on M and trial = 1 -
+ *   or, if a pivot is not > 0 or not finite, h = e and trial = 0; dev_acc = dev_in; passes goes up by one.
+ *   THE RAY (free rule only, after the start, a rejection and a step): S = fma(s_j, h_j, S) over M ascending; S not > 0 or not finite:
+ *   done = 2, h as the step left it; else h = h (N_c / S) - what espm_pixel_ml_newton does at the head of its pass.
+ *   d[b, c] = h.
+ * THE CALLER'S done IS HONOURED: a problem that enters with done != 0 is neither read nor written (d, state, dev, gap, slope, passes:
+ * bit-untouched; its d row keeps its final point), and a workgroup with none entered returns at entry.  A problem's results depend on
+ * its own sums only: a model alone gives the bits it gives inside any batch.  No float atomics.
+ * ESPM_EINVAL, before the device is touched: a null pointer (dev_in, q, a_tri with start == 0; t, slope with a pinned model; every
+ * other always), n below 1 or above 65535 x ESPM_CDIAG_BLOCK, n_models outside 1..ESPM_SML_MAX_MODELS, an empty mask or bits at or
+ * above k, a pin[b] that is neither -1 nor a component of mask, tol not positive, s[j] not > 0 (or not finite) for a j in mask,
+ * state_bytes below ESPM_CML_STATE_BYTES(k, n, n_models).  ESPM_EUNSUPPORTED for k outside 1..ESPM_DIAG_MAX_K.  Only the narrow build
+ * has the kernels; the wide builds return ESPM_EUNSUPPORTED.  No espm_mu_state is involved: ESPM_MU_ABI_VERSION stays. */
+#define ESPM_CML_STATE_EXTRA 3   /* rows of state beyond the 2 k of the accepted point and e: dev_acc, tau, trial               */
+#define ESPM_CML_STATE_BYTES(k, n, n_models) ((size_t)(n_models) * (size_t)(2 * (k) + ESPM_CML_STATE_EXTRA) * (size_t)(n) * sizeof(double))
+int espm_channel_ml_step(int n, int k, int n_models, int start, const double* dev_in, const double* q, const double* a_tri,
+                         const double* xsum, const double* s, uint32_t mask, const int32_t* pin, const double* t, double tol, double* d,
+                         void* state, size_t state_bytes, double* dev, double* gap, double* slope, int32_t* passes, uint8_t* done,
+                         uint8_t* active, int64_t* live, espm_stream_t stream);
+
 /* ---- LDS of the sparse H-step (csrc/mu_ell_plan.hpp: plan_h_ell; espm_amd.ell.lds_bytes_h, the store choice of espm_amd.store) ----
  * Dynamic LDS, in bytes, that the H-step of the sparse count store (x_dtype = ESPM_X_ELL) takes for n_pad channels and k components
  * at the full tile (tile_px = ESPM_ELL_TILE) without the copy of colsum(GW') that a riding W tail adds: the G W table plus the

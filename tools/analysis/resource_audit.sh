@@ -12,7 +12,7 @@ run() { /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c -I $R/
 run mu_w_accum "" w_accum & run mu_w_reduce "" w_reduce & run mu_w_exchange "" w_exchange & run mu_w_finish "" w_finish & run mu_w_dict "" w_dict & run mu_aux "" aux & run mu_ell "" ell & run mu_fused "" fused & run mu_fused_plain "" plain & run mu_fused_stream "" stream & run mu_l2 "" l2 &
 wait
 for i in 0 1 2 3; do run mu_h_step "-DESPM_H_PARTS=4 -DESPM_H_PART=$i" h$i & done
-run mu_ell_build "" build & run mu_init "" init & run mu_xchg "" xchg & run mu_diag "" diag & run mu_diag_chan "" diag_chan & run mu_binning "" binning & run mu_split "" split & run mu_sample "" sample & run mu_attrib "" attrib & run mu_marginals "" marginals & run mu_residual "" residual & run mu_pixel_ml "" pixel_ml & run mu_pixel_ml_newton "" pixel_ml_newton & run mu_pixel_ml_pinned "" pixel_ml_pinned & run mu_pixel_ml_simplex "" pixel_ml_simplex & run mu_spectra_ml "" spectra_ml &
+run mu_ell_build "" build & run mu_init "" init & run mu_xchg "" xchg & run mu_diag "" diag & run mu_diag_chan "" diag_chan & run mu_binning "" binning & run mu_split "" split & run mu_sample "" sample & run mu_attrib "" attrib & run mu_marginals "" marginals & run mu_residual "" residual & run mu_pixel_ml "" pixel_ml & run mu_pixel_ml_newton "" pixel_ml_newton & run mu_pixel_ml_pinned "" pixel_ml_pinned & run mu_pixel_ml_simplex "" pixel_ml_simplex & run mu_spectra_ml "" spectra_ml & run mu_channel_ml "" channel_ml &
 for i in 0 1; do run mu_h_chain "-DESPM_CHAIN_PARTS=2 -DESPM_CHAIN_PART=$i" chain$i & done
 wait
 python3 - "$O" > "$OUT" <<'PY'
