@@ -108,6 +108,8 @@ class MUEngine:
         block of image rows and ``shape_2d`` its local (rows, ny).
     x_facts : ``store.XFacts``, what the caller already knows about X exactly as handed over; discarded when a group is given
         or fix_zero_lines is set.
+    tile_px, x_tile, w_blocks : (tests, tuning) the H-step's pixel tile, the pixel-block width of the channel-major X and - dense stores
+        only - the number of pixel blocks of the W accumulation, instead of what ``espm_mu_query`` picks for the image's size.
     precision : "fp32" (default) or "fp64" - the latter constructs ``engine_fp64.MUEngineF64`` (every array and operation in
         fp64, the reference's simplex bisection; one GPU, 1..8 components).
     """
@@ -123,7 +125,7 @@ class MUEngine:
                  epsilon_reg=1.0, simplex_H=False, simplex_W=True, log_shift=1e-14, dicotomy_tol=1e-5,
                  tol=1e-4, sigmaL=8.0, fixed_H=None, fixed_W=None, simplex_rows=None, xscale=1.0,
                  x_store="auto", max_iter=200, device=None, group=None, compute_loss=True,
-                 fix_zero_lines=True, gw_floor=1e-30, x_tile=None, tile_px=None, h_variant=None, bregman=False, h_rule=0, pg_gamma_w=0.0,
+                 fix_zero_lines=True, gw_floor=1e-30, x_tile=None, tile_px=None, w_blocks=None, h_variant=None, bregman=False, h_rule=0, pg_gamma_w=0.0,
                  filled_channels=None, filled_pixels=None, frobenius=False, fused=True, force_sharded=False, autotune=False, x_facts=None,
                  precision="fp32"):
         if precision != "fp32":   # ("fp64" constructs MUEngineF64 in __new__)
@@ -158,7 +160,7 @@ class MUEngine:
         self.x_store, self.x_store_note, self.n_heavy, nnz, refill = self._select_store(
             Xd, layout, x_store, x_facts, empty_ch, empty_px, log_shift, h_rule, pg_gamma_w,
             filled_channels is not None or filled_pixels is not None)
-        st = self.st = self._geometry(shape_2d, tile_px, x_tile)
+        st = self.st = self._geometry(shape_2d, tile_px, x_tile, w_blocks)
         self._build_store(Xd, layout, self.n_heavy, nnz, empty_px)
         if refill:
             _set_lines(Xd, layout, empty_px, empty_ch, log_shift)
@@ -296,8 +298,8 @@ class MUEngine:
             raise ValueError("x_store must be 'auto', 'ell', 'u8', 'bf16' or 'f32'")
         return x_store, note, n_heavy, nnz, refill
 
-    def _geometry(self, shape_2d, tile_px, x_tile):
-        """The MUState with the problem's sizes and the tiling espm_mu_query gives them (tile_px / x_tile override it)."""
+    def _geometry(self, shape_2d, tile_px, x_tile, w_blocks=None):
+        """The MUState with the problem's sizes and the tiling espm_mu_query gives them (tile_px / x_tile / w_blocks override it)."""
         p, x_store = self.p, self.x_store
         st = MUState()
         st.n, st.p, st.k = self.n, p, self.k
@@ -323,6 +325,14 @@ class MUEngine:
                 st.x_tile = int(tile_px)
             if x_tile is not None:
                 st.x_tile = int(x_tile)
+        if w_blocks is not None:  # override the pixel blocks of the W accumulation chosen by espm_mu_query (tests, tuning): dense stores
+            if x_store == "ell":
+                raise ValueError("w_blocks is for the dense stores: the sparse store's blocks are fixed by ell_pb (two H tiles)")
+            most = (p + 15) // 16   # (the most espm_mu_query itself gives an image)
+            if not 1 <= int(w_blocks) <= most:
+                raise ValueError(f"w_blocks={w_blocks} must be 1..{most} (ceil(p / 16)) for the {p} pixels of X")
+            ppb = (p + int(w_blocks) - 1) // int(w_blocks)   # (the query's arithmetic: whole pixels per block, then the blocks that leaves)
+            st.nblk_w = (p + ppb - 1) // ppb
         p_total = torch.tensor([p], dtype=torch.int64, device=self.device)
         if self.group is not None:
             torch.distributed.all_reduce(p_total, group=self.group)

@@ -370,13 +370,19 @@ from espm_amd.engine import MUEngine
 store, k, lam, mode, n_it = sys.argv[2], int(sys.argv[3]), float(sys.argv[4]), sys.argv[5], int(sys.argv[6])
 rng = np.random.default_rng(7)
 n, nx, ny = 64, 40, 36
+tile_px = None
+if len(sys.argv) > 7:   # another geometry: tile_px, n, nx, ny (tests/test_gpu_dense_geometry.py)
+    tile_px, n, nx, ny = (int(v) for v in sys.argv[7:11])
 W = rng.random((n, k)) + 0.05
 H = rng.random((k, nx * ny)) + 0.05
 H /= H.sum(axis=0, keepdims=True)
 X = rng.poisson((0.3 if store == "ell" else 6.0) * n * (W / W.sum(axis=0)) @ H).astype(np.float64)
 if store == "u8":
     X = np.minimum(X, 255.0)
-eng = MUEngine(X, k, shape_2d=(nx, ny), lambda_L=lam, mu=0.1, simplex_H=True, simplex_W=False, tol=1e-4, max_iter=n_it + 2, device="cuda:0")
+if store == "f32":
+    X = X * (0.5 + rng.random(X.shape))
+eng = MUEngine(X, k, shape_2d=(nx, ny), lambda_L=lam, mu=0.1, simplex_H=True, simplex_W=False, tol=1e-4, max_iter=n_it + 2, device="cuda:0",
+               tile_px=tile_px)
 assert eng.x_store == store, eng.x_store
 H0 = np.full((k, nx * ny), 1.0 / k)
 eng.load_state(W, H0)
@@ -392,17 +398,18 @@ else:
 torch.cuda.synchronize()
 same = all(bool((a == b).all()) for a, b in zip(held, (eng.w[eng.st.cur], eng.gw_s, eng.colsum_gw)))
 hist = eng.hist[:n_it + 1].cpu().numpy()
-print(json.dumps(dict(chain=int(chain), held=same, it=int(eng.st.it), h=hashlib.sha256(eng.get_H().tobytes()).hexdigest(),
+print(json.dumps(dict(chain=int(chain), held=same, it=int(eng.st.it), tile_px=int(eng.st.tile_px), store=eng.x_store, h=hashlib.sha256(eng.get_H().tobytes()).hexdigest(),
                       hist=hashlib.sha256(hist.tobytes()).hexdigest(), hstat=hashlib.sha256(eng.hstat[eng.st.cur].cpu().numpy().tobytes()).hexdigest(),
                       loss_last=float(eng.history()["loss"][-1]))))
 """
 
 
-def _child(store, k, lam, mode, n_it=9):
+def _child(store, k, lam, mode, n_it=9, geometry=None):
+    """geometry: (tile_px, n, nx, ny) instead of the image's own tile and 64 channels on 40 x 36 pixels."""
     env = dict(os.environ)
     env["ESPM_H_CHAIN"] = "0" if mode == "general" else "1"   # (granular: sequenced by the host, the buffer is not used)
-    out = subprocess.run([sys.executable, "-c", _CHILD, ROOT, store, str(k), str(lam), mode, str(n_it)], env=env, capture_output=True, text=True,
-                         timeout=300)
+    out = subprocess.run([sys.executable, "-c", _CHILD, ROOT, store, str(k), str(lam), mode, str(n_it)] + [str(v) for v in geometry or ()], env=env,
+                         capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     import json
     return json.loads(out.stdout.strip().splitlines()[-1])
